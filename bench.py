@@ -77,6 +77,13 @@ def parse_args():
                     help="frames of the input clip the encoder sees: all of them, as the reference's generate_vid does (default; its rec pass reads those "
                          "codes), or only the conditioning frames synthesis reads (the default line carries that figure as `encode_cond_only`)")
     ap.add_argument("--no-encode-cond-leg", action="store_true", help="skip the second timed pass (same K batches) with only the conditioning frames encoded")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="after the timed steps also run the side measurements (alone passes, single call, kernel probes, the other-noise / "
+                         "cond-only / strict-f32 legs over the same K batches, cpu_baseline) and print the full line; without it the run is "
+                         "the warm-up, the K timed steps and the self-check of batch 0, and the line holds the headline fields only")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB in all: "
+                         "a fixed, seeded sample of an array that does not fit)")
     return ap.parse_args()
 
 
@@ -405,6 +412,50 @@ def conv_traffic(args, kind, launches):
     return r
 
 
+# the line without --diagnostics: the measurement, how it was taken, and the self-check of the timed path (plus the ranks and
+# backend of `multi_gpu`)
+HEADLINE_KEYS = ("metric", "value", "unit", "per_gpu", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                 "dtype", "data", "config", "self_check", "stage_ms_per_step", "latency_ms_per_batch", "hbm_peak_allocated_gb", "outputs")
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # the files on disk, .npy headers included
+DUMP_HEADER_BYTES = 1024             # room left per file for its .npy header (numpy writes 128 bytes for these)
+DUMP_SAMPLE_SEED = 12345
+DUMP_MIN_SHARE = 4 * 2 ** 20     # every later array keeps at least this much of the limit (or all of itself)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write `arrays` ([(name, tensor)], in priority order) as out_dir/<name>.npy: integers wider than 16 bits as float64,
+    everything else as float32 (both exact).  An array that does not fit in what is left of DUMP_LIMIT_BYTES is written as a fixed, seeded sample of its
+    flattened elements (sorted indices drawn from DUMP_SAMPLE_SEED: the same shape gives the same sample).  The files, headers
+    included, stay within DUMP_LIMIT_BYTES.  Returns the manifest."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = []
+    for name, t in arrays:
+        t = t.detach().cpu()
+        wide_int = not t.is_floating_point() and t.element_size() > 2     # exact in float64 only (uint8 pixels are exact in float32)
+        t = t.to(torch.float64 if wide_int else torch.float32)
+        host.append((name, t))
+    left, manifest = DUMP_LIMIT_BYTES - DUMP_HEADER_BYTES * len(host), {}
+    for i, (name, t) in enumerate(host):
+        item = t.element_size()
+        reserve = sum(min(u.numel() * u.element_size(), DUMP_MIN_SHARE) for _, u in host[i + 1:])
+        n = min(t.numel(), max(0, left - reserve) // item)
+        if n <= 0:
+            manifest[name] = {"shape": list(t.shape), "written": 0}
+            continue
+        flat = t.reshape(-1)
+        if n < t.numel():
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randperm(t.numel(), generator=g)[:n].sort().values
+            flat = flat[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.numpy() if n < t.numel() else t.numpy())
+        left -= n * item
+        manifest[name] = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "written": int(n),
+                          "sampled": bool(n < t.numel())}
+    return manifest
+
+
 def main():
     args = parse_args()
     if args.sample_noise is None:
@@ -450,6 +501,8 @@ def main():
             """uint8 pack on the decode stream, then the RCCL all-gather on a side stream (it overlaps the next batch)."""
             if step == kept.get("step"):     # the self-check below compares this batch with a serial run of the same inputs
                 kept["fake"] = fake
+            if step == kept.get("last_step"):   # --dump-outputs: what the timed path computed in its last step
+                kept["last_fake"] = fake
             return engine.all_gather_clips_async(ops.pack_u8(fake["vid"]))
 
         rank_seed = noise_seed_of_rank(engine.rank)    # this rank's own stream (rank 0: NOISE_SEED, as every round so far)
@@ -486,6 +539,7 @@ def main():
         batches = [make_batch(i) for i in range(args.steps)]   # inputs resident in HBM before the clock starts
         timer = ops.KernelTimer()
         kept["step"] = 0
+        kept["last_step"] = args.steps - 1 if args.dump_outputs else None
         torch.cuda.synchronize()
         engine.barrier()
         ops.KERNEL_TIMER = timer
@@ -496,7 +550,14 @@ def main():
         elapsed = engine.all_reduce_max(time.perf_counter() - t0)
         ops.KERNEL_TIMER = None
         kept["step"] = None
+        kept["last_step"] = None
         assert clips.shape[0] == args.batch * world
+        dumped = None
+        if args.dump_outputs and engine.is_main:
+            last = kept.pop("last_fake")
+            dumped = {"dir": args.dump_outputs, "step": args.steps - 1,
+                      "arrays": dump_outputs(args.dump_outputs, [("code", last["code"]), ("vid", last["vid"]), ("clips_u8", clips)])}
+            del last
 
         # per-rank stage times (rank order) for the line: which rank, and which stage of it, bounds a multi-GPU run
         rank_stages = [{k: v / args.steps for k, v in stage.items() if k not in ("timeline", "token_groups")}]
@@ -518,7 +579,7 @@ def main():
             # its own: 266-267 every time, tools/r05/alone_var.py) -- the first pass runs into whatever the timed region left behind
             # (clock state; worker threads winding down on the host side of the launch-bound small convolutions).
             passes, serial_call_s = [], []
-            for _ in range(3):       # ALONE_PASSES
+            for _ in range(3 if args.diagnostics else 1):       # ALONE_PASSES (without --diagnostics: the self-check pass only)
                 timer_p = ops.KernelTimer()
                 ops.KERNEL_TIMER = timer_p
                 torch.manual_seed(rank_seed)
@@ -551,7 +612,7 @@ def main():
             # reference's order (token loop, then decode); the same call with the decoder following its own token loop frame by frame
             # (schedule="stream", the default of generate_vid since round 6): one untimed call (its decode step's capture key), two timed
             stream_call_s, same_stream = [], None
-            for rep in range(3):
+            for rep in range(3 if args.diagnostics else 0):
                 torch.manual_seed(rank_seed)
                 torch.cuda.synchronize()
                 t_call = time.perf_counter()
@@ -562,7 +623,7 @@ def main():
                 else:
                     same_stream = bool(torch.equal(out_q["fake"]["code"], out_s["fake"]["code"]) and torch.equal(out_q["fake"]["vid"], out_s["fake"]["vid"]))
                 del out_q
-            single_call = {"serial_frames_per_s": predicted * args.batch / min(serial_call_s), "stream_frames_per_s": predicted * args.batch / min(stream_call_s),
+            single_call = None if not stream_call_s else {"serial_frames_per_s": predicted * args.batch / min(serial_call_s), "stream_frames_per_s": predicted * args.batch / min(stream_call_s),
                            "serial_ms_per_call": [round(1e3 * v) for v in serial_call_s], "stream_ms_per_call": [round(1e3 * v) for v in stream_call_s],
                            "stream_equals_serial": same_stream,
                            "note": "Generator.generate_vid on ONE batch with nothing else in flight, wall time per call (best of the calls listed): `serial` = encode, "
@@ -728,7 +789,7 @@ def main():
                 "note": "HIP events on each token stream around the whole loop of every token group of the timed region (prefill of the conditioning frame "
                         "included); bytes = weights counted ONCE per step + mean KV bytes of every batch in the group; `frac` is ONE loop's stream while "
                         "`concurrent_token_loops` loops and the decoder share the memory system (aggregate_frac = loops x frac)"}
-            if args.schedule == "pipelined" and args.config in ("bair", "bair-p2p", "kinetics"):
+            if args.diagnostics and args.schedule == "pipelined" and args.config in ("bair", "bair-p2p", "kinetics"):
                 # the same token loop with the chip to itself (per step, alone against in-run): one whole loop over the
                 # stacked rows of a full token group, graph-replayed, in-kernel noise, outside the timed region
                 g_rows = max(1, int(round(mean_group))) * args.batch
@@ -765,37 +826,39 @@ def main():
                                     "note": "algorithmic bytes per batch of the token loops (weights once per step of a group + keys and values) and of the "
                                             "decoder's convolutions over the measured step time; the stencil kernels of the decoder (~0.43 TB per BAIR batch, "
                                             "profiles/r04_pmc_decoder_kernels.txt) and the encoder come on top -- DESIGN.md 4.3"}
-            line["roofline_decode_kernels"] = decode_kernel_rooflines(gen, xopt, args.batch)
+            if args.diagnostics:
+                line["roofline_decode_kernels"] = decode_kernel_rooflines(gen, xopt, args.batch)
             # The top kernel by time (VERDICT r5, weak 6 / line hygiene 9): the decode GEMM as ONE entry -- its launches of a step stream the
             # step's weights once: bytes per launch = weights / launches; `alone` from the token-loop probe above is per step, so the
             # per-launch figure here is measured live on the stacked rows of a token group with every layer's OWN weights (HBM-cold,
             # unlike roofline_decode_kernels' warm re-launches); in-run duration and L2 requests are rocprofv3's (committed record).
-            n_gemm = 4 * len(net_t.blocks) + 1
-            g16 = {"kernel": "gemm16_kernel<WNT, RB, CB, U> (every GEMM of a decode step: ln1+qkv, proj, ln2+fc, fc2 per layer, ln_f+head)",
-                   "bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s", "launches_per_step": n_gemm,
-                   "algorithmic_bytes_per_launch": w_bytes / n_gemm,
-                   "note": "weights only (the activations of 16-128 rows are KBs and L2-resident); one step = one pass over the weights for every batch of the token group"}
-            try:
-                rows_g = max(1, int(round(mean_group))) * args.batch
-                us_alone = gemm16_alone_us(gen, rows_g)
-                g16["alone"] = {"rows": rows_g, "avg_launch_us": us_alone, "achieved": w_bytes / n_gemm / (us_alone * 1e-6) / 1e9,
-                                "frac": w_bytes / n_gemm / (us_alone * 1e-6) / 1e9 / HBM_PEAK_GBPS,
-                                "measured": "HIP events around a hipGraph of the step's GEMMs over ALL layers (each launch its own layer's weights: 1.2 GB per "
-                                            "pass, nothing re-read from cache), nothing beside it; attention / embed / pick left out"}
-                g16["achieved"], g16["frac"] = g16["alone"]["achieved"], g16["alone"]["frac"]
-            except Exception as exc:   # never lose the line to a side measurement
-                g16["alone"] = {"error": repr(exc)}
-            prof = gemm16_profile(args)
-            if prof:
-                by = w_bytes / n_gemm
-                g16["in_run"] = {"avg_launch_us": prof["in_run_avg_us"], "achieved": by / (prof["in_run_avg_us"] * 1e-6) / 1e9,
-                                 "frac": by / (prof["in_run_avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS, "rows": prof["rows"], "source": prof["in_run_source"],
-                                 "not_measured_by_this_command": True}
-                g16["l2"] = {"read_requests_per_launch": prof["l2_read_requests_per_launch"],
-                             "bytes_through_the_cu_l2_path_per_launch": prof["l2_read_requests_per_launch"] * prof["l2_request_bytes"],
-                             "over_algorithmic": prof["l2_read_requests_per_launch"] * prof["l2_request_bytes"] / by,
-                             "hbm_fetch_over_algorithmic": prof["hbm_fetch_bytes_per_launch"] / by, "source": prof["counters_source"]}
-            line["roofline_gemm16"] = g16
+            if args.diagnostics:
+                n_gemm = 4 * len(net_t.blocks) + 1
+                g16 = {"kernel": "gemm16_kernel<WNT, RB, CB, U> (every GEMM of a decode step: ln1+qkv, proj, ln2+fc, fc2 per layer, ln_f+head)",
+                       "bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s", "launches_per_step": n_gemm,
+                       "algorithmic_bytes_per_launch": w_bytes / n_gemm,
+                       "note": "weights only (the activations of 16-128 rows are KBs and L2-resident); one step = one pass over the weights for every batch of the token group"}
+                try:
+                    rows_g = max(1, int(round(mean_group))) * args.batch
+                    us_alone = gemm16_alone_us(gen, rows_g)
+                    g16["alone"] = {"rows": rows_g, "avg_launch_us": us_alone, "achieved": w_bytes / n_gemm / (us_alone * 1e-6) / 1e9,
+                                    "frac": w_bytes / n_gemm / (us_alone * 1e-6) / 1e9 / HBM_PEAK_GBPS,
+                                    "measured": "HIP events around a hipGraph of the step's GEMMs over ALL layers (each launch its own layer's weights: 1.2 GB per "
+                                                "pass, nothing re-read from cache), nothing beside it; attention / embed / pick left out"}
+                    g16["achieved"], g16["frac"] = g16["alone"]["achieved"], g16["alone"]["frac"]
+                except Exception as exc:   # never lose the line to a side measurement
+                    g16["alone"] = {"error": repr(exc)}
+                prof = gemm16_profile(args)
+                if prof:
+                    by = w_bytes / n_gemm
+                    g16["in_run"] = {"avg_launch_us": prof["in_run_avg_us"], "achieved": by / (prof["in_run_avg_us"] * 1e-6) / 1e9,
+                                     "frac": by / (prof["in_run_avg_us"] * 1e-6) / 1e9 / HBM_PEAK_GBPS, "rows": prof["rows"], "source": prof["in_run_source"],
+                                     "not_measured_by_this_command": True}
+                    g16["l2"] = {"read_requests_per_launch": prof["l2_read_requests_per_launch"],
+                                 "bytes_through_the_cu_l2_path_per_launch": prof["l2_read_requests_per_launch"] * prof["l2_request_bytes"],
+                                 "over_algorithmic": prof["l2_read_requests_per_launch"] * prof["l2_request_bytes"] / by,
+                                 "hbm_fetch_over_algorithmic": prof["hbm_fetch_bytes_per_launch"] / by, "source": prof["counters_source"]}
+                line["roofline_gemm16"] = g16
             line["multi_gpu"] = {"rccl_ranks": (torch.distributed.get_world_size() if engine.distributed else 1), "backend": engine.backend if engine.distributed else None,
                                  "stage_ms_per_step_by_rank": rank_stages,
                                  "host_threads_per_rank": {"torch_intra_op": torch.get_num_threads(), "launch_threads": 1 + (gen.last_chains if args.schedule == "pipelined" else 0),
@@ -810,7 +873,7 @@ def main():
                                                   "this run is one line for N = " + str(world) + "; the N > 1 path is covered by code, by the world-2 gloo tests and by "
                                                   "tools/host_stress.py (profiles/r06_host_stress.txt: 8 ranks' host work side by side, no GPU) -- the driver derives "
                                                   "efficiency from the N = 1, 2, 4, 8 lines when a node exists (tools/scale_sweep.sh runs them)"}
-            if args.encode == "all" and args.config == "bair" and world == 1 and not args.no_encode_cond_leg and not args.rec_pass:
+            if args.diagnostics and args.encode == "all" and args.config == "bair" and world == 1 and not args.no_encode_cond_leg and not args.rec_pass:
                 # the same K batches and schedule with only the conditioning frame of every clip encoded: synthesis reads nothing else
                 # ("from conditioning frames resident on GPU"); the reference also encodes the 15 frames it is about to
                 # replace, for its rec pass, and that is what `value` above includes.  Reported beside it, never as `value`.
@@ -829,7 +892,7 @@ def main():
                                                         "the synthesized clips are the same bits (tests/test_features_gpu.py::test_encode_conditioning_frames_only)"}
                 finally:
                     xopt.encode_all = True
-            if args.config == "bair" and world == 1 and not args.no_other_noise_leg and args.schedule == "pipelined" and not args.rec_pass:
+            if args.diagnostics and args.config == "bair" and world == 1 and not args.no_other_noise_leg and args.schedule == "pipelined" and not args.rec_pass:
                 # the same K batches and schedule with the OTHER noise source: reference-seed sampling (host) must cost the schedule nothing
                 other = "device" if args.sample_noise == "host" else "host"
                 trs = [gen.transformer_model] + [tr_ for tr_, _ in gen._chains]
@@ -851,7 +914,7 @@ def main():
                 finally:
                     for tr_ in trs:
                         tr_.sample_noise = args.sample_noise
-            if args.config == "bair" and world == 1 and not args.conv_precision and not args.no_strict_f32:
+            if args.diagnostics and args.config == "bair" and world == 1 and not args.conv_precision and not args.no_strict_f32:
                 # the same path with EXACT fp32 convolutions (v_mfma_f32_32x32x2_f32 instead of the split-bf16 products): what the
                 # arithmetic choice of `dtype` buys, on the SAME schedule and the same K batches, in the driver's own line; plus the
                 # one B = 16 comparison of the two arithmetics: timed batch 0 decoded by both (GPU vs GPU, teacher-forced on the
@@ -899,8 +962,14 @@ def main():
                 finally:
                     ops.CONV_PRECISION = kind
                     ops.KERNEL_TIMER = None
-            if not args.no_cpu_baseline and args.config == "bair" and world == 1:   # rank 0 at N = 1 only
+            if args.diagnostics and not args.no_cpu_baseline and args.config == "bair" and world == 1:   # rank 0 at N = 1 only
                 line["cpu_baseline"] = cpu_baseline(gen, opt)
+            if dumped:
+                line["outputs"] = dumped
+            if not args.diagnostics:
+                full = line
+                line = {k: full[k] for k in HEADLINE_KEYS if k in full}
+                line["multi_gpu"] = {k: full["multi_gpu"][k] for k in ("rccl_ranks", "backend")}
             print(json.dumps(line))
 
 

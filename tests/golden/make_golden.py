@@ -1,7 +1,7 @@
 """Generate the golden fixtures under tests/golden/ from the imported reference.
 
-Run in the build container only (needs /root/reference):
-    python tests/golden/make_golden.py
+Needs a checkout of the upstream reference:
+    CCVS_REFERENCE_ROOT=<reference checkout> python tests/golden/make_golden.py [ops tiny ... refchecks]
 It imports the upstream reference through `ref_harness` (stubs, CPU), runs the
 reference's own modules on seeded inputs and stores inputs, weights (reference
 `state_dict()` layouts) and outputs as `.npz`.  The fixtures are DATA; no reference
@@ -378,6 +378,95 @@ def tiny_keep_first(ns):
     print("  wrote tiny_keepfirst.npz")
 
 
+def reference_checks(ns):
+    """The reference outputs tests/test_oracle_vs_reference.py compares the oracle with: encoder / decoder with fresh weights,
+    the GPT with spatio-temporal and flat positions, the bytes of `save_video_batch` (helpers/generator.py:285-333,
+    `torchvision.io.write_video` replaced by a recorder), and what the reference's own parser gives for the nine
+    `scripts/*/save_videos*.sh` launch lines (reference_launch_lines.json).  The weights are not stored: every entry is
+    re-drawn by `rh.seeded_weights` with the mean and std the reference's initialiser gave it, and the spec goes into
+    reference_checks.json; the uint8 outputs are stored as SHA-256 digests of their bytes."""
+    import hashlib
+    import importlib
+    import json
+    import tempfile
+    import torchvision
+    arrays, meta = {}, {}
+
+    def seed_module(module, key, seed):
+        spec = rh.weight_spec(module)
+        with torch.no_grad():
+            for name, t in rh.seeded_weights(spec, seed).items():
+                module.state_dict()[name].copy_(t)
+        meta[key] = {"seed": seed, "spec": spec}
+
+    opt = rh.parse_reference_options(rh.TINY_ARGV)["qvid_generator"]
+    torch.manual_seed(123)
+    enc, dec = ns.sae.SkipGANEncoder(opt), ns.sae.SkipGANDecoder(opt)
+    seed_module(enc, "fresh/enc", 1000)
+    seed_module(dec, "fresh/dec", 2000)
+    vid = torch.rand(1, 2, 3, 32, 32) * 2 - 1
+    with torch.no_grad():
+        z, inter = enc(vid)
+        ctx = [[f[:, :1] for f in inter], [f[:, 1:] for f in inter]]
+        rgb, _, flows, occs, _ = dec(z[:, :1].contiguous(), ctx, return_all=True, inter_pre_warping=False)
+        oz, _ = O.encoder_forward(rh.seeded_weights(meta["fresh/enc"]["spec"], 1000), opt, vid)
+        report("fresh/z", oz, z)
+        report("fresh/rgb", O.decoder_forward(rh.seeded_weights(meta["fresh/dec"]["spec"], 2000), opt, z[:, :1].contiguous(), ctx,
+                                              return_all=True)[0], rgb)
+    assert torch.isfinite(rgb).all() and rgb.abs().max() > 0
+    arrays["fresh/vid"], arrays["fresh/z"], arrays["fresh/rgb"] = vid.numpy(), z.numpy(), rgb.numpy()
+    arrays["fresh/n_inter"], arrays["fresh/n_flows"] = np.array(len(inter)), np.array(len(flows))
+    for i, f in enumerate(inter):
+        arrays[f"fresh/inter{i}"] = f.numpy()
+    for i, f in enumerate(flows + occs):
+        arrays[f"fresh/flow_occ{i}"] = f.numpy()
+
+    torch.manual_seed(5)
+    for k, mode in enumerate(("spatio-temporal", None)):
+        tag = f"gpt_{mode or 'flat'}"
+        gpt = ns.mingpt.GPT(vocab_size=30, block_size=48, num_blocks=3, n_layer=1, n_head=2, n_embd=32, emb_mode=mode, shape=[4, 4])
+        with torch.no_grad():
+            for n, p in gpt.named_parameters():
+                if n.endswith("_emb"):
+                    p.normal_(0, 0.1)
+            seed_module(gpt, tag, 3000 + 100 * k)
+            idx = torch.randint(0, 30, (2, 21))
+            y = gpt(idx)
+        arrays[f"{tag}/idx"], arrays[f"{tag}/logits"] = idx.numpy(), y.numpy()
+        sd = dict(gpt.state_dict())
+        report(f"{tag}/logits", O.gpt_forward(sd, O.namespace(z_shape=[4, 4], emb_mode=mode, n_layer=1, n_head=2, z_len=48), idx), y)
+
+    g = importlib.import_module("helpers.generator")
+    got = []
+    torchvision.io.write_video = lambda fn, v, fps: got.append((os.path.basename(fn), v.clone()))
+    g.torchvision = torchvision
+    vid = torch.rand(2, 3, 3, 64, 64, generator=torch.Generator().manual_seed(1)) * 2.4 - 1.2
+    state = torch.tensor([[[0.5, 0.25]] * 3, [[0.999, 0.0]] * 3])      # the second marker sits in a corner: clipped cross
+    saved = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for tag, args, kw in (("bair_state", (2, 3, tmp, 4, True, False, [-1, 1], "bair"), {"state": state}),
+                              ("bairhd", (2, 0, tmp, 4, True, False, [-1, 1], "bairhd"), {}),
+                              ("kinetics600", (2, 0, tmp, 4, True, True, [-1, 1], "kinetics600"), {})):
+            got.clear()
+            g.save_video_batch(vid.clone(), *args, **kw)
+            u8 = torch.stack([v for _, v in got]).contiguous()
+            saved[tag] = {"names": [n for n, _ in got], "shape": list(u8.shape), "dtype": str(u8.dtype),
+                          "sha256": hashlib.sha256(u8.numpy().tobytes()).hexdigest()}
+    meta["save_video_batch"] = saved
+    np.savez_compressed(os.path.join(HERE, "reference_checks.npz"), **arrays)
+    print("  wrote reference_checks.npz", sum(a.nbytes for a in arrays.values()) / 1e6, "MB raw")
+
+    lines = json.load(open(os.path.join(HERE, "reference_launch_lines.json")))
+    parsed = {}
+    for script, argv in lines.items():
+        want = rh.parse_reference_options(argv)
+        parsed[script] = {k: {f: getattr(want[k], f) for f in fields if hasattr(want[k], f)}
+                          for k, fields in rh.LAUNCH_LINE_FIELDS.items() if want.get(k) is not None}
+    meta["launch_lines"] = parsed
+    json.dump(meta, open(os.path.join(HERE, "reference_checks.json"), "w"), sort_keys=True, separators=(",", ":"))
+    print("  wrote reference_checks.json:", len(parsed), "launch lines")
+
+
 def op_fixtures(ns):
     """Per-op vectors at a few real channel counts on small maps."""
     sae = ns.sae
@@ -522,7 +611,7 @@ def op_fixtures(ns):
 
 if __name__ == "__main__":
     ns = rh.load_reference()
-    which = sys.argv[1:] or ["ops", "tiny", "state", "statefront", "keepfirst", "statemodel", "beam", "prefix"]
+    which = sys.argv[1:] or ["ops", "tiny", "state", "statefront", "keepfirst", "statemodel", "beam", "prefix", "refchecks"]
     if "ops" in which:
         print("== op fixtures")
         op_fixtures(ns)
@@ -547,3 +636,6 @@ if __name__ == "__main__":
     if "keepfirst" in which:
         print("== tiny keep_first ring")
         tiny_keep_first(ns)
+    if "refchecks" in which:
+        print("== reference checks")
+        reference_checks(ns)

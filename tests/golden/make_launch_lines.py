@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Writes tests/golden/reference_launch_lines.json: the argument vectors of the reference's nine `scripts/*/save_videos*.sh`
 launch lines (everything after `helpers/generator.py`, ${GPU_IDS} -> 0).  Data for tests/test_reference_scripts_gpu.py, which
-runs on a box without the reference tree.   python tests/golden/make_launch_lines.py"""
+runs without the reference tree.   CCVS_REFERENCE_ROOT=<reference checkout> python tests/golden/make_launch_lines.py"""
 import glob
 import json
 import os
 import re
 import shlex
 
-REF = os.environ.get("CCVS_REFERENCE_ROOT", "/root/reference")
+REF = os.environ["CCVS_REFERENCE_ROOT"]
 out = {}
 for path in sorted(glob.glob(os.path.join(REF, "scripts", "*", "save_videos*.sh"))):
     body = open(path).read().split("helpers/generator.py", 1)[1].replace("\\\n", " ")

@@ -1,10 +1,9 @@
-"""Import the upstream CCVS reference on CPU (this container only).
+"""Import the upstream CCVS reference on CPU, from a checkout named by CCVS_REFERENCE_ROOT.
 
-TEST INFRASTRUCTURE.  Never imported by the product (`ccvs_amd/`), by `bench.py`
-or by any `-m gpu` test: `/root/reference` does not exist on the GPU box.  It is
-used by `tests/golden/make_golden.py` to produce the committed `.npz` fixtures and
-by the `not gpu` test `tests/test_oracle_vs_reference.py` (skipped when the
-reference tree is absent).
+FIXTURE INFRASTRUCTURE.  Never imported by the product (`ccvs_amd/`) or by `bench.py`;
+the tests import it only for the tiny launch lines below (`TINY_ARGV` ...) and never
+load the reference.  `tests/golden/make_golden.py` loads the reference through it to
+produce the committed fixtures under tests/golden/.
 
 The reference hard-codes `.cuda()`, JIT-builds two CUDA extensions at import and
 uses a cupy kernel for the cost volume.  The recipe here:
@@ -27,11 +26,11 @@ import contextlib
 
 import torch
 
-REF_ROOT = os.environ.get("CCVS_REFERENCE_ROOT", "/root/reference")
+REF_ROOT = os.environ.get("CCVS_REFERENCE_ROOT", "")
 
 
 def reference_available():
-    return os.path.isdir(os.path.join(REF_ROOT, "models", "skip_vid_generator"))
+    return bool(REF_ROOT) and os.path.isdir(os.path.join(REF_ROOT, "models", "skip_vid_generator"))
 
 
 def _stub(name, **attrs):
@@ -74,7 +73,7 @@ def load_reference():
     """Returns a namespace with the reference classes, importing them once."""
     if _LOADED:
         return _LOADED["ns"]
-    assert reference_available(), f"reference tree not found at {REF_ROOT}"
+    assert reference_available(), f"reference tree not found at CCVS_REFERENCE_ROOT={REF_ROOT!r}"
 
     class _Any:
         def __init__(self, *a, **k):
@@ -171,6 +170,39 @@ def patched_overlapping_shift():
         yield
     finally:
         torch.Tensor.__setitem__ = orig
+
+
+def seeded_weights(spec, seed):
+    """spec: [[name, shape, mean, std], ...] -> {name: tensor}.  Entry i is randn(shape) drawn from a generator seeded with
+    seed + i, times std, plus mean: weights a fixture can name by their spec instead of storing them."""
+    out = {}
+    for i, (name, shape, mean, std) in enumerate(spec):
+        g = torch.Generator().manual_seed(seed + i)
+        out[name] = torch.randn(list(shape), generator=g) * std + mean
+    return out
+
+
+def weight_spec(module, skip=(".kernel", ".mask")):
+    """The spec of `seeded_weights` for every floating-point entry of `module.state_dict()` (the fixed blur kernels and causal
+    masks excepted), with the mean and std the module's own initialiser gave the entry."""
+    spec = []
+    for name, t in module.state_dict().items():
+        if name.endswith(skip) or not t.is_floating_point():
+            continue
+        std = float(t.float().std()) if t.numel() > 1 else 0.0
+        spec.append([name, list(t.shape), float(t.float().mean()), std])
+    return spec
+
+
+# the option fields tests/test_oracle_vs_reference.py compares, per launch line: those the synthesis path reads
+LAUNCH_LINE_FIELDS = {
+    "transformer": ["vid_len", "cond_len", "z_len", "z_chunk", "z_num", "z_shape", "state_size", "state_num", "num_blocks", "top_k", "temperature",
+                    "sample", "p2p", "stft", "state", "keep_state", "use_start_token", "cat", "n_layer", "n_head", "n_embd", "emb_mode",
+                    "sample_state", "top_k_state", "temperature_state", "batch_size_vid", "max_dim", "aspect_ratio", "fps", "imagenet_norm"],
+    "qvid_generator": ["necf", "necf_mult", "z_num", "z_size", "z_shape", "skip_context", "skip_memory", "keep_first", "n_first", "use_inter",
+                       "inter_p", "max_dim", "aspect_ratio", "vid_len", "use_ema"],
+    "stft_ae": ["stft_num", "stft_size", "stft_hsize", "stft_shape"],
+}
 
 
 TINY_ARGV = [

@@ -86,3 +86,31 @@ def test_descendants_in_their_own_session_are_killed(tmp_path, monkeypatch, caps
     pid = int(open(str(marker) + ".pid").read())
     time.sleep(0.2)
     assert not psutil.pid_exists(pid) or psutil.Process(pid).status() == psutil.STATUS_ZOMBIE, "the orphaned worker survived"
+
+
+def test_dump_outputs_limit_dtypes_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: wide integers as float64, floats and uint8 as float32, small arrays whole, and an array beyond what is left of the
+    limit written as a sample that is the same from run to run."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64 * 1024)
+    monkeypatch.setattr(bench, "DUMP_MIN_SHARE", 4 * 1024)
+    code = torch.arange(60, dtype=torch.int64).view(3, 20)
+    vid = torch.randn(4, 10000, generator=torch.Generator().manual_seed(0))
+    u8 = torch.arange(256, dtype=torch.uint8).repeat(100)
+    arrays = [("code", code), ("vid", vid), ("clips_u8", u8)]
+    m1 = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    m2 = bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert m1 == m2
+    total = 0
+    for name, t in arrays:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == (np.float64 if name == "code" else np.float32) and np.array_equal(a, b)
+        total += os.path.getsize(tmp_path / "a" / f"{name}.npy")
+        assert m1[name]["written"] == a.size and m1[name]["shape"] == list(t.shape)
+    assert total <= 64 * 1024 and total > 60 * 1024      # the files, headers included, fill the limit without passing it
+    assert np.array_equal(np.load(tmp_path / "a" / "code.npy"), code.double().numpy()) and not m1["code"]["sampled"]
+    assert m1["vid"]["sampled"] and m1["clips_u8"]["written"] > 0
+    sample = np.load(tmp_path / "a" / "vid.npy")
+    assert np.isin(sample, vid.numpy().ravel()).all()

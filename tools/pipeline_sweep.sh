@@ -8,7 +8,7 @@ export CCVS_BENCH_SUPERVISE=0
 for combo in $1; do
   IFS=, read L C R <<< "$combo"
   RAMP=""; [ "$R" != "-" ] && RAMP="--ramp ${R//+/,}"
-  timeout 900 python3 bench.py --steps $STEPS --warmup 4 --no-cpu-baseline --lanes $L --chains $C $RAMP 2>/dev/null | tail -1 > /tmp/line.json
+  timeout 900 python3 bench.py --steps $STEPS --warmup 4 --diagnostics --no-cpu-baseline --lanes $L --chains $C $RAMP 2>/dev/null | tail -1 > /tmp/line.json
   python3 - "$combo" <<'PY'
 import json, sys
 try:
