@@ -8,8 +8,11 @@ MFMA convolution with fused bias / LeakyReLU(0.1) / residual epilogues, FIR resa
 cost volume, back-warp, confidence fusion), and the torch.cat / repeat / one-hot plumbing of
 the reference is replaced by kernels that read and write channel-slice views in place.
 
-Not supported (outside the hot path): layout decoders, skip_rgb / ToRGB,
-deformable conv, trade-off and masked-flow variants, `no_corr`, training.
+The flow-decoder variants of Matching (--q_use_masked_flow, --q_use_deformed_conv, --q_use_tradeoff,
+--q_no_corr) run on their own kernels (deformable convolution on the matrix cores, grouped x2 transposed
+convolution of the trade-off feature, masked-flow / trade-off epilogue).
+
+Not supported (outside the hot path): layout decoders, skip_rgb / ToRGB, training.
 """
 import math
 
@@ -168,30 +171,58 @@ def backwarp(input, flow, backwarp_grid=None):
     return ops.backwarp(input, flow, 1.0)
 
 
-def _check_variants(opt):
-    for flag in ("use_masked_flow", "use_deformed_conv", "use_tradeoff", "no_corr"):
-        if getattr(opt, flag, False):
-            raise NotImplementedError(f"--q_{flag} is outside the MI355X hot path")
+class DeformConv2d(nn.Module):
+    """Parameter holder of torchvision.ops.DeformConv2d(C, C, 3, stride=1, padding=1) (Matching.deform, skip_autoencoder.py:160),
+    torchvision's initialiser; run by `ops.deform_conv3x3` with Matching's one-offset-per-pixel form."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, bias=True):
+        super().__init__()
+        if in_channels != out_channels or kernel_size != 3 or stride != 1 or padding != 1:
+            raise NotImplementedError("DeformConv2d (HIP): only the C -> C 3x3, stride 1, padding 1 form of Matching")
+        self.weight = nn.Parameter(torch.empty(out_channels, in_channels, kernel_size, kernel_size))
+        self.bias = nn.Parameter(torch.empty(out_channels)) if bias else None
+        nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if self.bias is not None:
+            bound = 1 / math.sqrt(in_channels * kernel_size * kernel_size)
+            nn.init.uniform_(self.bias, -bound, bound)
+        self._packed = None
+
+    def packed(self):
+        w = self.weight
+        key = (w.data_ptr(), w._version, w.device, ops.CONV_PRECISION)
+        if self._packed is None or self._packed[0] != key:
+            self._packed = (key, ops.pack_deform_weight(w))
+        return self._packed[1]
 
 
 class Matching(nn.Module):
-    """Coarse flow / occlusion estimate from the 7x7 cost volume (skip_autoencoder.py:131-206)."""
+    """Coarse flow / occlusion estimate from the 7x7 cost volume, or from [input | inter] with `no_corr`
+    (skip_autoencoder.py:131-206).  The parameters are built in the reference's order."""
 
     def __init__(self, flow_mult, kernel, feat_size, use_corr, corr_stride, use_masked_flow, use_deformed_conv,
                  use_tradeoff, no_proj, first):
         super().__init__()
-        if not use_corr or use_masked_flow or use_deformed_conv or use_tradeoff:
-            raise NotImplementedError("Matching (HIP): only the correlation variant is supported")
         self.flow_mult, self.corr_stride, self.first = flow_mult, corr_stride, first
+        self.use_corr, self.use_masked_flow = use_corr, use_masked_flow
+        self.use_deformed_conv, self.use_tradeoff = use_deformed_conv, use_tradeoff
         self.proj = ConvLayer(feat_size, max(16, feat_size // 4), 1) if (feat_size > 16 and not no_proj) else None
+        self.upsample_toff = None
         if first:
             self.upsample_flow = self.upsample_occ = None
         else:
             self.upsample_flow = nn.ConvTranspose2d(2, 2, kernel_size=4, stride=2, padding=1, bias=False, groups=2)
             self.upsample_occ = nn.ConvTranspose2d(1, 1, kernel_size=4, stride=2, padding=1, bias=False, groups=1)
-        self.upsample_corr = None if corr_stride == 1 else nn.ConvTranspose2d(49, 49, kernel_size=4, stride=2, padding=1,
-                                                                                 bias=False, groups=49)
-        self.convs = nn.Sequential(ConvLayer(49, 128, 3), ConvLayer(128, 64, 3), ConvLayer(64, 32, 3))
+            if use_tradeoff:
+                self.upsample_toff = nn.ConvTranspose2d(32, feat_size, kernel_size=4, stride=2, padding=1, bias=False, groups=32)
+        self.deform = DeformConv2d(feat_size, feat_size, 3, stride=1, padding=1) if use_deformed_conv else None
+        self.upsample_corr = None
+        if use_corr:
+            if corr_stride != 1:
+                self.upsample_corr = nn.ConvTranspose2d(49, 49, kernel_size=4, stride=2, padding=1, bias=False, groups=49)
+            convs = [ConvLayer(49, 128, 3)]
+        else:
+            convs = [ConvLayer(2 * feat_size, 128, 3)]
+        self.convs = nn.Sequential(*convs, ConvLayer(128, 64, 3), ConvLayer(64, 32, 3))
         self.flow_head = ConvLayer(32, 2, kernel, activate=False)
         self.occ_head = ConvLayer(32, 1, kernel, activate=False)
 
@@ -201,9 +232,7 @@ class Subpixel(nn.Module):
 
     def __init__(self, flow_mult, kernel, feat_size, use_tradeoff):
         super().__init__()
-        if use_tradeoff:
-            raise NotImplementedError
-        self.flow_mult = flow_mult
+        self.flow_mult, self.use_tradeoff = flow_mult, use_tradeoff
         self.convs = nn.Sequential(ConvLayer(2 * feat_size + 2 + 1, 128, 3), ConvLayer(128, 64, 3), ConvLayer(64, 32, 3))
         self.flow_head = ConvLayer(32, 2, kernel, activate=False)
         self.occ_head = ConvLayer(32, 1, kernel, activate=False)
@@ -236,12 +265,13 @@ class InterBlock(nn.Module):
 
     def __init__(self, opt, height, width, flow_mult, kernel, feat_size, corr_stride, first=False):
         super().__init__()
-        _check_variants(opt)
         self.flow_mult, self.feat_size, self.corr_stride = flow_mult, feat_size, corr_stride
         self.height, self.width = int(height), int(width)
-        self.matching = Matching(flow_mult, kernel, feat_size, True, corr_stride, False, False, False,
-                                 getattr(opt, "no_proj", False), first=first)
-        self.subpixel = Subpixel(flow_mult, kernel, feat_size, False)
+        use_tradeoff = bool(getattr(opt, "use_tradeoff", False))
+        self.matching = Matching(flow_mult, kernel, feat_size, not getattr(opt, "no_corr", False), corr_stride,
+                                 bool(getattr(opt, "use_masked_flow", False)), bool(getattr(opt, "use_deformed_conv", False)),
+                                 use_tradeoff, getattr(opt, "no_proj", False), first=first)
+        self.subpixel = Subpixel(flow_mult, kernel, feat_size, use_tradeoff)
         self._m_heads = _FusedHeads(self.matching.flow_head, self.matching.occ_head)
         self._s_heads = _FusedHeads(self.subpixel.flow_head, self.subpixel.occ_head)
         self._up_w = None
@@ -255,6 +285,8 @@ class InterBlock(nn.Module):
             self._proj_weight()
         if self.matching.upsample_flow is not None:
             self._upsample_fo_weight()
+        if not self.matching.use_corr:
+            self._m0_split()
         self._sub0_split()
 
     def _upsample_fo_weight(self):
@@ -266,10 +298,11 @@ class InterBlock(nn.Module):
         return self._up_w[1]
 
     @torch.no_grad()
-    def forward_fused(self, dec, inters, fo_prev=None):
+    def forward_fused(self, dec, inters, fo_prev=None, toff_prev=None):
         """dec: [N,s,H,W] channel-slice VIEW of the decoder feature, updated in place.
         inters: k context features [N,s,H,W].  fo_prev: [N*k,3,h,w] (flow | occ) of the coarser
-        level or None.  Returns this level's [N*k,3,H,W] (flow | occ) view."""
+        level or None; toff_prev: its Subpixel feature [N*k,32,h,w] (--q_use_tradeoff) or None.
+        Returns (this level's [N*k,3,H,W] (flow | occ) view, its Subpixel feature or None)."""
         n, s, h, w = dec.shape
         k = len(inters)
         m = self.matching
@@ -288,14 +321,37 @@ class InterBlock(nn.Module):
             sp_in = torch.empty(n * k, s + 3, h, w, dtype=torch.float32, device=dec.device)
             fo = sp_in[:, s:]
         inter_w = None
+        variant = m.use_masked_flow or m.use_deformed_conv or m.use_tradeoff or not m.use_corr
         if fo_prev is not None:
             ops.dwconvT4x4s2(fo_prev, self._upsample_fo_weight(), out=fo)       # learned x2 of flow and occ
-            proj_w = self._proj_weight() if (m.proj is not None and ops.FUSE_WARP_PROJ) else None
-            if proj_w is None:
+            proj_w = self._proj_weight() if (m.proj is not None and ops.FUSE_WARP_PROJ and not variant) else None
+            # Matching variants (skip_autoencoder.py:182-195): deformable conv instead of the back-warp, then * (1 - sigmoid(occ)),
+            # + the up-sampled trade-off feature, LeakyReLU -- fused into the deform kernel's epilogue or one pass behind the warp
+            occ_mask = fo[:, 2:3] if m.use_masked_flow else None
+            toff_up = ops.gconvT4x4s2(toff_prev, m.upsample_toff.weight) if m.use_tradeoff else None
+            act_v = m.use_deformed_conv or m.use_tradeoff
+            if m.use_deformed_conv:
+                inter_w = ops.deform_conv3x3(ctxs, fo[:, :2], self.flow_mult, m.deform.packed(), m.deform.bias, occ=occ_mask,
+                                             toff=toff_up, act=act_v)
+            elif proj_w is None:
                 inter_w = ops.backwarp(ctxs, fo[:, :2], self.flow_mult)
+                if occ_mask is not None or toff_up is not None:
+                    ops.flow_mask_toff_(inter_w, occ_mask, toff_up, act=act_v)
+            del toff_up
         else:  # coarsest level: the cost volume reads the contexts themselves
             proj_w = None
             inter_w = torch.stack(ctxs, dim=1).view(n * k, s, h, w)
+        if not m.use_corr:
+            # no_corr (skip_autoencoder.py:200-201): convs(cat([input, inter])); the input half of the first convolution is the
+            # same for the k contexts of a frame, computed once per frame and broadcast in the epilogue (as for Subpixel below)
+            w_in, w_inter = self._m0_split()
+            conv0 = m.convs[0].conv
+            pre = ops.conv2d(dec, w_in, None, conv0.out_channel, 3, pad=1)
+            feat = ops.conv2d(inter_w, w_inter, conv0.bias, conv0.out_channel, 3, pad=1, act=True, pre=pre, pre_div=k, out_p8=p8)
+            feat = m.convs[2](m.convs[1](feat, out_p8=p8), out_p8=p8)
+            self._m_heads(feat, fo, accumulate=fo_prev is not None)
+            del feat, pre, inter_w
+            return self._subpixel_and_blend(dec, ctxs, fo, sp_in, p8, p8_warp)
         if m.proj is not None:
             pa = m.proj(dec)                                                     # input projected once per n, not k times
             if inter_w is None:   # warp and projection in one pass: the warped s-channel tensor is never written
@@ -311,6 +367,11 @@ class InterBlock(nn.Module):
         feat = m.convs[2](m.convs[1](m.convs[0](corr, out_p8=p8), out_p8=p8), out_p8=p8)
         self._m_heads(feat, fo, accumulate=fo_prev is not None)
         del corr, feat, pa, pb, inter_w
+        return self._subpixel_and_blend(dec, ctxs, fo, sp_in, p8, p8_warp)
+
+    def _subpixel_and_blend(self, dec, ctxs, fo, sp_in, p8, p8_warp):
+        """Subpixel refinement into `fo`, then the warp / fusion / blend of the contexts into `dec`; returns (fo, toff)."""
+        s, k = dec.shape[1], len(ctxs)
         sp = self.subpixel
         w_dec, w_rest, w_rest8 = self._sub0_split()
         conv0 = sp.convs[0].conv
@@ -322,11 +383,24 @@ class InterBlock(nn.Module):
         else:
             ops.backwarp(ctxs, fo[:, :2], self.flow_mult, out=sp_in[:, :s])
             feat = ops.conv2d(sp_in, w_rest, conv0.bias, conv0.out_channel, 3, pad=1, act=True, pre=pre, pre_div=k, out_p8=p8)
-        feat = sp.convs[2](sp.convs[1](feat, out_p8=p8), out_p8=p8)
+        # with the trade-off variant the last feature is the next level's `toff` (skip_autoencoder.py:227): written as fp32
+        feat = sp.convs[2](sp.convs[1](feat, out_p8=p8), out_p8=p8 and not sp.use_tradeoff)
         self._s_heads(feat, fo, accumulate=True)
+        toff = feat if sp.use_tradeoff else None
         del feat, pre
         ops.warp_fuse_blend(dec, ctxs, fo[:, :2], fo[:, 2:3], self.flow_mult, k)
-        return fo
+        return fo, toff
+
+    def _m0_split(self):
+        """no_corr: the first Matching conv ConvLayer(2s, 128, 3) split along its input channels into the (input, inter) blocks,
+        both with the full fan-in scale 1/sqrt(2s*9)."""
+        conv = self.matching.convs[0].conv
+        w = conv.weight
+        key = (w.data_ptr(), w._version, w.device, ops.CONV_PRECISION)
+        if getattr(self, "_m0", None) is None or self._m0[0] != key:
+            s = self.feat_size
+            self._m0 = (key, ops.pack_conv_weight(w[:, :s], scale=conv.scale), ops.pack_conv_weight(w[:, s:], scale=conv.scale))
+        return self._m0[1], self._m0[2]
 
     def _proj_weight(self):
         """(w_t, CoutPad) of Matching.proj for `ops.backwarp_proj`, or None when the fused kernel has no instantiation."""
@@ -354,8 +428,8 @@ class InterBlock(nn.Module):
         """Reference signature (skip_autoencoder.py:246): returns (fused input, flows, occs, toffs)."""
         fo_prev = torch.cat([flows, occs], dim=1) if flows is not None else None
         out = input.contiguous().clone()
-        fo = self.forward_fused(out, inters, fo_prev)
-        return out, fo[:, :2], fo[:, 2:3], None
+        fo, toff = self.forward_fused(out, inters, fo_prev, toffs)
+        return out, fo[:, :2], fo[:, 2:3], toff
 
 
 class SkipGANEncoder(nn.Module):
@@ -447,7 +521,7 @@ class SkipGANDecoder(nn.Module):
             inter_tgts = [[flatten_vid(t)[0] for t in inter_tgt] for inter_tgt in inter_tgts]
         out = self.blocks[0](input)
         inter_flows, inter_occs, inter_dec = [], [], []
-        fo = None
+        fo = toff = None
         for i in range(self.num_resolutions):
             if i > 0:
                 out = self.blocks[i](out)
@@ -455,7 +529,7 @@ class SkipGANDecoder(nn.Module):
                 s = self.inter_sizes[i]
                 if inter_pre_warping and return_all:
                     inter_dec.append(out[:, :s].clone())
-                fo = self.inter_blocks[i].forward_fused(out[:, :s], [tgt[-1 - i] for tgt in inter_tgts], fo)
+                fo, toff = self.inter_blocks[i].forward_fused(out[:, :s], [tgt[-1 - i] for tgt in inter_tgts], fo, toff)
                 if return_all:
                     if not inter_pre_warping:
                         inter_dec.append(out[:, :s])

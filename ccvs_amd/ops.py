@@ -440,6 +440,83 @@ def warp_fuse_blend(dec, ctx, flows, occs, flow_mult, k):
     return dec
 
 
+# ------------------------------------------------------------------ Matching variants
+def pack_deform_weight(weight, precision=None):
+    """DeformConv2d weight [C,C,3,3] (plain, no EqualConv2d scale) -> PackedConv in the convolution's layout for `deform_conv3x3`."""
+    return pack_conv_weight(weight, precision, scale=1.0)
+
+
+def deform_conv3x3(ctxs, flow, flow_mult, w_packed, bias, occ=None, toff=None, act=False):
+    """torchvision.ops.DeformConv2d(C, C, 3, padding=1) of the list of k context tensors [N/k,C,H,W] (see `backwarp`) with one offset per
+    pixel, flow * flow_mult read as (row, column) offsets -- Matching's `deform(inter, offset)` (`ccvs_deform_conv3x3_ctx`), then
+    [* (1 - sigmoid(occ))] [+ toff] [LeakyReLU(0.1)] in its epilogue.  flow [N,2,H,W], occ [N,1,H,W], toff [N,C,H,W]: [N,C,H,W]."""
+    _need_gpu(flow, w_packed.data, bias, occ, toff)
+    if not _planes_dense(flow):
+        flow = flow.contiguous()
+    if occ is not None and not _planes_dense(occ):
+        occ = occ.contiguous()
+    if toff is not None:
+        toff = _as_rows_dense(toff)
+    cl, keep = _ctx_list(ctxs)
+    nf, c, h, w = keep[0].shape
+    n = nf * cl.k
+    assert flow.shape == (n, 2, h, w) and w_packed.k == 3 and w_packed.kw == 3 and w_packed.cin == c and w_packed.cout == c
+    assert occ is None or occ.shape == (n, 1, h, w)
+    assert toff is None or toff.shape == (n, c, h, w)
+    out = torch.empty(n, c, h, w, dtype=torch.float32, device=flow.device)
+    prec = {"f32": 0, "bf16x3": 1}[w_packed.kind]
+    prof = KERNEL_TIMER
+    if prof is not None:
+        prof.begin("deform_" + w_packed.kind, flops=2.0 * n * c * c * 9 * h * w, nbytes=4.0 * (2 * n * c * h * w + 2 * n * h * w),
+                   side=4.0 * 9 * c * c, tag=(n, c, h, w))
+    L = _lib.load()
+    _lib.check(L.ccvs_deform_conv3x3_ctx(C.byref(cl), h * w, _p(flow), flow.stride(0), float(flow_mult), _p(w_packed.data), w_packed.cout_pad,
+                                         prec, _p(bias), _p(occ), occ.stride(0) if occ is not None else 0, _p(toff),
+                                         toff.stride(0) if toff is not None else 0, toff.stride(1) if toff is not None else 0, _p(out),
+                                         out.stride(0), out.stride(1), n, c, h, w, ACT_LRELU if act else ACT_NONE, _stream()),
+               "ccvs_deform_conv3x3_ctx")
+    if prof is not None:
+        prof.end()
+    return out
+
+
+def gconvT4x4s2(x, w, out=None):
+    """nn.ConvTranspose2d(G, G * mult, 4, stride=2, padding=1, groups=G, bias=False) with weight w [G, mult, 4, 4] (Matching.upsample_toff):
+    x [N,G,H,W] -> [N,G*mult,2H,2W] (`ccvs_gconvT4x4s2`)."""
+    _need_gpu(x, w, out)
+    if not _planes_dense(x):
+        x = x.contiguous()
+    n, g, h, ww = x.shape
+    assert w.shape[0] == g and w.shape[2:] == (4, 4)
+    mult = w.shape[1]
+    if out is None:
+        out = torch.empty(n, g * mult, 2 * h, 2 * ww, dtype=torch.float32, device=x.device)
+    assert out.shape == (n, g * mult, 2 * h, 2 * ww) and _rows_dense(out)
+    L = _lib.load()
+    _lib.check(L.ccvs_gconvT4x4s2(_p(x), x.stride(0), _p(w.detach().contiguous()), _p(out), out.stride(0), out.stride(1), n, g, mult, h, ww,
+                                  _stream()), "ccvs_gconvT4x4s2")
+    return out
+
+
+def flow_mask_toff_(x, occ=None, toff=None, act=False):
+    """In place on x [N,C,H,W]: x = act(x [* (1 - sigmoid(occ))] [+ toff]) -- Matching's masked-flow / trade-off steps after the plain
+    back-warp (`ccvs_flow_mask_toff`)."""
+    _need_gpu(x, occ, toff)
+    assert _rows_dense(x)
+    n, c, h, w = x.shape
+    if occ is not None:
+        occ = occ if _planes_dense(occ) else occ.contiguous()
+        assert occ.shape == (n, 1, h, w)
+    if toff is not None:
+        toff = _as_rows_dense(toff)
+        assert toff.shape == (n, c, h, w)
+    L = _lib.load()
+    _lib.check(L.ccvs_flow_mask_toff(_p(x), x.stride(0), x.stride(1), _p(occ), occ.stride(0) if occ is not None else 0, _p(toff),
+                                     toff.stride(0) if toff is not None else 0, toff.stride(1) if toff is not None else 0, n, c, h, w,
+                                     ACT_LRELU if act else ACT_NONE, _stream()), "ccvs_flow_mask_toff")
+    return x
+
+
 # ------------------------------------------------------------------ vector quantiser
 def vq_argmin(z, codebook_t, e_sq):
     """z [N,C,H,W] -> int64 [N*H*W] (n,h,w raster order)."""

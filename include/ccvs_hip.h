@@ -371,6 +371,31 @@ int ccvs_gpt_decode_prepare(const ccvs_gpt_decode* d, void* stream);
  * 16 (stream, budget) pairs behind a mutex; a budget of 0 removes the stream's entry. */
 int ccvs_stream_cu_limit(void* stream, int32_t cu_limit);
 
+/* ---- Matching variants (--q_use_deformed_conv, --q_use_masked_flow, --q_use_tradeoff; skip_autoencoder.py:131-206) ---------
+ * ccvs_deform_conv3x3_ctx: torchvision.ops.DeformConv2d(C, C, 3, stride 1, padding 1) of the k contexts (ctx as in
+ * ccvs_backwarp_ctx, planes of x_sC = H*W) with ONE offset per pixel shared by the nine taps, as Matching builds it from the
+ * up-sampled flow: offset channel 2t = flow x * flow_mult is read as the ROW offset and 2t+1 = flow y * flow_mult as the
+ * COLUMN offset, so tap (i, j) of output (y, x) samples (y - 1 + i + fx * m, x - 1 + j + fy * m) bilinearly in pixel units,
+ * zero outside (torchvision's bilinear_interpolate).  flow [N,2,H,W] (batch stride flow_sN, planes dense).
+ * w: the [C,C,3,3] weight (no scale) packed like ccvs_conv2d_bf16x3's (precision 1 = split-bf16, [9][C/8][2][CoutPad][8] bf16) or
+ * ccvs_conv2d's (precision 0 = fp32, [9][C][CoutPad]).  Epilogue, in this order: + bias[co]; * (1 - sigmoid(occ)) when occ is not
+ * NULL (occ [N,1,H,W], batch stride occ_sN); + toff (when not NULL; [N,C,H,W], strides toff_sN / toff_sC); LeakyReLU(0.1) when
+ * act.  y [N,C,H,W] with strides y_sN / y_sC (planes dense).  C % 16 == 0. */
+int ccvs_deform_conv3x3_ctx(const ccvs_ctx_list* ctx, int64_t x_sC, const float* flow, int64_t flow_sN, float flow_mult,
+                            const void* w, int32_t CoutPad, int32_t precision, const float* bias, const float* occ, int64_t occ_sN,
+                            const float* toff, int64_t toff_sN, int64_t toff_sC, float* y, int64_t y_sN, int64_t y_sC, int32_t N,
+                            int32_t C, int32_t H, int32_t W, int32_t act, void* stream);
+/* Grouped ConvTranspose2d(G, G * mult, 4, stride 2, padding 1, groups=G, bias=False) (Matching.upsample_toff, G = 32):
+ * output channel o reads input channel o / mult.  w [G, mult, 4, 4]; x [N,G,H,W] (batch stride x_sN, planes dense) ->
+ * y [N,G*mult,2H,2W] (batch stride y_sN, channel stride y_sC, planes dense). */
+int ccvs_gconvT4x4s2(const float* x, int64_t x_sN, const float* w, float* y, int64_t y_sN, int64_t y_sC, int32_t N, int32_t G,
+                     int32_t mult, int32_t H, int32_t W, void* stream);
+/* In place on the warped context feature x [N,C,H,W] (strides x_sN / x_sC, planes dense): x = act(x * (1 - sigmoid(occ)) + toff)
+ * with the factor only when occ is not NULL ([N,1,H,W], batch stride occ_sN), the addend only when toff is not NULL (strides
+ * toff_sN / toff_sC) and LeakyReLU(0.1) when act: the masked-flow / trade-off steps of Matching after the plain back-warp. */
+int ccvs_flow_mask_toff(float* x, int64_t x_sN, int64_t x_sC, const float* occ, int64_t occ_sN, const float* toff, int64_t toff_sN,
+                        int64_t toff_sC, int32_t N, int32_t C, int32_t H, int32_t W, int32_t act, void* stream);
+
 /* ---- output stage ---------------------------------------------------------------------
  * save_video_batch's clamp / rescale / x255 / uint8 / channels-last pack
  * (helpers/generator.py:306-309).  vid [N,3,H,W] fp32 in [lo,hi] -> out [N,H,W,3] u8. */
