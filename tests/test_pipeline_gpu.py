@@ -231,14 +231,17 @@ def test_sequence_gemm_rows_do_not_depend_on_the_launch():
     """Whole-sequence calls (`CCVS_GEMM_SEQ`; the QKV form with Tq > 1) run ONE kernel form whatever the row count: the rows of
     a 256-row prefill (a batch alone) and the same rows inside a 272- / 768-row launch (the batch stacked into a token group)
     are the same bits -- the old pick by M put 256 rows on the weight-stream kernel and 257+ on the row-blocked one, whose K
-    partitions differ.  Logits-level check: plain, deep-K, LayerNorm-folded + GELU, and the QKV form with its cache scatter."""
+    partitions differ.  Logits-level check: plain, deep-K, LayerNorm-folded + GELU, and the QKV form with its cache scatter.
+    1024 / 2048 rows are 8 / 16 row tiles of gemm_seq_kernel, which take the XCD-swizzled workgroup order; the K = 1040 GEMM (a
+    strided x, 65 stages of 16) ends on the odd-stage exit of the two-stage loop."""
     from ccvs_amd import ops
     g = torch.Generator().manual_seed(9)
-    C, F, M = 256, 1024, 768
+    C, F, M = 256, 1024, 2048
     x = torch.randn(M, C, generator=g).cuda()
     h = torch.randn(M, 4096, generator=g).cuda()
     w_proj, b_proj = (torch.randn(C, C, generator=g) * 0.05).cuda(), torch.randn(C, generator=g).cuda()
     w_fc2, b_fc2 = (torch.randn(C, 4096, generator=g) * 0.02).cuda(), torch.randn(C, generator=g).cuda()
+    w_odd = (torch.randn(C, 1040, generator=g) * 0.03).cuda()
     w_fc, b_fc = (torch.randn(F, C, generator=g) * 0.05).cuda(), torch.randn(F, generator=g).cuda()
     gamma, beta = (1 + 0.1 * torch.randn(C, generator=g)).cuda(), (0.1 * torch.randn(C, generator=g)).cuda()
     fc_packed = ops.pack_ln_linear(w_fc, b_fc, gamma, beta)
@@ -254,16 +257,23 @@ def test_sequence_gemm_rows_do_not_depend_on_the_launch():
                ops.gemm_ln(xs, *fc_packed, epilogue=ops.EPI_GELU | SEQ)]
         kc, vc = torch.zeros(m // Tq, H, Tq, C // H, device="cuda"), torch.zeros(m // Tq, H, Tq, C // H, device="cuda")
         out.append(ops.gemm_ln_qkv(xs, *qkv_packed, kc, vc, m // Tq, Tq, 0))
+        out.append(ops.gemm_nt(hs[:, :1040], w_odd, b_proj, ops.EPI_GELU | SEQ))
         return out + [kc, vc]
 
     ref = run(256)
-    for m in (64, 272, 768):
+    for m in (64, 272, 768, 1024, 2048):
         got = run(m)
         n = min(m, 256)
-        for a, b in zip(ref[:4], got[:4]):
+        for a, b in zip(ref[:5], got[:5]):
             assert torch.equal(a[:n], b[:n]), m
-        for a, b in zip(ref[4:], got[4:]):
+        for a, b in zip(ref[5:], got[5:]):
             assert torch.equal(a[:n // Tq], b[:n // Tq]), m
+        if m == 1024:
+            ref1k = got
+    for a, b in zip(ref1k[:5], got[:5]):   # every row tile of the 8-tile launch inside the 16-tile one
+        assert torch.equal(a, b[:1024])
+    for a, b in zip(ref1k[5:], got[5:]):
+        assert torch.equal(a, b[:1024 // Tq])
     want = torch.nn.functional.gelu(torch.nn.functional.layer_norm(x[:256], (C,), gamma, beta) @ w_fc.t() + b_fc)
     assert (ref[2] - want).abs().max().item() < 2e-4
 
