@@ -11,7 +11,8 @@ Differences by design:
     decoded clips of all ranks are all-gathered once at the end (`Engine.all_gather_clips`);
   * with no dataset on disk the input is the seeded synthetic tensor BASELINE.md specifies
     (`vid = rand(B,T,3,H,W)*2-1`).
-State / STFT / layout / deblurring conditioning are "next" rows and raise.
+Deblurring (`--x_deblurring`): the blurred clip's codes are the transformer's ancillary stream and its skip features the decoder's
+(`condition`, `blur`).  Layout conditioning is a "next" row and raises.
 """
 import os
 import sys
@@ -44,9 +45,10 @@ class Generator:
         self.state_model = None
         self._dec_stream, self._chains, self._warm_keys = None, [], set()
         self.last_cu_limit, self.last_lanes, self.last_chains = 0, 0, 0
-        for flag in ("layout", "deblurring"):
-            if getattr(self.opt, flag, False):
-                raise NotImplementedError(f"--{flag} is not on the MI355X path (SURVEY 8f); --x_state / --x_stft [--keep_state] / --x_cat are")
+        if getattr(self.opt, "layout", False):
+            raise NotImplementedError("--layout is not on the MI355X path (SURVEY 8f); --x_state / --x_stft [--keep_state] / --x_cat / --x_deblurring are")
+        if getattr(self.opt, "deblurring", False) and self.opt.step_by_step:
+            raise NotImplementedError("--step_by_step with --deblurring is not on the MI355X path (the plain synthesis schedule runs the mode)")
 
     # ------------------------------------------------------------------ models / data
     def build_models(self, is_main=True):
@@ -118,10 +120,12 @@ class Generator:
         """First half of generate_vid (generator.py:57-130): encode every frame, tokenise the ancillary streams, crop to the
         conditioning window.  Returns the working set of one batch as a dict: `encoded`, `cropped`, `total_len`,
         `cond_len`, `crop_prop`.  `draw=False` (a warm-up pass whose results are discarded): nothing is drawn from the process
-        generator -- missing class labels are zeros instead of the reference's randint (generator.py:124)."""
+        generator -- missing class labels are zeros instead of the reference's randint (generator.py:124), and the blur's sigma is not
+        drawn.  With `deblurring` the working set also holds the blurred clip (`blur`: {"vid"})."""
         opt, qopt = self.opt, self.qvid_opt
-        if getattr(opt, "layout", False) or getattr(opt, "deblurring", False):
-            raise NotImplementedError("layout / deblurring conditioning is not on the MI355X path (SURVEY 8f)")
+        if getattr(opt, "layout", False):
+            raise NotImplementedError("layout conditioning is not on the MI355X path (SURVEY 8f)")
+        deblurring = bool(getattr(opt, "deblurring", False))
         if opt.down_size is not None:  # generator.py:60-66
             vid = data["vid"].cuda()
             bs, t = vid.shape[:2]
@@ -149,7 +153,7 @@ class Generator:
         cond_step, t_step = (1, opt.vid_len - 1) if opt.p2p else (0, opt.vid_len)
         total_len = (cond_step + t_step) * size
         cond_len = cond_step * size
-        if opt.state or opt.stft:                                           # generator.py:91-92
+        if opt.state or opt.stft or deblurring:                             # generator.py:91-92
             total_len += t_step * opt.state_size
         if opt.gen_from_img:
             crop_prop = opt.cond_len / size
@@ -180,8 +184,14 @@ class Generator:
                 n_lbl = encoded_data["code"].size(0)
                 data["vid_lbl"] = torch.randint(low=0, high=len(opt.categories), size=[n_lbl]) if draw else torch.zeros(n_lbl, dtype=torch.int64)
             cropped["vid_lbl"] = data["vid_lbl"]
+        blurred = None
+        if deblurring:                                                      # generator.py:125-128: the blurred clip, ALL frames, is
+            blurred = blur(data, blur_sigma=opt.blur_sigma, draw=draw)      # the ancillary stream and the decoder's skip features
+            blurred_encoded = self.vid_model(blurred, mode='vid_encoder')
+            cropped["state_code"] = blurred_encoded["code"]
+            cropped["inter"] = blurred_encoded["inter"]
         return {"data": data, "encoded": encoded_data, "cropped": cropped, "total_len": total_len, "cond_len": cond_len,
-                "crop_prop": crop_prop}
+                "crop_prop": crop_prop, "blur": blurred}
 
     def _frames_to_encode(self, n_frames, size):
         """Frames of the input clip the encoder has to see.  The reference encodes all of them (generator.py:69); with
@@ -276,7 +286,8 @@ class Generator:
                     if v is not None:
                         setattr(self, k, v)
             self._events_stream = ev
-            out = {"real": out["real"], "fake": out["fake"], "rec": out["rec"], "enc_code": out["enc_code"], "real_state": out["real_state"]}
+            out = {"real": out["real"], "fake": out["fake"], "rec": out["rec"], "enc_code": out["enc_code"], "real_state": out["real_state"],
+                   "blur": out.get("blur")}
             if save:
                 self.save_results(out, global_iter)
             return out
@@ -311,7 +322,7 @@ class Generator:
 
         self._events = ev
         out = {"real": data["vid"], "fake": fake_data, "rec": rec_data, "enc_code": encoded_data["code"],
-               "real_state": data.get("state") if opt.state else None}
+               "real_state": data.get("state") if opt.state else None, "blur": ws["blur"]["vid"] if ws["blur"] is not None else None}
         if save:
             self.save_results(out, global_iter)
         return out
@@ -332,7 +343,7 @@ class Generator:
         reading its own stream (`ccvs_gpt_decode.noise_stream`), and several loops run beside each other."""
         opt = self.opt
         size = int(self.qvid_opt.z_shape[0]) * int(self.qvid_opt.z_shape[1])
-        if not (not (opt.state or opt.stft) and getattr(opt, "beam_size", None) is None and getattr(opt, "use_graph", True)
+        if not (not (opt.state or opt.stft or getattr(opt, "deblurring", False)) and getattr(opt, "beam_size", None) is None and getattr(opt, "use_graph", True)
                 and opt.vid_len * size <= opt.z_len):
             return False
         if batch is not None:
@@ -489,8 +500,8 @@ class Generator:
     # ------------------------------------------------------------------ output stage
     def save_results(self, out, global_iter):
         bs = out["real"].shape[0]
-        for name in ("real", "fake", "rec"):
-            item = out[name]
+        for name in ("real", "fake", "rec", "blur"):                       # generator.py:191-212
+            item = out.get(name)
             if item is None:
                 continue
             vid = item["vid"] if isinstance(item, dict) else item
@@ -658,9 +669,22 @@ def square_trajectory(init_state, vid_len):
     return {"state": state}
 
 
-def blur(data, blur_sigma=10):
-    """helpers/generator.py:381-390 (deblurring mode input)."""
-    raise NotImplementedError("deblurring mode is not on the MI355X path yet (SURVEY 8f)")
+def blur_kernel_size(blur_sigma):
+    """helpers/generator.py:386-387: the odd size int(3 s) (+ 1 when even), clamped to 3 .. 13 (s = 1, 2, 3, >= 4: 3, 7, 9, 13)."""
+    k = int(3 * blur_sigma) + 1 if int(3 * blur_sigma) % 2 == 0 else int(3 * blur_sigma)
+    return max(3, min(k, 13))
+
+
+def blur(data, blur_sigma=10, draw=True):
+    """helpers/generator.py:381-390: transforms.GaussianBlur(kernel_size, sigma=blur_sigma) over the [B*T, C, H, W] frames of
+    data["vid"], on the GPU (`ops.gaussian_blur`).  torchvision's forward draws its sigma with `torch.empty(1).uniform_(s, s)`: one
+    draw from the CPU default generator whose value is s.  `draw=True` makes that draw, so that the process generator stands where
+    the reference's does; `draw=False` (a warm-up pass) leaves it alone.  Returns {"vid": [B, T, C, H, W]} on the device."""
+    vid = data["vid"].cuda()
+    bs, t = vid.shape[:2]
+    sigma = torch.empty(1).uniform_(blur_sigma, blur_sigma).item() if draw else float(blur_sigma)
+    out = ops.gaussian_blur(vid.reshape(bs * t, *vid.shape[2:]), blur_kernel_size(blur_sigma), sigma)
+    return {"vid": out.view(bs, t, *vid.shape[2:])}
 
 
 if __name__ == "__main__":

@@ -505,6 +505,10 @@ class PipelinedRun:
                 self.held.append(data)         # a ragged batch starts the next group
                 break
             other_draw = self.noise_feed is not None and opt.cat and "vid_lbl" not in data
+            if self.host_noise and self.noise_feed is None and getattr(opt, "deblurring", False):
+                # the blur's sigma draw (`condition`) comes behind the previous batches' noise, drawn inline by their token stages
+                for j in self.jobs:
+                    self._wait_job(j, "the token stage")
             if other_draw:
                 self.noise_feed.drain()        # `condition` draws the labels from the same generator: behind the previous batch's noise
             ev = {k: torch.cuda.Event(enable_timing=True) for k in ("e0", "e1", "d0", "d1")}
@@ -593,7 +597,8 @@ class PipelinedRun:
                             m["noise"] = None
                         tr.net_t.noise_streams = streams
                     # one window of tokens, frame tokens only: the loop reports every finished frame (mingpt `progress`)
-                    by_frame = self.stream_frames and int(job["total_len"]) <= opt.z_len and not (opt.state or opt.stft)
+                    by_frame = (self.stream_frames and int(job["total_len"]) <= opt.z_len
+                                and not (opt.state or opt.stft or getattr(opt, "deblurring", False)))
                     tr.net_t.progress = feed.on_tokens if by_frame else None
                     job["t0"].record()
                     out = tr(tok_in, mode='inference', total_len=job["total_len"])
@@ -740,12 +745,14 @@ class PipelinedRun:
             job, m = task["job"], task["m"]
             ws = m["ws"]
             out = {"real": ws["data"]["vid"], "fake": fake, "rec": None, "enc_code": ws["encoded"]["code"],
-                   "real_state": ws["data"].get("state") if self.opt.state else None, "index": m["i"]}
+                   "real_state": ws["data"].get("state") if self.opt.state else None, "index": m["i"],
+                   "blur": ws["blur"]["vid"] if ws.get("blur") is not None else None}
             with torch.cuda.stream(self.dec_streams[task["sid"]]):
                 if self.rec_pass:
                     out["rec"] = self.gen.reconstruct(ws)
                 out["finished"] = self.finish(m["i"], fake) if self.finish is not None else None
-                for t in (fake["vid"], fake["code"]) + ((out["rec"]["vid"],) if out["rec"] is not None else ()):   # handed to the caller's stream
+                for t in ((fake["vid"], fake["code"]) + ((out["rec"]["vid"],) if out["rec"] is not None else ())
+                          + ((out["blur"],) if out["blur"] is not None else ())):   # handed to the caller's stream
                     t.record_stream(self.entry)
                 if self.consume is not None:   # a long run: the caller takes every batch as it comes, nothing is kept here
                     self.consume(out)

@@ -664,6 +664,13 @@ class GPT(nn.Module):
         n_code, n_state = t0, ns0
         device_noise = sampler["sample"] and sampler["noise"] == "device"
         eager = trace is not None or (sampler["sample"] and not device_noise) or not use_graph
+        if self.warm_only and eager:
+            # an eager loop captures nothing (the KV cache is allocated above); running it would draw host noise from the process
+            # generator ahead of the real call.  The result has the call's lengths (a sliding window's warm-up goes on from it), the
+            # picks left at token 0
+            out = torch.zeros(b, nc, dtype=torch.int64, device=dev)
+            out[:, :t0] = code
+            return out, state_buf[:, :nst].clone()
         words = self._philox_words() if device_noise else None
         self._set_decode_state(words)
 

@@ -308,6 +308,30 @@ def dwconvT4x4s2(x, w, out=None):
     return out
 
 
+def gaussian_kernel1d(k, sigma):
+    """torchvision's `_get_gaussian_kernel1d` (0.8.1): float32 linspace / exp / sum, normalised."""
+    half = (k - 1) * 0.5
+    x = torch.linspace(-half, half, steps=k)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    return pdf / pdf.sum()
+
+
+def gaussian_blur(x, k, sigma):
+    """transforms.GaussianBlur(kernel_size=k, sigma=sigma)(x) of [N,C,H,W] fp32 (helpers/generator.py:381-390 `blur`): reflect
+    padding, the separable k x k Gaussian (`ccvs_gaussian_blur`).  x may have any batch / channel strides; the result is contiguous."""
+    _need_gpu(x)
+    assert x.dtype == torch.float32 and x.dim() == 4
+    if not _rows_dense(x):
+        x = x.contiguous()
+    n, c, h, w = x.shape
+    wt = gaussian_kernel1d(int(k), float(sigma))
+    wbuf = (C.c_float * int(k))(*wt.tolist())
+    out = torch.empty(n, c, h, w, dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().ccvs_gaussian_blur(_p(x), x.stride(0), x.stride(1), _p(out), n, c, h, w, int(k), wbuf, _stream()),
+               "ccvs_gaussian_blur")
+    return out
+
+
 # ------------------------------------------------------------------ cost volume / warp
 def correlation7x7(first, second, stride, first_div=1, lrelu=False):
     _need_gpu(first, second)

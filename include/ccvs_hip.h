@@ -131,6 +131,13 @@ int ccvs_upfirdn2d(const float* x, float* y, const float* residual, int64_t NC, 
 int ccvs_dwconvT4x4s2(const float* x, int64_t x_sN, const float* w, float* y, int64_t y_sN, int32_t N, int32_t C, int32_t H,
                       int32_t W, void* stream);
 
+/* torchvision GaussianBlur(kernel_size=k, sigma) of the deblurring mode (helpers/generator.py:381-390): reflect padding of k / 2,
+ * then the separable k x k filter outer(w, w).  x [N,C,H,W] fp32 (batch / channel strides x_sN / x_sC, planes dense) -> y
+ * [N,C,H,W] contiguous.  k odd in 3 .. 13, k / 2 < H and < W (as F.pad(mode="reflect") requires); `weights`: the k float32 1-D
+ * weights, a HOST pointer (copied into the launch). */
+int ccvs_gaussian_blur(const float* x, int64_t x_sN, int64_t x_sC, float* y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t k,
+                       const float* weights, void* stream);
+
 /* ---- cost volume / warping -----------------------------------------------------------
  * ccvs_correlation7x7 replaces FunctionCorrelation(first, second, stride)
  * (modules/correlation.py:279-338,405-406; kernels :11-100) fused with the
