@@ -7,9 +7,11 @@
 // 7x7 displacement correlation (modules/correlation.py:11-100):
 //   out[n][7*(dy+3)+(dx+3)][y][x] = (1/C) sum_c A[n/div][c][y*s][x*s] * B[n][c][(y+dy)*s][(x+dx)*s]
 // One workgroup = 8x32 output pixels, one lane per pixel with 49 running sums in
-// registers; per chunk of CORR_CC channels the B halo tile is staged in LDS (zero outside the
-// image: the reference's padded `rearrange` copy is never materialised).  Only the samples
-// B[(y+dy)*s][(x+dx)*s] are ever read, so the tile holds the stride-s SUBSAMPLED halo,
+// registers, each channel added with an explicit fmaf (with `+=` the compiler paired two
+// channels' products of one sum into a v_pk_mul_f32 and two unfused adds: that sum was
+// rounded unlike the other 48 and unlike the two-pixel form below).  Per chunk of CORR_CC
+// channels the B halo tile is staged in LDS (zero outside the image: the reference's padded
+// `rearrange` copy is never materialised).  Only the samples B[(y+dy)*s][(x+dx)*s] are ever read, so the tile holds the stride-s SUBSAMPLED halo,
 // (8+6) x (32+6) values per channel whatever s: a quarter of the staging at s = 2, and the
 // lanes of a wave read consecutive LDS words (with the full-resolution tile they were 2 words
 // apart: every read a two-way bank conflict).
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(256) void correlation7x7_kernel(const float* __rest
 #pragma unroll
             for (int dy = 0; dy < 7; ++dy)
 #pragma unroll
-                for (int dx = 0; dx < 7; ++dx) acc[dy * 7 + dx] += a * bp[dy * IW + dx];
+                for (int dx = 0; dx < 7; ++dx) acc[dy * 7 + dx] = fmaf(a, bp[dy * IW + dx], acc[dy * 7 + dx]);
         }
     }
     if (live) {
@@ -104,7 +106,7 @@ __global__ __launch_bounds__(256) void correlation7x7_kernel(const float* __rest
 // pixel and channel; SQ_LDS_IDX_ACTIVE / SQ_BUSY_CYCLES = 1.05, no conflicts).  A lane that owns the pixel pair (x, x + 1) needs the
 // 8 consecutive values B[y + dy][x .. x + 7] per row and channel: four 8-byte LDS reads (256 B/clk) serve 14 products instead of
 // fourteen 4-byte reads (128 B/clk), and the 49 results per pixel leave as 8-byte stores.  Workgroup = 8 x 64 output pixels;
-// per (pixel, displacement) the channels are added in the same order as above: the same bits.
+// per (pixel, displacement) the channels are added in the same order as above, each with one fmaf: the same bits.
 template <int S>
 __global__ __launch_bounds__(256) void correlation7x7x2_kernel(const float* __restrict__ first, const float* __restrict__ second,
                                                                float* __restrict__ out, int C, int H, int W, int Ho, int Wo,
@@ -186,8 +188,8 @@ __global__ __launch_bounds__(256) void correlation7x7x2_kernel(const float* __re
                 }
 #pragma unroll
                 for (int dx = 0; dx < 7; ++dx) {
-                    acc0[dy * 7 + dx] += a0 * r[dx];
-                    acc1[dy * 7 + dx] += a1 * r[dx + 1];
+                    acc0[dy * 7 + dx] = fmaf(a0, r[dx], acc0[dy * 7 + dx]);
+                    acc1[dy * 7 + dx] = fmaf(a1, r[dx + 1], acc1[dy * 7 + dx]);
                 }
             }
         }

@@ -14,7 +14,10 @@ uses a cupy kernel for the cost volume.  The recipe here:
 * `Tensor.cuda` / `Module.cuda` -> identity,
 * `skip_autoencoder.FunctionCorrelation` -> a brute-force CPU loop restatement of
   the CUDA index math (`modules/correlation.py:44-96`); the reference has no CPU
-  implementation (`correlation.py:333-334`), so this op is "parity unpinned",
+  implementation (`correlation.py:333-334`).  The stand-in is pinned to the
+  reference's own kernel, compiled from its text by `oracle/build_ref_correlation.py`
+  into `oracle/_ref/` (rebuild: `python oracle/build_ref_correlation.py`), in
+  `tests/test_correlation_ref_gpu.py`,
 * the overlapping in-place shift of `quantized_video_model.py:898,900,946`
   (rejected by torch >= 1.8) is patched at run time by wrapping
   `Tensor.__setitem__` so that an overlapping RHS view is cloned first.
@@ -26,7 +29,7 @@ import contextlib
 
 import torch
 
-REF_ROOT = os.environ.get("CCVS_REFERENCE_ROOT", "")
+REF_ROOT = os.environ.get("CCVS_REFERENCE_ROOT") or "/root/reference"   # the same default as oracle/build_ref_correlation.py
 
 
 def reference_available():
