@@ -71,8 +71,7 @@ extern "C" int ccvs_conv2d_bf16x3(const float* x, const void* w_split, const flo
     static const int pt_env = getenv("CCVS_CONV_PT") ? atoi(getenv("CCVS_CONV_PT")) : -1;
     k.pt = pt_env >= 0 ? pt_env : __atomic_load_n(&g_conv_pt_mode, __ATOMIC_RELAXED);
     k.ktail = 0; k.nwork = 0; k.gx = k.gy = 1; k.work0 = 0; k.xcd_chunk = 0; k.cu_limit = d->cu_limit > 0 ? d->cu_limit : ccvs_cu_limit_of(stream);
-    static const int pre_order = getenv("CCVS_CONV_PRE_ORDER") ? atoi(getenv("CCVS_CONV_PRE_ORDER")) : 1;   // 0: image-major tiles for every launch
-    k.zi = (pre_order && d->pre && k.pre_div > 1 && !d->transposed && d->N % k.pre_div == 0) ? k.pre_div : 0;
+    k.zi = (d->pre && k.pre_div > 1 && !d->transposed && d->N % k.pre_div == 0) ? k.pre_div : 0;
     if (k.in_p8) CCVS_REQUIRE(!d->transposed && d->stride == 1 && d->Cin % 8 == 0, "ccvs_conv2d_bf16x3: packed input needs stride 1, Cin %% 8 == 0");
     if (k.out_p8) CCVS_REQUIRE(!d->transposed && d->Cout % 8 == 0 && !d->accumulate && !residual, "ccvs_conv2d_bf16x3: packed output needs Cout %% 8 == 0, no residual / accumulate");
     const int CinG = 2 * ((d->Cin + 15) / 16);  // 8-channel groups, Cin padded to 16
@@ -94,21 +93,17 @@ extern "C" int ccvs_conv2d_bf16x3(const float* x, const void* w_split, const flo
     // Small launches (the 8 x 8 ... 32 x 32 levels of the encoder / decoder at 16 images: one or four pixel tiles per image):
     // with 128 output channels per workgroup they are 16-64 workgroups walking the whole K depth alone on a quarter of the
     // chip.  Narrower channel blocks give the same tiles to 2-4 x as many workgroups (same arithmetic per output, bit-identical).
-    static const int small_split = getenv("CCVS_CONV_SMALL_SPLIT") ? atoi(getenv("CCVS_CONV_SMALL_SPLIT")) : 256;   // workgroups aimed at; 0: off
+    constexpr long small_split = 256;   // workgroups aimed at
     while (mb > 1 && (long)k.tiles_x * k.tiles_y * gz * (d->CoutPad / (32 * mb)) < small_split) mb >>= 1;
     // Few input channels per output byte (the 49- and 99-channel layers in front of 128 outputs): 64 output channels per
     // workgroup and two workgroups per CU, so that one tile's prologue / epilogue runs beside the other's K loop
-    // (conv2d_bf16_kernels.h, WPC).  CCVS_CONV_WPC2 = largest Cin that takes this form (0: off).
-    static const int wpc2_cin = getenv("CCVS_CONV_WPC2") ? atoi(getenv("CCVS_CONV_WPC2")) : 64;   // 49->128: +6...7 %; 99->128: none (tools/conv_one.py)
+    // (conv2d_bf16_kernels.h, WPC).  wpc2_cin = largest Cin that takes this form.
+    constexpr int wpc2_cin = 64;   // 49->128: +6...7 %; 99->128: none (tools/conv_one.py)
     int wpc2 = 0;
-    static const int wpc2_p8out = getenv("CCVS_CONV_WPC2_P8OUT") ? atoi(getenv("CCVS_CONV_WPC2_P8OUT")) : 0;   // experiment: ... also when the layer writes packed output
-    if (wpc2_cin > 0 && mb >= 2 && TW == 32 && d->Cin <= wpc2_cin && d->kh == 3 && d->kw == 3 && d->stride == 1 && !d->transposed && !d->in_p8 && (!d->out_p8 || wpc2_p8out)) {
+    if (mb >= 2 && TW == 32 && d->Cin <= wpc2_cin && d->kh == 3 && d->kw == 3 && d->stride == 1 && !d->transposed && !d->in_p8 && !d->out_p8) {
         mb = 2;
         wpc2 = 1;
     }
-    // experiment (CCVS_CONV_P8_WPC2): packed-input 3 x 3 layers as 64-channel workgroups, two per CU (see launch_conv_bf16)
-    static const int p8_wpc2 = getenv("CCVS_CONV_P8_WPC2") ? atoi(getenv("CCVS_CONV_P8_WPC2")) : 0;
-    if (p8_wpc2 && mb == 4 && TW == 32 && d->in_p8 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->pad == 1 && k.cu_limit <= 0) mb = 2;
 #define CB_DISPATCH(TWv)                                                                                        \
     if (mb == 4) return ccvs_conv_bf16_launch_##TWv##_4(k, w_split, d->w_ktail, CinG, halo_h, halo_w, ntx_max, gz, st, wpc2);           \
     if (mb == 2) return ccvs_conv_bf16_launch_##TWv##_2(k, w_split, d->w_ktail, CinG, halo_h, halo_w, ntx_max, gz, st, wpc2);           \

@@ -21,16 +21,8 @@
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// The 16-byte stores of the epilogues.  -DCB_STORE_WT (an experiment, tools/r05/store_wt_ab.sh): write-through (`sc1`) -- the output
-// tile leaves no dirty lines in the XCD's L2, so the write-back at the END of every other kernel on the chip (the release at a
-// kernel boundary: 123 per token step beside these convolutions) finds nothing of ours to flush.
-#ifdef CB_STORE_WT
-__device__ __forceinline__ void cb_store16(void* dst, f32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
-}
-#else
+// the 16-byte stores of the epilogues
 __device__ __forceinline__ void cb_store16(void* dst, f32x4 v) { *reinterpret_cast<f32x4*>(dst) = v; }
-#endif
 __device__ __forceinline__ void cb_store16(void* dst, uint4 v) { cb_store16(dst, f32x4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)}); }
 
 #define CB_CC 16      // input channels per chunk = one MFMA K step
@@ -149,8 +141,9 @@ __device__ __forceinline__ int conv_add_kind(const ConvK& p) {
     return n_add == 0 ? 0 : (n_add > 1 ? 4 : (p.pre ? 1 : (p.res ? 2 : 3)));
 }
 
-// NW waves (4 or 8): with 8, every wave owns ONE 32-pixel block (half the accumulators) and twice as many threads stage the
-// halo tile -- the workgroup is alone on its CU (LDS), so the extra waves are what overlaps its loads (env CCVS_CONV_SYNC_WAVES).
+// NW waves, launched with 8 (NW = 4 was measured slower): every wave owns ONE 32-pixel block (half the accumulators of
+// 4 waves) and twice as many threads stage the halo tile -- the workgroup is alone on its CU (LDS), so the extra waves are what
+// overlaps its loads.
 template <int TW, int MB, int NW>
 __global__ __launch_bounds__(64 * NW) void conv2d_bf16x3_kernel(ConvK p, const uint4* __restrict__ wsplit, int CinG) {
     constexpr int TH = 256 / TW;
@@ -303,8 +296,8 @@ __global__ __launch_bounds__(64 * NW) void conv2d_bf16x3_kernel(ConvK p, const u
 //   NTY = 0      scalar staging, any tap count (k x 1 heads with odd padding, unaligned views): 16 dword loads per
 //        staging thread and step, software-pipelined one step deep in registers together with the weights
 //        (convert + store what was loaded during step s-1, then request the bundle of step s+2).
-//   NTY = -2     the same with two pixel passes per thread and step (transposed layers: larger halo tiles).
-// Stride-2 layers and halo tiles that do not fit the double buffer use the synchronous kernel above.
+//   NTY = -2     the same with two pixel passes per thread and step (larger halo tiles).
+// Stride-2 and transposed layers and halo tiles that do not fit the double buffer use the synchronous kernel above.
 // ---------------------------------------------------------------------------------------
 // (MB = 2 compiled for 4 waves per SIMD -- two workgroups per CU, 17 VGPRs spilled -- measured 236 vs 246 TFLOP/s on 128->64 3x3 at 256^2: not kept)
 // PP = pixel blocks (of 32) per MFMA wave: 2 = the 256-pixel tile; 4 = a 512-pixel tile (TW x 512/TW), for layers with <= 64
@@ -317,12 +310,12 @@ __global__ __launch_bounds__(64 * NW) void conv2d_bf16x3_kernel(ConvK p, const u
 // WPC = 2 (64 output channels per workgroup, dense 3 x 3 only): compiled for TWO workgroups per CU (<= 128 VGPRs, ~77 KB of
 // LDS each, one register set in the staging waves).  A tile's prologue (workgroup launch, first chunk: ~5 us) and epilogue
 // (131 KB of output per 128-channel tile: ~10 us at the rate the chip writes) are not overlapped with anything while a CU holds
-// ONE workgroup -- CCVS_CONV_ABLATE runs: 14.5 us of the 36 us a 49->128 tile takes, 40 % -- so layers with few input channels
+// ONE workgroup -- timing ablations: 14.5 us of the 36 us a 49->128 tile takes, 40 % -- so layers with few input channels
 // per output byte gain from a second resident workgroup whose K loop runs meanwhile, although its activations are then
 // staged once per 64 output channels instead of once per 128.
 template <int TW, int MB, int NTY, int PP = 2, int WPC = 1>
-__global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) void conv2d_bf16x3_pc_kernel(ConvK p, const uint4* __restrict__ wsplit, int CinG, int ntx_max, int ablate) {
-    static_assert(WPC == 1 || (WPC == 2 && MB == 2 && PP == 2 && (NTY == 3 || NTY == -83)), "two workgroups per CU: the 64-channel 3 x 3 forms only");
+__global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) void conv2d_bf16x3_pc_kernel(ConvK p, const uint4* __restrict__ wsplit, int CinG, int ntx_max) {
+    static_assert(WPC == 1 || (WPC == 2 && MB == 2 && PP == 2 && NTY == 3), "two workgroups per CU: the 64-channel 3 x 3 form only");
     static_assert(PP == 2 || (PP == 4 && (NTY > 0 || NTY == -83) && MB == 2), "the 512-pixel tile exists for the VEC / packed staging modes and 64 output channels");
     static_assert(conv_nty_fetch_bytes(NTY) != 0, "unknown staging mode: classify it in conv_common.h (conv_nty_*)");
     constexpr bool VEC = conv_nty_vec(NTY);
@@ -345,16 +338,6 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
     __shared__ float bias_s[32 * MB];   // the workgroup's bias values: read from LDS in the epilogue (see there: no vector-memory wait between its stores)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // Wave priority of the WHOLE workgroup (bits 16-17 of `ablate`, set by the launcher from CCVS_CONV_PRIO): beside the token
-    // loops of other batches every SIMD also hosts waves of the decode kernels, and vector / memory issue is arbitrated by
-    // priority, then age (tools/conv_contention_probe.py: one memory-streaming wave per SIMD costs the convolution 20-35 %,
-    // a VALU-spinning one 140-200 % -- whether its loads hit L2 or HBM makes no difference).
-    {
-        const int prio = (ablate >> 16) & 3;
-        if (prio == 1) __builtin_amdgcn_s_setprio(1);
-        else if (prio == 2) __builtin_amdgcn_s_setprio(2);
-        else if (prio == 3) __builtin_amdgcn_s_setprio(3);
-    }
     // (measured: making the role provably wave-uniform with readfirstlane, or s_setprio(1) on the MFMA
     //  waves, both cost ~25 % on the 195->128 3x3 shape with hipcc / ROCm 7.2 -- left as plain predication)
     const bool producer = wave >= 4;
@@ -370,29 +353,15 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
     CONV_TILE_COORDS(p, bx, by, bz)
     const int ty = bx / p.tiles_x, tx = bx - ty * p.tiles_x;
     const int n0 = by * NT;
-    int n = bz, cls = 0;
-    if (!TAP3 && p.transposed) { cls = n & 3; n >>= 2; }
-    // GEO3 (the written-out 3 x 3 instantiations: stride 1, padding 1, not transposed -- the launcher sees to it): the tap table and
+    const int n = bz;   // (never a transposed layer: the launcher sees to it)
+    // GEO3 (the written-out 3 x 3 instantiations: stride 1, padding 1 -- the launcher sees to it): the tap table and
     // with it the halo tile's geometry (IH, IW, row pitch, plane, item counts) are COMPILE-TIME constants.  The set-up in front of the
     // first barrier was ~1900 instructions per wave, two dozen of them integer divisions by these launch-uniform values (25
     // instructions each): 8.4 k cycles of a tile's 10.8 k-cycle prologue (profiles/r05_conv_ablate_cycles.txt) were this code, not latency.
     constexpr bool GEO3 = TAP3;
-    const AxisTaps ay = GEO3 ? axis_taps_k3(p.Hout) : axis_taps(p.kh, p.stride, p.pad, p.transposed, cls >> 1, p.Hout);
-    const AxisTaps ax = GEO3 ? axis_taps_k3(p.Wout) : axis_taps(p.kw, p.stride, p.pad, p.transposed, cls & 1, p.Wout);
+    const AxisTaps ay = GEO3 ? axis_taps_k3(p.Hout) : axis_taps(p.kh, p.stride, p.pad, 0, 0, p.Hout);
+    const AxisTaps ax = GEO3 ? axis_taps_k3(p.Wout) : axis_taps(p.kw, p.stride, p.pad, 0, 0, p.Wout);
     if (ty * TH >= ay.V || tx * TW >= ax.V) return;
-    if (ablate & 32768) return;   // timing experiments: the cost of dispatching the workgroups alone
-    {   // Phase stagger (bits 18-23 of `ablate`, CCVS_CONV_STAGGER): the first workgroup of every CU starts ph x stg x ~3.8 us late,
-        // ph = 0..7 by dispatch order, so that the CUs do not run their tiles -- whose prologues read and whose epilogues write in
-        // bursts -- in lock-step from the launch on
-        const int stg = (ablate >> 18) & 63;
-        if (stg) {
-            const int lin = p.nwork > 0 ? (int)blockIdx.x : (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-            if (lin < 256) {
-                const int ph = (lin >> 3) & 7;
-                for (int i = 0; i < ph * stg; ++i) __builtin_amdgcn_s_sleep(127);
-            }
-        }
-    }
     if (tid < 32 * MB) bias_s[tid] = (p.bias && n0 + tid < p.Cout) ? p.bias[n0 + tid] : 0.f;   // visible after the first step barrier
 
     const int IH = (TH - 1) * ay.s + ay.ext + 1;
@@ -462,8 +431,7 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
         // 128 B (slot = 4 q + r (4 NQ + 1) mod 8 with 4 NQ + 1 = 1 or 5 mod 8), and their global loads touch 4 cache lines
         // instead of the 8 of the rows-fastest order (a wave-load: 32 lines instead of 64 for the texture addresser).
         const int NQP = (NQ + 1) >> 1;                       // column pairs
-        const bool pairs = !(ablate & 8192);                 // 8192: the rows-fastest order of round 2
-        const int per_half = pairs ? NQP * IH * 2 : IH * NQ;
+        const int per_half = NQP * IH * 2;
         const int n_items = per_half * 2;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
@@ -471,16 +439,10 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
             const int it = min(it0_, n_items - 1);
             vh[j] = it / per_half;
             const int rem = it - vh[j] * per_half;
-            int vq, vr;
-            if (pairs) {
-                const int t = rem >> 1;
-                const int qh = t / IH;
-                vr = t - qh * IH;
-                vq = 2 * qh + (rem & 1);
-            } else {
-                vq = rem / IH;
-                vr = rem - vq * IH;
-            }
+            const int t = rem >> 1;
+            const int qh = t / IH;
+            const int vr = t - qh * IH;
+            int vq = 2 * qh + (rem & 1);
             vitem[j] = it0_ < n_items && vq < NQ;
             vq = min(vq, NQ - 1);
             const int gy = iy0 + vr, gxa = ix0 - xsh + 4 * vq;
@@ -570,7 +532,6 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
     };
     auto load_xv = [&](int set, int c_) {   // `set` is a compile-time constant at every call site
         xvc0[set] = c_ * CB_CC;
-        if (ablate & 16) return;
         const bool full = xvc0[set] + CB_CC <= cin_;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
@@ -597,12 +558,7 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
                     for (int i = 0; i < 8; ++i) v[i] = (vin[j] && xvc0[set] + 8 * vh[j] + i < cin_) ? v[i] : 0.f;
                 }
                 uint4 hi, lo;
-                if (ablate & 8) {
-                    hi = make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3]));
-                    lo = make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7]));
-                } else {
-                    split8(v, hi, lo);
-                }
+                split8(v, hi, lo);
                 dst[(vh[j] * 2 + 0) * plane + ve[j] + px] = hi;
                 dst[(vh[j] * 2 + 1) * plane + ve[j] + px] = lo;
             }
@@ -686,7 +642,6 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
         }
     }
 
-    if (ablate & 4096) return;   // timing experiments: dispatch + address set-up + the first chunk / first weights, no step loop
     // Step -1 only lets the producers fetch the first register bundle (everyone meets at the barrier);
     // steps 0 .. nsteps-1 are the real ones.  (ci, a) = (chunk, tap row) of step s.
     // The two roles run SEPARATE loops that meet at the same barrier once per step: in one shared loop the register
@@ -694,11 +649,10 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
     if (producer && P8IN) {
         // chunk c+1 is requested at step (c, 0) and must have landed when step (c, nt-1) ends; raw s_barrier: a
         // __syncthreads() here would drain the DMA (vmcnt 0) at EVERY step
-        const bool work = !(ablate & 1);
         __builtin_amdgcn_s_barrier();  // step -1
         for (int ci = 0; ci < nchunks; ++ci) {
             for (int a = 0; a < nt; ++a) {
-                if (work && a == 0 && ci + 1 < nchunks) dma_x(ci + 1, in_buf + ((ci + 1) & 1) * in_sz);
+                if (a == 0 && ci + 1 < nchunks) dma_x(ci + 1, in_buf + ((ci + 1) & 1) * in_sz);
                 if (a == nt - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __builtin_amdgcn_s_barrier();
             }
@@ -715,61 +669,51 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
         // have landed -- and the MFMA waves with it.  The loads stay in flight across the barriers; hipcc waits for them
         // where their registers are first read (store_xv, two chunks later).
         constexpr int NTYc = VEC ? NTY : 1;
-        const bool work = !(ablate & (1 | 256));   // 256: weights still arrive, activations are not staged
-        const bool drain = ablate & 64;   // experiments: the old __syncthreads() steps
-        const bool deep = WPC == 1 && !(ablate & 2048);   // 2048: one chunk of lead (the round-2 schedule; always with two workgroups per CU)
-        if (work) {
-            load_xv(0, min(1, nchunks - 1));
-            if (deep) load_xv(1, min(2, nchunks - 1));
-        }
+        constexpr bool deep = WPC == 1;   // two chunks of lead; with two workgroups per CU one (the round-2 schedule)
+        load_xv(0, min(1, nchunks - 1));
+        if (deep) load_xv(1, min(2, nchunks - 1));
         __syncthreads();
         for (int ci = 0; ci < nchunks; ci += 2) {
-            if (work) {   // set 0 holds chunk ci + 1
-                if (ci + 1 < nchunks) store_xv(0, in_buf + ((ci + 1) & 1) * in_sz);
-                if (deep) load_xv(0, min(ci + 3, nchunks - 1));
-                else load_xv(1, min(ci + 2, nchunks - 1));
-            }
+            // set 0 holds chunk ci + 1
+            if (ci + 1 < nchunks) store_xv(0, in_buf + ((ci + 1) & 1) * in_sz);
+            if (deep) load_xv(0, min(ci + 3, nchunks - 1));
+            else load_xv(1, min(ci + 2, nchunks - 1));
 #pragma unroll
             for (int a = 0; a < NTYc; ++a) {
                 if (a > 0 && ktail && ci == nchunks - 1) break;   // the packed tail chunk is one step
-                if (drain) __syncthreads();
-                else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             }
             if (ci + 1 >= nchunks) break;
-            if (work) {   // set 1 holds chunk ci + 2
-                if (ci + 2 < nchunks) store_xv(1, in_buf + ((ci + 2) & 1) * in_sz);
-                if (deep) load_xv(1, min(ci + 4, nchunks - 1));
-                else load_xv(0, min(ci + 3, nchunks - 1));
-            }
+            // set 1 holds chunk ci + 2
+            if (ci + 2 < nchunks) store_xv(1, in_buf + ((ci + 2) & 1) * in_sz);
+            if (deep) load_xv(1, min(ci + 4, nchunks - 1));
+            else load_xv(0, min(ci + 3, nchunks - 1));
 #pragma unroll
             for (int a = 0; a < NTYc; ++a) {
                 if (a > 0 && ktail && ci + 1 == nchunks - 1) break;
-                if (drain) __syncthreads();
-                else asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing (never stored) requests
     } else if (producer) {
       int ci = -1, a = nt - 1;
       for (int s = -1; s < nsteps; ++s) {
-        if (!(ablate & 1)) {
-            if (s >= 0) {  // (1) convert + store the bundle loaded during the previous step
-                if (s + 1 < nsteps) store_w(w_buf + ((s + 1) & 1) * w_sz);
-                if (ci + 1 < nchunks) store_x(a, in_buf + ((ci + 1) & 1) * in_sz);
-            }
-            // (2) issue the loads of the following bundle: W_row(s+2), halo parts of slot a+1
-            int a1 = a + 1, c1 = ci;
-            if (a1 == nt) { a1 = 0; ++c1; }
-            int a2 = a1 + 1, c2 = c1;
-            if (a2 == nt) { a2 = 0; ++c2; }
-            if (s + 2 < nsteps) load_w(c2, a2);
-            const int cx = (a1 == 0) ? ci + 2 : ci + 1;  // chunk whose parts of slot a1 are stored next step
-            if (cx < nchunks) {
-                load_x(cx, a1);
-            } else {
+        if (s >= 0) {  // (1) convert + store the bundle loaded during the previous step
+            if (s + 1 < nsteps) store_w(w_buf + ((s + 1) & 1) * w_sz);
+            if (ci + 1 < nchunks) store_x(a, in_buf + ((ci + 1) & 1) * in_sz);
+        }
+        // (2) issue the loads of the following bundle: W_row(s+2), halo parts of slot a+1
+        int a1 = a + 1, c1 = ci;
+        if (a1 == nt) { a1 = 0; ++c1; }
+        int a2 = a1 + 1, c2 = c1;
+        if (a2 == nt) { a2 = 0; ++c2; }
+        if (s + 2 < nsteps) load_w(c2, a2);
+        const int cx = (a1 == 0) ? ci + 2 : ci + 1;  // chunk whose parts of slot a1 are stored next step
+        if (cx < nchunks) {
+            load_x(cx, a1);
+        } else {
 #pragma unroll
-                for (int q = 0; q < CB_XQ; ++q) xoff[q] = -2;
-            }
+            for (int q = 0; q < CB_XQ; ++q) xoff[q] = -2;
         }
         __syncthreads();
         if (++a == nt) { a = 0; ++ci; }
@@ -777,26 +721,13 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
     } else {
       int ci = -1, a = nt - 1;
       const int nloop = ktail ? nsteps - 1 : nsteps;
-#ifdef CB_STAMPS   // debug build: T0 loop top, T1 weight DMA issued, T2 the step's matrix instructions issued, T3 behind the step barrier
-      const bool stamp_on = p.dbg && tid == 0 && (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) == p.dbg_block;
-#define CB_STAMP(K)                                                                         \
-    if (stamp_on && s >= 0 && s < 24) {                                                     \
-        unsigned long long t_;                                                              \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");          \
-        p.dbg[4 * s + (K)] = (long long)t_;                                                 \
-    }
-#else
-#define CB_STAMP(K)
-#endif
       for (int s = -1; s < nloop; ++s) {
-        CB_STAMP(0)
-        if (DMAW && !(ablate & (1 | 128)) && s + 1 < nsteps) {   // 128: activations still staged, no weight DMA  // weights of step s+1 by LDS-DMA; hipcc drains them (vmcnt 0) at the barrier
+        if (DMAW && s + 1 < nsteps) {   // weights of step s+1 by LDS-DMA; hipcc drains them (vmcnt 0) at the barrier
             int a1 = a + 1, c1 = ci;
             if (a1 == nt) { a1 = 0; ++c1; }
             dma_w(c1, a1, w_buf + ((s + 1) & 1) * w_sz);
         }
-        CB_STAMP(1)
-        if (s >= 0 && !(ablate & 2)) {
+        if (s >= 0) {
             const uint4* it0 = in_buf + (ci & 1) * in_sz + (khalf * 2) * plane + (ay.d0 + a * ay.dd - ay.lo) * IWS;
             const uint4* wt0 = w_buf + (s & 1) * w_sz + (khalf * 2) * NT + (lane & 31);
             if constexpr (PP == 4) {
@@ -948,12 +879,9 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
 #undef CB_TAP
             }
         }
-        CB_STAMP(2)
         __syncthreads();
-        CB_STAMP(3)
         if (++a == nt) { a = 0; ++ci; }
       }
-#undef CB_STAMP
       if constexpr (NTY == 3) {
         if (ktail) {
             // Packed K tail: the last chunk holds r = Cin % 16 <= 3 real channels.  Its nine taps x r channels are contracted
@@ -962,41 +890,39 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
             // requested by the last iteration of the loop above); the pixel operand is gathered from the chunk's staged
             // tile, 2 bytes per (tap, channel) -- once per tile, against 9 - nj tap steps of 6 MB MFMAs saved.  Outside the
             // loop on purpose: inside it hipcc hoists the gather's address arithmetic over the whole loop and spills.
-            if (!(ablate & 2)) {
-                const int s = nsteps - 1;
-                const int r_ = p.ktail, nq_ = 9 * r_, nj_ = (nq_ + 15) >> 4;
-                const unsigned short* ih = reinterpret_cast<const unsigned short*>(in_buf + ((nchunks - 1) & 1) * in_sz);
-                const uint4* wtl = w_buf + (s & 1) * w_sz + (khalf * 2) * NT + (lane & 31);
-                for (int j = 0; j < nj_; ++j) {
-                    bf16x8 gb[PP][2];
+            const int s = nsteps - 1;
+            const int r_ = p.ktail, nq_ = 9 * r_, nj_ = (nq_ + 15) >> 4;
+            const unsigned short* ih = reinterpret_cast<const unsigned short*>(in_buf + ((nchunks - 1) & 1) * in_sz);
+            const uint4* wtl = w_buf + (s & 1) * w_sz + (khalf * 2) * NT + (lane & 31);
+            for (int j = 0; j < nj_; ++j) {
+                bf16x8 gb[PP][2];
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp) {
+                    unsigned hw[4], lw[4];
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        const int q = 16 * j + 8 * khalf + i;
+                        const int qc = min(q, nq_ - 1);
+                        const int t = qc / r_, c = qc - t * r_;
+                        const int tyy = t / 3, txx = t - 3 * tyy;
+                        const int e = (bofs[pp] + tyy * IWS + txx) * 8 + c;   // bf16 index inside the [pixel][8] plane
+                        unsigned hv = ih[e], lv = ih[plane * 8 + e];
+                        if (q >= nq_) { hv = 0; lv = 0; }
+                        if (i & 1) { hw[i >> 1] |= hv << 16; lw[i >> 1] |= lv << 16; }
+                        else { hw[i >> 1] = hv; lw[i >> 1] = lv; }
+                    }
+                    gb[pp][0] = __builtin_bit_cast(bf16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
+                    gb[pp][1] = __builtin_bit_cast(bf16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
+                }
+#pragma unroll
+                for (int m = 0; m < MB; ++m) {
+                    const bf16x8 ah = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + m * 32]);
+                    const bf16x8 al = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + NT + m * 32]);
 #pragma unroll
                     for (int pp = 0; pp < PP; ++pp) {
-                        unsigned hw[4], lw[4];
-#pragma unroll
-                        for (int i = 0; i < 8; ++i) {
-                            const int q = 16 * j + 8 * khalf + i;
-                            const int qc = min(q, nq_ - 1);
-                            const int t = qc / r_, c = qc - t * r_;
-                            const int tyy = t / 3, txx = t - 3 * tyy;
-                            const int e = (bofs[pp] + tyy * IWS + txx) * 8 + c;   // bf16 index inside the [pixel][8] plane
-                            unsigned hv = ih[e], lv = ih[plane * 8 + e];
-                            if (q >= nq_) { hv = 0; lv = 0; }
-                            if (i & 1) { hw[i >> 1] |= hv << 16; lw[i >> 1] |= lv << 16; }
-                            else { hw[i >> 1] = hv; lw[i >> 1] = lv; }
-                        }
-                        gb[pp][0] = __builtin_bit_cast(bf16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
-                        gb[pp][1] = __builtin_bit_cast(bf16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
-                    }
-#pragma unroll
-                    for (int m = 0; m < MB; ++m) {
-                        const bf16x8 ah = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + m * 32]);
-                        const bf16x8 al = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + NT + m * 32]);
-#pragma unroll
-                        for (int pp = 0; pp < PP; ++pp) {
-                            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gb[pp][0], acc[m][pp], 0, 0, 0);
-                            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][1], acc[m][pp], 0, 0, 0);
-                            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][0], acc[m][pp], 0, 0, 0);
-                        }
+                        acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gb[pp][0], acc[m][pp], 0, 0, 0);
+                        acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][1], acc[m][pp], 0, 0, 0);
+                        acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][0], acc[m][pp], 0, 0, 0);
                     }
                 }
             }
@@ -1004,314 +930,282 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
         }
       }
     }
-    if (ablate & 16384) return;   // timing experiments: no epilogue (nothing is written)
     // ---- epilogue ------------------------------------------------------------------------------
     // Dense convolutions: the accumulators (one pixel column per lane, 16 couts in registers) go
     // through LDS so that ALL 8 waves write 16-byte pieces along x (a lane then owns 4 consecutive
     // pixels of one channel) instead of 128 scalar stores per consumer lane: the store tail was
     // issue-bound.  32 couts x 256 pixels per pass, MB passes.
-    if (GEO3 || !p.transposed) {
-        float* stage = reinterpret_cast<float*>(smem4);
-        constexpr int NIT = (8 * NPIX + 255 + NP) / (256 + NP);   // 16-byte pieces of a 32-channel pass per thread
-        constexpr bool LEANK = MB == 1 || WPC == 2;   // kernels capped at 128 registers: the fast path below or the plain piece-by-piece one
-        // addends of the epilogue: 0 none, 1 pre-activation image, 2 residual, 3 accumulate, 4 more than one of them
-        const int add_kind = conv_add_kind(p);
-        const bool fast_epi = add_kind <= 3 && (tx + 1) * TW <= ax.V && (ty + 1) * TH <= ay.V && n0 + NT <= p.Cout && (p.Wout & 3) == 0 &&
-                              (reinterpret_cast<uintptr_t>(p.y) & 15) == 0 && (p.out_sN & 3) == 0 && (p.out_sC & 3) == 0 &&
-                              (add_kind != 1 || ((reinterpret_cast<uintptr_t>(p.pre) & 15) == 0 && (p.pre_sN & 3) == 0 && (p.pre_sC & 3) == 0)) &&
-                              (add_kind != 2 || ((reinterpret_cast<uintptr_t>(p.res) & 15) == 0 && (p.res_sN & 3) == 0 && (p.res_sC & 3) == 0));
+    float* stage = reinterpret_cast<float*>(smem4);
+    constexpr int NIT = (8 * NPIX + 255 + NP) / (256 + NP);   // 16-byte pieces of a 32-channel pass per thread
+    constexpr bool LEANK = MB == 1 || WPC == 2;   // kernels capped at 128 registers: the fast path below or the plain piece-by-piece one
+    // addends of the epilogue: 0 none, 1 pre-activation image, 2 residual, 3 accumulate, 4 more than one of them
+    const int add_kind = conv_add_kind(p);
+    const bool fast_epi = add_kind <= 3 && (tx + 1) * TW <= ax.V && (ty + 1) * TH <= ay.V && n0 + NT <= p.Cout && (p.Wout & 3) == 0 &&
+                          (reinterpret_cast<uintptr_t>(p.y) & 15) == 0 && (p.out_sN & 3) == 0 && (p.out_sC & 3) == 0 &&
+                          (add_kind != 1 || ((reinterpret_cast<uintptr_t>(p.pre) & 15) == 0 && (p.pre_sN & 3) == 0 && (p.pre_sC & 3) == 0)) &&
+                          (add_kind != 2 || ((reinterpret_cast<uintptr_t>(p.res) & 15) == 0 && (p.res_sN & 3) == 0 && (p.res_sC & 3) == 0));
 #pragma unroll
-        for (int m = 0; m < MB; ++m) {
-            const bool p8_out = (PP == 2 || P8IN) && p.out_p8;
-            if (!producer) {
-                if (p8_out) {
-                    // packed output: the pass is staged [pixel][32 channels] (36 floats apart: conflict-free 16-byte accesses) -- a
-                    // lane writes its four groups of 4 consecutive channels as ds_write_b128, a reader fetches the 8 channels of its
-                    // pixel as two ds_read_b128 (channel-major staging cost the packed epilogue 8 ds_read_b32 per item: the
-                    // 128-channel producers ran 20 % slower than with fp32 output)
+    for (int m = 0; m < MB; ++m) {
+        const bool p8_out = (PP == 2 || P8IN) && p.out_p8;
+        if (!producer) {
+            if (p8_out) {
+                // packed output: the pass is staged [pixel][32 channels] (36 floats apart: conflict-free 16-byte accesses) -- a
+                // lane writes its four groups of 4 consecutive channels as ds_write_b128, a reader fetches the 8 channels of its
+                // pixel as two ds_read_b128 (channel-major staging cost the packed epilogue 8 ds_read_b32 per item: the
+                // 128-channel producers ran 20 % slower than with fp32 output)
 #pragma unroll
-                    for (int pp = 0; pp < PP; ++pp) {
-                        float* sp = stage + ((rw * PP + pp) * 32 + (lane & 31)) * 36 + 4 * khalf;
+                for (int pp = 0; pp < PP; ++pp) {
+                    float* sp = stage + ((rw * PP + pp) * 32 + (lane & 31)) * 36 + 4 * khalf;
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const f32x4 q4 = {acc[m][pp][4 * g], acc[m][pp][4 * g + 1], acc[m][pp][4 * g + 2], acc[m][pp][4 * g + 3]};
-                            *reinterpret_cast<f32x4*>(sp + 8 * g) = q4;
-                        }
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x4 q4 = {acc[m][pp][4 * g], acc[m][pp][4 * g + 1], acc[m][pp][4 * g + 2], acc[m][pp][4 * g + 3]};
+                        *reinterpret_cast<f32x4*>(sp + 8 * g) = q4;
                     }
-                } else {
-#pragma unroll
-                    for (int pp = 0; pp < PP; ++pp)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            stage[((r & 3) + 8 * (r >> 2) + 4 * khalf) * NPIX + (rw * PP + pp) * 32 + (lane & 31)] = acc[m][pp][r];
                 }
+            } else {
+#pragma unroll
+                for (int pp = 0; pp < PP; ++pp)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        stage[((r & 3) + 8 * (r >> 2) + 4 * khalf) * NPIX + (rw * PP + pp) * 32 + (lane & 31)] = acc[m][pp][r];
             }
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: the previous pass's stores stay in flight
-            if (p8_out) {   // (the 512-pixel tile writes packed output only in its packed-input form)
-                // packed output: a thread takes one pixel x 8 output channels of the staged 32 x 256 block, applies the
-                // epilogue, splits to hi / lo and writes two 16-byte units (lanes = consecutive pixels: coalesced)
-                uint4* y4 = reinterpret_cast<uint4*>(p.y);
-                const int gout = (p.Cout + 7) >> 3;
-                const long hw_out = (long)p.Hout * p.Wout;
-                // (bias from LDS; with a pre-activation image its values for all items are fetched first, WITHOUT one the code path holds
-                //  no vector-memory load at all: a load that is merely conditional still makes hipcc wait, vmcnt(0), where its value
-                //  would be used -- i.e. for the stores of the item before; see the fp32 epilogue below)
-                constexpr int NI8 = 4 * NPIX / 512;   // (pixel, 8 channels) items of a 32-channel pass per thread
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: the previous pass's stores stay in flight
+        if (p8_out) {   // (the 512-pixel tile writes packed output only in its packed-input form)
+            // packed output: a thread takes one pixel x 8 output channels of the staged 32 x 256 block, applies the
+            // epilogue, splits to hi / lo and writes two 16-byte units (lanes = consecutive pixels: coalesced)
+            uint4* y4 = reinterpret_cast<uint4*>(p.y);
+            const int gout = (p.Cout + 7) >> 3;
+            const long hw_out = (long)p.Hout * p.Wout;
+            // (bias from LDS; with a pre-activation image its values for all items are fetched first, WITHOUT one the code path holds
+            //  no vector-memory load at all: a load that is merely conditional still makes hipcc wait, vmcnt(0), where its value
+            //  would be used -- i.e. for the stores of the item before; see the fp32 epilogue below)
+            constexpr int NI8 = 4 * NPIX / 512;   // (pixel, 8 channels) items of a 32-channel pass per thread
 #define CB_P8_ITEM(i)                                                                          \
-        const int item_ = tid + 512 * (i);                                                     \
-        const int gq_ = item_ / NPIX, px_ = item_ - gq_ * NPIX;                                \
-        const int co0_ = n0 + m * 32 + gq_ * 8;                                                \
-        const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                                  \
-        const int vy_ = ty * TH + prow_, vx_ = tx * TW + pcol_;                                \
-        const bool ok_ = co0_ < p.Cout && vy_ < ay.V && vx_ < ax.V;                            \
-        const long opix_ = ok_ ? (long)vy_ * p.Wout + vx_ : 0;
+    const int item_ = tid + 512 * (i);                                                         \
+    const int gq_ = item_ / NPIX, px_ = item_ - gq_ * NPIX;                                    \
+    const int co0_ = n0 + m * 32 + gq_ * 8;                                                    \
+    const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                                      \
+    const int vy_ = ty * TH + prow_, vx_ = tx * TW + pcol_;                                    \
+    const bool ok_ = co0_ < p.Cout && vy_ < ay.V && vx_ < ax.V;                                \
+    const long opix_ = ok_ ? (long)vy_ * p.Wout + vx_ : 0;
 #define CB_P8_FINISH(PRE)                                                                      \
-    _Pragma("unroll") for (int i = 0; i < NI8; ++i) {                                          \
-        CB_P8_ITEM(i)                                                                          \
-        if (ok_) {                                                                             \
-            float v[8];                                                                        \
-            const f32x4 s0 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8);      \
-            const f32x4 s1 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8 + 4);  \
-            _Pragma("unroll") for (int c = 0; c < 8; ++c) {                                    \
-                float t = c < 4 ? s0[c] : s1[c - 4];                                           \
-                t += (PRE);                                                                    \
-                t += bias_s[m * 32 + gq_ * 8 + c];                                             \
-                if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                   \
-                v[c] = t * p.out_scale;                                                        \
-            }                                                                                  \
-            uint4 hi, lo;                                                                      \
-            split8(v, hi, lo);                                                                 \
-            uint4* dst = y4 + ((long)n * gout + (co0_ >> 3)) * 2 * hw_out + opix_;             \
-            cb_store16(dst, hi);                                                               \
-            cb_store16(dst + hw_out, lo);                                                      \
+_Pragma("unroll") for (int i = 0; i < NI8; ++i) {                                              \
+    CB_P8_ITEM(i)                                                                              \
+    if (ok_) {                                                                                 \
+        float v[8];                                                                            \
+        const f32x4 s0 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8);          \
+        const f32x4 s1 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8 + 4);      \
+        _Pragma("unroll") for (int c = 0; c < 8; ++c) {                                        \
+            float t = c < 4 ? s0[c] : s1[c - 4];                                               \
+            t += (PRE);                                                                        \
+            t += bias_s[m * 32 + gq_ * 8 + c];                                                 \
+            if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                       \
+            v[c] = t * p.out_scale;                                                            \
         }                                                                                      \
-    }
-                if (p.pre) {
-                    float pv[NI8][8];
-                    const float* pb = p.pre + (long)(n / p.pre_div) * p.pre_sN;
+        uint4 hi, lo;                                                                          \
+        split8(v, hi, lo);                                                                     \
+        uint4* dst = y4 + ((long)n * gout + (co0_ >> 3)) * 2 * hw_out + opix_;                 \
+        cb_store16(dst, hi);                                                                   \
+        cb_store16(dst + hw_out, lo);                                                          \
+    }                                                                                          \
+}
+            if (p.pre) {
+                float pv[NI8][8];
+                const float* pb = p.pre + (long)(n / p.pre_div) * p.pre_sN;
 #pragma unroll
-                    for (int i = 0; i < NI8; ++i) {
-                        CB_P8_ITEM(i)
+                for (int i = 0; i < NI8; ++i) {
+                    CB_P8_ITEM(i)
 #pragma unroll
-                        for (int c = 0; c < 8; ++c) pv[i][c] = pb[(long)min(co0_ + c, p.Cout - 1) * p.pre_sC + opix_];
-                    }
-                    CB_P8_FINISH(pv[i][c])
-                } else {
-                    CB_P8_FINISH(0.f)
+                    for (int c = 0; c < 8; ++c) pv[i][c] = pb[(long)min(co0_ + c, p.Cout - 1) * p.pre_sC + opix_];
                 }
+                CB_P8_FINISH(pv[i][c])
+            } else {
+                CB_P8_FINISH(0.f)
+            }
 #undef CB_P8_ITEM
 #undef CB_P8_FINISH
-                if (m + 1 < MB) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-                continue;
-            }
-            if constexpr (P8IN && PP == 4) {   // this instantiation writes packed output only (the launcher sees to it): its fp32
-                continue;                        // epilogue, compiled in as well, keeps hipcc from unrolling the pass loop
-            } else {
-            // No wait on vector memory inside the store loop: `s_waitcnt vmcnt` counts stores too, so a wait for a load issued
-            // after a store -- the bias value, the residual of the next piece -- also waits until that store has been
-            // acknowledged by memory (~0.6 us).  With the loads of every piece interleaved with its store the tile's 131 KB left
-            // the CU one round trip at a time: 9.9 us per 128-channel tile (CCVS_CONV_ABLATE runs), a quarter of the time a
-            // 49->128 tile takes.  The bias values are fetched once in front of the first pass; a layer without addends
-            // (most of them) issues no load at all here, the others fetch the addends of ALL pieces of a pass first.
-            auto piece = [&](int i, int& co, long& opix, int& nv, int& col, int& px) -> bool {
-                const int idx4 = tid + (256 + NP) * i;
-                col = idx4 / (NPIX / 4);
-                px = (idx4 % (NPIX / 4)) * 4;
-                co = n0 + m * 32 + col;
-                const int prow = px / TW, pcol = px - prow * TW;
-                const int vy = ty * TH + prow, vx = tx * TW + pcol;
-                opix = (long)vy * p.Wout + vx;
-                nv = min(4, ax.V - vx);
-                return idx4 < 8 * NPIX && co < p.Cout && vy < ay.V && vx < ax.V;
-            };
-            if (fast_epi) {
-                // The whole tile inside the image, every output channel real, every row 16-byte aligned (the layers that matter):
-                // straight-line code -- hipcc can then COUNT its waits (vmcnt(n) for the addend of piece i leaves the stores of
-                // the pieces before it in flight; behind a per-piece branch it falls back to vmcnt(0))
-                const float* abase = add_kind == 1 ? p.pre + (long)(n / p.pre_div) * p.pre_sN : add_kind == 2 ? p.res + (long)n * p.res_sN : p.y + (long)n * p.out_sN;
-                const long a_sC = add_kind == 1 ? p.pre_sC : add_kind == 2 ? p.res_sC : p.out_sC;
-                float* ybase = p.y + (long)n * p.out_sN;
-                // (offsets are recomputed where they are used: kept in arrays across the two phases they cost the 32-channel kernels,
-                //  capped at 128 registers, a spill)
+            if (m + 1 < MB) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+            continue;
+        }
+        if constexpr (P8IN && PP == 4) {   // this instantiation writes packed output only (the launcher sees to it): its fp32
+            continue;                        // epilogue, compiled in as well, keeps hipcc from unrolling the pass loop
+        } else {
+        // No wait on vector memory inside the store loop: `s_waitcnt vmcnt` counts stores too, so a wait for a load issued
+        // after a store -- the bias value, the residual of the next piece -- also waits until that store has been
+        // acknowledged by memory (~0.6 us).  With the loads of every piece interleaved with its store the tile's 131 KB left
+        // the CU one round trip at a time: 9.9 us per 128-channel tile (timing ablations), a quarter of the time a
+        // 49->128 tile takes.  The bias values are fetched once in front of the first pass; a layer without addends
+        // (most of them) issues no load at all here, the others fetch the addends of ALL pieces of a pass first.
+        auto piece = [&](int i, int& co, long& opix, int& nv, int& col, int& px) -> bool {
+            const int idx4 = tid + (256 + NP) * i;
+            col = idx4 / (NPIX / 4);
+            px = (idx4 % (NPIX / 4)) * 4;
+            co = n0 + m * 32 + col;
+            const int prow = px / TW, pcol = px - prow * TW;
+            const int vy = ty * TH + prow, vx = tx * TW + pcol;
+            opix = (long)vy * p.Wout + vx;
+            nv = min(4, ax.V - vx);
+            return idx4 < 8 * NPIX && co < p.Cout && vy < ay.V && vx < ax.V;
+        };
+        if (fast_epi) {
+            // The whole tile inside the image, every output channel real, every row 16-byte aligned (the layers that matter):
+            // straight-line code -- hipcc can then COUNT its waits (vmcnt(n) for the addend of piece i leaves the stores of
+            // the pieces before it in flight; behind a per-piece branch it falls back to vmcnt(0))
+            const float* abase = add_kind == 1 ? p.pre + (long)(n / p.pre_div) * p.pre_sN : add_kind == 2 ? p.res + (long)n * p.res_sN : p.y + (long)n * p.out_sN;
+            const long a_sC = add_kind == 1 ? p.pre_sC : add_kind == 2 ? p.res_sC : p.out_sC;
+            float* ybase = p.y + (long)n * p.out_sN;
+            // (offsets are recomputed where they are used: kept in arrays across the two phases they cost the 32-channel kernels,
+            //  capped at 128 registers, a spill)
 #define CB_EPI_OFFS(i)                                                                               \
-        const int idx4_ = tid + (256 + NP) * (i);                                                    \
-        const int col_ = idx4_ / (NPIX / 4), px_ = (idx4_ % (NPIX / 4)) * 4;                         \
-        const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                                        \
-        const long opix_ = (long)(ty * TH + prow_) * p.Wout + tx * TW + pcol_;                       \
-        const int co_ = n0 + m * 32 + col_;
+    const int idx4_ = tid + (256 + NP) * (i);                                                        \
+    const int col_ = idx4_ / (NPIX / 4), px_ = (idx4_ % (NPIX / 4)) * 4;                             \
+    const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                                            \
+    const long opix_ = (long)(ty * TH + prow_) * p.Wout + tx * TW + pcol_;                           \
+    const int co_ = n0 + m * 32 + col_;
 #define CB_EPI_FINISH(ADD1, ADD2, ADD3)                                                              \
-    _Pragma("unroll") for (int i = 0; i < NIT; ++i) {                                                \
-        CB_EPI_OFFS(i)                                                                               \
-        const float4 a4 = *reinterpret_cast<const float4*>(stage + col_ * NPIX + px_);              \
-        float v[4] = {a4.x, a4.y, a4.z, a4.w};                                                       \
-        const float bv = bias_s[m * 32 + col_];                                                      \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                              \
-            float t = (v[j] + (ADD1)) + bv;                                                          \
-            if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                             \
-            t = (t + (ADD2)) * p.out_scale;                                                          \
-            v[j] = t + (ADD3);                                                                       \
-        }                                                                                            \
-        cb_store16(ybase + (long)co_ * p.out_sC + opix_, f32x4{v[0], v[1], v[2], v[3]});           \
-    }
-                if (add_kind == 0) {
-                    CB_EPI_FINISH(0.f, 0.f, 0.f)
-                } else {
-                    f32x4 ad[NIT];
+_Pragma("unroll") for (int i = 0; i < NIT; ++i) {                                                    \
+    CB_EPI_OFFS(i)                                                                                   \
+    const float4 a4 = *reinterpret_cast<const float4*>(stage + col_ * NPIX + px_);                  \
+    float v[4] = {a4.x, a4.y, a4.z, a4.w};                                                           \
+    const float bv = bias_s[m * 32 + col_];                                                          \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                  \
+        float t = (v[j] + (ADD1)) + bv;                                                              \
+        if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                                 \
+        t = (t + (ADD2)) * p.out_scale;                                                              \
+        v[j] = t + (ADD3);                                                                           \
+    }                                                                                                \
+    cb_store16(ybase + (long)co_ * p.out_sC + opix_, f32x4{v[0], v[1], v[2], v[3]});               \
+}
+            if (add_kind == 0) {
+                CB_EPI_FINISH(0.f, 0.f, 0.f)
+            } else {
+                f32x4 ad[NIT];
 #pragma unroll
-                    for (int i = 0; i < NIT; ++i) {
-                        CB_EPI_OFFS(i)
-                        ad[i] = *reinterpret_cast<const f32x4*>(abase + (long)co_ * a_sC + opix_);
-                    }
-                    if (add_kind == 1) { CB_EPI_FINISH(ad[i][j], 0.f, 0.f) }
-                    else if (add_kind == 2) { CB_EPI_FINISH(0.f, ad[i][j], 0.f) }
-                    else { CB_EPI_FINISH(0.f, 0.f, ad[i][j]) }
+                for (int i = 0; i < NIT; ++i) {
+                    CB_EPI_OFFS(i)
+                    ad[i] = *reinterpret_cast<const f32x4*>(abase + (long)co_ * a_sC + opix_);
                 }
+                if (add_kind == 1) { CB_EPI_FINISH(ad[i][j], 0.f, 0.f) }
+                else if (add_kind == 2) { CB_EPI_FINISH(0.f, ad[i][j], 0.f) }
+                else { CB_EPI_FINISH(0.f, 0.f, ad[i][j]) }
+            }
 #undef CB_EPI_OFFS
 #undef CB_EPI_FINISH
-            } else if (!LEANK && add_kind == 0) {
-                // no addend (most layers): a code path of its own WITHOUT any vector-memory load, so that hipcc has no reason to
-                // put a wait between the stores (a conditional load makes it wait with vmcnt(0) at the first use of the value)
+        } else if (!LEANK && add_kind == 0) {
+            // no addend (most layers): a code path of its own WITHOUT any vector-memory load, so that hipcc has no reason to
+            // put a wait between the stores (a conditional load makes it wait with vmcnt(0) at the first use of the value)
 #pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    int co, nv, col, px;
-                    long opix;
-                    if (!piece(i, co, opix, nv, col, px)) continue;
-                    const float4 a4 = *reinterpret_cast<const float4*>(stage + col * NPIX + px);
-                    float v[4] = {a4.x, a4.y, a4.z, a4.w};
-                    const float bv = bias_s[m * 32 + col];
-                    float* dst = p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
+            for (int i = 0; i < NIT; ++i) {
+                int co, nv, col, px;
+                long opix;
+                if (!piece(i, co, opix, nv, col, px)) continue;
+                const float4 a4 = *reinterpret_cast<const float4*>(stage + col * NPIX + px);
+                float v[4] = {a4.x, a4.y, a4.z, a4.w};
+                const float bv = bias_s[m * 32 + col];
+                float* dst = p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float t = (v[j] + 0.f) + bv;
+                    if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);
+                    v[j] = (t + 0.f) * p.out_scale + 0.f;
+                }
+                if (nv == 4 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+                    cb_store16(dst, f32x4{v[0], v[1], v[2], v[3]});
+                } else {
+                    _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) dst[j] = v[j];
+                }
+            }
+        } else if (!LEANK && add_kind <= 3) {
+            // exactly one addend: its pieces are fetched first, then every piece is finished and stored
+            float ad[NIT][4];
+#pragma unroll
+            for (int i = 0; i < NIT; ++i) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) ad[i][j] = 0.f;
+                int co, nv, col, px;
+                long opix;
+                if (!piece(i, co, opix, nv, col, px)) continue;
+                const float* src = add_kind == 1 ? p.pre + (long)(n / p.pre_div) * p.pre_sN + (long)co * p.pre_sC + opix
+                                 : add_kind == 2 ? p.res + (long)n * p.res_sN + (long)co * p.res_sC + opix
+                                                 : p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
+                if (nv == 4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
+                    const float4 t = *reinterpret_cast<const float4*>(src);
+                    ad[i][0] = t.x; ad[i][1] = t.y; ad[i][2] = t.z; ad[i][3] = t.w;
+                } else {
+                    _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) ad[i][j] = src[j];
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NIT; ++i) {
+                int co, nv, col, px;
+                long opix;
+                if (!piece(i, co, opix, nv, col, px)) continue;
+                const float4 a4 = *reinterpret_cast<const float4*>(stage + col * NPIX + px);
+                float v[4] = {a4.x, a4.y, a4.z, a4.w};
+                const float bv = bias_s[m * 32 + col];
+                float* dst = p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    float t = (v[j] + (add_kind == 1 ? ad[i][j] : 0.f)) + bv;
+                    if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);
+                    t = (t + (add_kind == 2 ? ad[i][j] : 0.f)) * p.out_scale;
+                    v[j] = t + (add_kind == 3 ? ad[i][j] : 0.f);
+                }
+                if (nv == 4 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+                    cb_store16(dst, f32x4{v[0], v[1], v[2], v[3]});
+                } else {
+                    _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) dst[j] = v[j];
+                }
+            }
+        } else {
+            // piece by piece (several addends at once -- no layer of the models does this -- and the ragged tiles of the
+            // register-capped kernels): the form of rounds 1-3
+#pragma unroll
+            for (int i = 0; i < NIT; ++i) {
+                int co, nv, col, px;
+                long opix;
+                if (!piece(i, co, opix, nv, col, px)) continue;
+                const float4 a4 = *reinterpret_cast<const float4*>(stage + col * NPIX + px);
+                float v[4] = {a4.x, a4.y, a4.z, a4.w};
+                const float bv = bias_s[m * 32 + col];
+                float* dst = p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
+                const float* rsrc = p.res ? p.res + (long)n * p.res_sN + (long)co * p.res_sC + opix : nullptr;
+                const float* psrc = p.pre ? p.pre + (long)(n / p.pre_div) * p.pre_sN + (long)co * p.pre_sC + opix : nullptr;
+                const bool vec = (nv == 4) && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) &&
+                                 (!rsrc || (reinterpret_cast<uintptr_t>(rsrc) & 15) == 0) &&
+                                 (!psrc || (reinterpret_cast<uintptr_t>(psrc) & 15) == 0);
+                float rv[4] = {0.f, 0.f, 0.f, 0.f}, ov[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
+                if (vec) {
+                    if (psrc) { const float4 t = *reinterpret_cast<const float4*>(psrc); pv[0] = t.x; pv[1] = t.y; pv[2] = t.z; pv[3] = t.w; }
+                    if (rsrc) { const float4 t = *reinterpret_cast<const float4*>(rsrc); rv[0] = t.x; rv[1] = t.y; rv[2] = t.z; rv[3] = t.w; }
+                    if (p.accumulate) { const float4 t = *reinterpret_cast<const float4*>(dst); ov[0] = t.x; ov[1] = t.y; ov[2] = t.z; ov[3] = t.w; }
+                } else {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        float t = (v[j] + 0.f) + bv;
-                        if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);
-                        v[j] = (t + 0.f) * p.out_scale + 0.f;
-                    }
-                    if (nv == 4 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-                        cb_store16(dst, f32x4{v[0], v[1], v[2], v[3]});
-                    } else {
-                        _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) dst[j] = v[j];
-                    }
-                }
-            } else if (!LEANK && add_kind <= 3) {
-                // exactly one addend: its pieces are fetched first, then every piece is finished and stored
-                float ad[NIT][4];
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) ad[i][j] = 0.f;
-                    int co, nv, col, px;
-                    long opix;
-                    if (!piece(i, co, opix, nv, col, px)) continue;
-                    const float* src = add_kind == 1 ? p.pre + (long)(n / p.pre_div) * p.pre_sN + (long)co * p.pre_sC + opix
-                                     : add_kind == 2 ? p.res + (long)n * p.res_sN + (long)co * p.res_sC + opix
-                                                     : p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
-                    if (nv == 4 && (reinterpret_cast<uintptr_t>(src) & 15) == 0) {
-                        const float4 t = *reinterpret_cast<const float4*>(src);
-                        ad[i][0] = t.x; ad[i][1] = t.y; ad[i][2] = t.z; ad[i][3] = t.w;
-                    } else {
-                        _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) ad[i][j] = src[j];
-                    }
-                }
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    int co, nv, col, px;
-                    long opix;
-                    if (!piece(i, co, opix, nv, col, px)) continue;
-                    const float4 a4 = *reinterpret_cast<const float4*>(stage + col * NPIX + px);
-                    float v[4] = {a4.x, a4.y, a4.z, a4.w};
-                    const float bv = bias_s[m * 32 + col];
-                    float* dst = p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float t = (v[j] + (add_kind == 1 ? ad[i][j] : 0.f)) + bv;
-                        if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);
-                        t = (t + (add_kind == 2 ? ad[i][j] : 0.f)) * p.out_scale;
-                        v[j] = t + (add_kind == 3 ? ad[i][j] : 0.f);
-                    }
-                    if (nv == 4 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-                        cb_store16(dst, f32x4{v[0], v[1], v[2], v[3]});
-                    } else {
-                        _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) dst[j] = v[j];
-                    }
-                }
-            } else {
-                // piece by piece (several addends at once -- no layer of the models does this -- and the ragged tiles of the
-                // register-capped kernels): the form of rounds 1-3
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    int co, nv, col, px;
-                    long opix;
-                    if (!piece(i, co, opix, nv, col, px)) continue;
-                    const float4 a4 = *reinterpret_cast<const float4*>(stage + col * NPIX + px);
-                    float v[4] = {a4.x, a4.y, a4.z, a4.w};
-                    const float bv = bias_s[m * 32 + col];
-                    float* dst = p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
-                    const float* rsrc = p.res ? p.res + (long)n * p.res_sN + (long)co * p.res_sC + opix : nullptr;
-                    const float* psrc = p.pre ? p.pre + (long)(n / p.pre_div) * p.pre_sN + (long)co * p.pre_sC + opix : nullptr;
-                    const bool vec = (nv == 4) && ((reinterpret_cast<uintptr_t>(dst) & 15) == 0) &&
-                                     (!rsrc || (reinterpret_cast<uintptr_t>(rsrc) & 15) == 0) &&
-                                     (!psrc || (reinterpret_cast<uintptr_t>(psrc) & 15) == 0);
-                    float rv[4] = {0.f, 0.f, 0.f, 0.f}, ov[4] = {0.f, 0.f, 0.f, 0.f}, pv[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (vec) {
-                        if (psrc) { const float4 t = *reinterpret_cast<const float4*>(psrc); pv[0] = t.x; pv[1] = t.y; pv[2] = t.z; pv[3] = t.w; }
-                        if (rsrc) { const float4 t = *reinterpret_cast<const float4*>(rsrc); rv[0] = t.x; rv[1] = t.y; rv[2] = t.z; rv[3] = t.w; }
-                        if (p.accumulate) { const float4 t = *reinterpret_cast<const float4*>(dst); ov[0] = t.x; ov[1] = t.y; ov[2] = t.z; ov[3] = t.w; }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            if (j < nv) {
-                                if (psrc) pv[j] = psrc[j];
-                                if (rsrc) rv[j] = rsrc[j];
-                                if (p.accumulate) ov[j] = dst[j];
-                            }
+                        if (j < nv) {
+                            if (psrc) pv[j] = psrc[j];
+                            if (rsrc) rv[j] = rsrc[j];
+                            if (p.accumulate) ov[j] = dst[j];
                         }
                     }
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        float t = (v[j] + pv[j]) + bv;
-                        if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);
-                        t = (t + rv[j]) * p.out_scale;
-                        v[j] = t + ov[j];
-                    }
-                    if (vec) {
-                        cb_store16(dst, f32x4{v[0], v[1], v[2], v[3]});
-                    } else {
-                        _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) dst[j] = v[j];
-                    }
                 }
-            }
-            if (m + 1 < MB) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (LDS only: the stores stay in flight)
-            }
-        }
-    } else if (!producer) {
 #pragma unroll
-    for (int pp = 0; pp < PP; ++pp) {
-        const int pj = (rw * PP + pp) * 32 + (lane & 31);
-        const int prow = pj / TW, pcol = pj - prow * TW;
-        const int vy = ty * TH + prow, vx = tx * TW + pcol;
-        if (vy >= ay.V || vx >= ax.V) continue;
-        const int oy = vy * ay.os + ay.oo, ox = vx * ax.os + ax.oo;
-        const long opix = (long)oy * p.Wout + ox;
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-            // (this path is taken by experiments only -- transposed layers run the synchronous kernel: the form of rounds 1-3)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = n0 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * khalf;
-                if (co < p.Cout) {
-                    float v = acc[m][pp][r];
-                    if (p.pre) v += p.pre[(long)(n / p.pre_div) * p.pre_sN + (long)co * p.pre_sC + opix];
-                    if (p.bias) v += p.bias[co];
-                    if (p.act == CCVS_ACT_LRELU) v = lrelu01(v);
-                    if (p.res) v += p.res[(long)n * p.res_sN + (long)co * p.res_sC + opix];
-                    v *= p.out_scale;
-                    float* dst = p.y + (long)n * p.out_sN + (long)co * p.out_sC + opix;
-                    if (p.accumulate) v += *dst;
-                    *dst = v;
+                for (int j = 0; j < 4; ++j) {
+                    float t = (v[j] + pv[j]) + bv;
+                    if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);
+                    t = (t + rv[j]) * p.out_scale;
+                    v[j] = t + ov[j];
+                }
+                if (vec) {
+                    cb_store16(dst, f32x4{v[0], v[1], v[2], v[3]});
+                } else {
+                    _Pragma("unroll") for (int j = 0; j < 4; ++j) if (j < nv) dst[j] = v[j];
                 }
             }
         }
-    }
+        if (m + 1 < MB) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (LDS only: the stores stay in flight)
+        }
     }
 }
 
@@ -1323,10 +1217,8 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
         if (e_ != hipSuccess) fprintf(stderr, "ccvs_conv2d_bf16x3: LDS limit of %s refused: %s\n", #KERNEL, hipGetErrorString(e_)); \
     } while (0)
 
-static int xcd_aware_p8() {
-    static const int v = getenv("CCVS_CONV_XCD") ? atoi(getenv("CCVS_CONV_XCD")) : 1;
-    return v;
-}
+// ConvK::xcd_chunk of a launch of n workgroups: the XCD-aware tile order (CONV_TILE_COORDS) where n splits into 8 runs of >= 8
+static int conv_xcd_chunk(long n) { return (n % 8 == 0 && n >= 64) ? (int)(n / 8) : 0; }
 
 // workgroups of kernel `fn` that fit one CU (HIP occupancy query, cached per kernel and LDS size)
 static int conv_occupancy(const void* fn, int threads, size_t smem_bytes) {
@@ -1337,8 +1229,6 @@ static int conv_occupancy(const void* fn, int threads, size_t smem_bytes) {
         if (cache[i].fn == fn && cache[i].smem == smem_bytes) return cache[i].occ;
     int occ = 1;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, threads, smem_bytes) != hipSuccess || occ < 1) occ = 1;
-    static const int occ_max = getenv("CCVS_CONV_CHUNK_OCC") ? atoi(getenv("CCVS_CONV_CHUNK_OCC")) : 0;  // experiments: cap workgroups per CU
-    if (occ_max > 0 && occ > occ_max) occ = occ_max;
     if (n_cache < 64) cache[n_cache++] = Entry{fn, smem_bytes, occ};
     return occ;
 }
@@ -1359,7 +1249,6 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
     }
     static bool attr_set = false;
     if (!attr_set) {
-        CB_SET_LDS((conv2d_bf16x3_kernel<TW, MB, 4>), 159 * 1024);
         CB_SET_LDS((conv2d_bf16x3_kernel<TW, MB, 8>), 159 * 1024);
         CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 0>), 159 * 1024);   // (+ the static bias block)
         CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -2>), 159 * 1024);   // (+ the static bias block)
@@ -1368,15 +1257,7 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 3>), 159 * 1024);   // (+ the static bias block)
         attr_set = true;
     }
-    static const int ablate_env = getenv("CCVS_CONV_ABLATE") ? atoi(getenv("CCVS_CONV_ABLATE")) : 0;  // timing experiments only (1: no staging, 2: no MFMA, 4: scalar staging, 128: no weight DMA, 256: no activation staging)
-    static const int conv_prio = getenv("CCVS_CONV_PRIO") ? atoi(getenv("CCVS_CONV_PRIO")) : 0;   // s_setprio of the producer / consumer kernels (0-3)
-    static const int conv_stagger = getenv("CCVS_CONV_STAGGER") ? atoi(getenv("CCVS_CONV_STAGGER")) : 0;   // experiments: phase stagger of the first workgroups (units of ~3.8 us)
-    const int ablate = (ablate_env & 0xffff) | ((conv_prio & 3) << 16) | ((conv_stagger & 63) << 18);
     ConvK k = k_in;
-#ifdef CB_STAMPS
-    k.dbg = getenv("CCVS_CONV_DBG") ? (long long*)strtoull(getenv("CCVS_CONV_DBG"), nullptr, 0) : nullptr;
-    k.dbg_block = getenv("CCVS_CONV_DBG_BLOCK") ? atoi(getenv("CCVS_CONV_DBG_BLOCK")) : 0;
-#endif
     if constexpr (TW == 32 && (MB == 4 || MB == 2)) {
         // persistent tiles (conv2d_bf16_pt.h): resident workgroups walk the tiles, a tile's prologue runs under the step loop of the tile before
         const int pt_on = k.pt;   // bit 0: fp32-input 128-channel layers, bit 1: packed-input layers (set per launch by the dispatcher, conv2d_bf16.hip)
@@ -1391,11 +1272,10 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
     // CUs and work on another stream (the token loop of the next batch) always finds the remaining ones free.
     long n_chunk = 1, cap = 0;
     const long total = (long)grid3.x * grid3.y * grid3.z;
-    static const int xcd_aware = getenv("CCVS_CONV_XCD") ? atoi(getenv("CCVS_CONV_XCD")) : 1;
     auto plan = [&](const void* fn, int threads, size_t smem_bytes) {
         k.nwork = 0; k.work0 = 0;
         k.gx = (int)grid3.x; k.gy = (int)grid3.y;
-        k.xcd_chunk = (xcd_aware && total % 8 == 0 && total >= 64) ? (int)(total / 8) : 0;
+        k.xcd_chunk = conv_xcd_chunk(total);
         n_chunk = 1;
         if (k.cu_limit <= 0) return;
         cap = (long)k.cu_limit * conv_occupancy(fn, threads, smem_bytes);
@@ -1409,7 +1289,7 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         if (k.nwork == 0) return grid3;
         k.work0 = (int)(c * cap);
         const long n = (total - c * cap < cap) ? total - c * cap : cap;
-        k.xcd_chunk = (xcd_aware && n % 8 == 0 && n >= 64) ? (int)(n / 8) : 0;   // within the chunk
+        k.xcd_chunk = conv_xcd_chunk(n);   // within the chunk
         return dim3((unsigned)n);
     };
 #define CB_LAUNCH(KERNEL, THREADS, SMEM, ...)                                                    \
@@ -1426,58 +1306,40 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
             ccvs_set_error("ccvs_conv2d_bf16x3: packed input with a %dx%d halo tile / %d taps per row is not supported", halo_h, halo_w, ntx_max);
             return CCVS_ERR_ARG;
         }
-        if constexpr (MB != 4) {   // (128 output channels per workgroup: the written-out form spills; no layer of the models needs it)
-            static bool attr_p = false;
-            if (!attr_p) {
-                CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -83>), 159 * 1024);
-                attr_p = true;
-            }
-        }
         if constexpr (TW == 32 && MB == 2) {   // 64 output channels: the 512-pixel tile (see below), packed input
-            static const int pp4p = (getenv("CCVS_CONV_PP4") ? atoi(getenv("CCVS_CONV_PP4")) : 1) && !(getenv("CCVS_CONV_P8_WPC2") && atoi(getenv("CCVS_CONV_P8_WPC2")));
             const int th4 = 16, halo_h4 = (th4 - 1) + k.kh, plane4 = halo_h4 * halo_w;
             const size_t smem_4 = (size_t)(2 * 4 * plane4 + 2 * ntx_max * 4 * NT) * 16;
-            if (pp4p && k.out_p8 && k.kh == 3 && k.kw == 3 && k.pad == 1 && k.cu_limit <= 0 && k.Hout >= 2 * th4 && 4 * plane4 <= 10 * 256 && smem_4 <= 156 * 1024 &&
+            if (k.out_p8 && k.kh == 3 && k.kw == 3 && k.pad == 1 && k.cu_limit <= 0 && k.Hout >= 2 * th4 && 4 * plane4 <= 10 * 256 && smem_4 <= 156 * 1024 &&
                 smem_4 >= (size_t)32 * 512 * 4) {
                 k.tiles_y = cdiv(k.Hout, th4);
                 const dim3 grid4(k.tiles_x * k.tiles_y, k.CoutPad / NT, gz);
                 const long total4 = (long)grid4.x * grid4.y * grid4.z;
                 k.nwork = 0; k.work0 = 0; k.gx = (int)grid4.x; k.gy = (int)grid4.y;
-                k.xcd_chunk = (xcd_aware_p8() && total4 % 8 == 0 && total4 >= 64) ? (int)(total4 / 8) : 0;
+                k.xcd_chunk = conv_xcd_chunk(total4);
                 static bool attr4p = false;
                 if (!attr4p) {
                     CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), 159 * 1024);
                     attr4p = true;
                 }
-                hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), grid4, dim3(512), (smem_4 > p8s4 ? smem_4 : p8s4), st, k, (const uint4*)wsplit, CinG, ntx_max, ablate);
+                hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), grid4, dim3(512), (smem_4 > p8s4 ? smem_4 : p8s4), st, k, (const uint4*)wsplit, CinG, ntx_max);
                 CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
                 return CCVS_OK;
             }
         }
-        bool done3 = false;
-        if constexpr (TW == 32 && MB == 2) {
-            // two workgroups per CU on packed input (experiment, CCVS_CONV_P8_WPC2): staging is LDS-DMA only, so a second resident
-            // workgroup costs no conversion work -- one tile's prologue / epilogue beside the other's step loop
-            static const int p8w2 = getenv("CCVS_CONV_P8_WPC2") ? atoi(getenv("CCVS_CONV_P8_WPC2")) : 0;
-            const size_t smem_2 = smem_p > p8s2 ? smem_p : p8s2;
-            if (p8w2 && k.kh == 3 && k.kw == 3 && k.pad == 1 && smem_2 <= 79 * 1024 && k.cu_limit <= 0) {
-                static bool attr2p = false;
-                if (!attr2p) {
-                    CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -83, 2, 2>), 159 * 1024);
-                    attr2p = true;
-                }
-                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -83, 2, 2>), 512, smem_2, (const uint4*)wsplit, CinG, ntx_max, ablate);
-                CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-                return CCVS_OK;
-            }
-        }
-        if constexpr (MB != 4) {
+        const size_t smem_p2 = smem_p > p8s2 ? smem_p : p8s2;
+        if constexpr (MB != 4) {   // (128 output channels per workgroup: the written-out form spills; no layer of the models needs it)
             if (k.kh == 3 && k.kw == 3 && k.pad == 1) {
-                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -83>), 512, (smem_p > p8s2 ? smem_p : p8s2), (const uint4*)wsplit, CinG, ntx_max, ablate);
-                done3 = true;
+                static bool attr_p = false;
+                if (!attr_p) {
+                    CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -83>), 159 * 1024);
+                    attr_p = true;
+                }
+                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -83>), 512, smem_p2, (const uint4*)wsplit, CinG, ntx_max);
+                CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
+                return CCVS_OK;
             }
         }
-        if (!done3) CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -8>), 512, (smem_p > p8s2 ? smem_p : p8s2), (const uint4*)wsplit, CinG, ntx_max, ablate);
+        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -8>), 512, smem_p2, (const uint4*)wsplit, CinG, ntx_max);
         CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
         return CCVS_OK;
     }
@@ -1485,27 +1347,25 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
     const int xsh = ((-k.pad % 4) + 4) % 4, nq = (xsh + halo_w + 3) / 4;
     const bool vec_ok = !k.transposed && k.stride == 1 && k.Win % 4 == 0 && k.in_sC % 4 == 0 && k.in_sN % 4 == 0 &&
                         (reinterpret_cast<uintptr_t>(k.x) & 15) == 0 && TW >= 16 && halo_h * ((nq + 1) / 2) * 4 <= 256 && ntx_max <= (MB == 1 ? 9 : 3) &&
-                        (k.kh == 1 || (k.kh == 3 && k.kw == 3 && k.pad == 1)) && !(ablate & 4);   // (3 x 3: the GEO3 instantiations assume padding 1)
+                        (k.kh == 1 || (k.kh == 3 && k.kw == 3 && k.pad == 1));   // (3 x 3: the GEO3 instantiations assume padding 1)
     // packed K tail (ccvs_conv_desc.w_ktail): read by the vectorised 3 x 3 instantiations only
-    static const int ktail_on = getenv("CCVS_CONV_KTAIL") ? atoi(getenv("CCVS_CONV_KTAIL")) : 1;
     const int ktail_r = k.Cin % CB_CC;
-    const bool kt = ktail_on && wktail && vec_ok && k.kh == 3 && k.kw == 3 && ktail_r >= 1 && ktail_r <= 3 && k.Cin > CB_CC;
+    const bool kt = wktail && vec_ok && k.kh == 3 && k.kw == 3 && ktail_r >= 1 && ktail_r <= 3 && k.Cin > CB_CC;
     if constexpr (TW == 32 && MB == 2) {
         // the 512-pixel tile (PP = 4, 16 x 32): 64 output channels, VEC staging, at least two tile rows of work.  Measured per
         // shape on a BAIR decode (tools/conv_shape_census.py): 128->64 3x3 at 256^2 253 -> 282 TFLOP/s; the 32-channel layers
         // (MB = 1: four workgroups per CU hide each other's latency with the 256-pixel tile, one with this one) LOSE -- 64->32
         // 204 -> 156, the 1 x 9 heads 159 -> 120 -- and stay on the 256-pixel tile.
-        static const int pp4 = getenv("CCVS_CONV_PP4") ? atoi(getenv("CCVS_CONV_PP4")) : 1;
         const int th4 = 16, halo_h4 = (th4 - 1) + k.kh;
         const size_t smem_4 = (size_t)(2 * 4 * halo_h4 * (nq * 4 + 1) + 2 * ntx_max * 4 * NT) * 16;
-        if (pp4 && !wpc2 && vec_ok && !k.out_p8 && k.Hout >= 2 * th4 && halo_h4 * ((nq + 1) / 2) * 4 <= 512 && smem_4 <= 156 * 1024 && smem_4 >= (size_t)32 * 512 * 4) {
+        if (!wpc2 && vec_ok && !k.out_p8 && k.Hout >= 2 * th4 && halo_h4 * ((nq + 1) / 2) * 4 <= 512 && smem_4 <= 156 * 1024 && smem_4 >= (size_t)32 * 512 * 4) {
             k.tiles_y = cdiv(k.Hout, th4);
             const dim3 grid4(k.tiles_x * k.tiles_y, k.CoutPad / NT, gz);
             const long total4 = (long)grid4.x * grid4.y * grid4.z;
             // (one launch over the whole chip; with a CU budget the 256-pixel form below runs in chunks)
             if (k.cu_limit <= 0) {
                 k.nwork = 0; k.work0 = 0; k.gx = (int)grid4.x; k.gy = (int)grid4.y;
-                k.xcd_chunk = (xcd_aware && total4 % 8 == 0 && total4 >= 64) ? (int)(total4 / 8) : 0;
+                k.xcd_chunk = conv_xcd_chunk(total4);
                 static bool attr4 = false;
                 if (!attr4) {
                     CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), 159 * 1024);   // (+ the static bias block)
@@ -1513,8 +1373,8 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
                     attr4 = true;
                 }
                 k.ktail = kt ? ktail_r : 0;
-                if (k.kh == 3) hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, 3, 4>), grid4, dim3(512), smem_4, st, k, (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max, ablate);
-                else hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), grid4, dim3(512), smem_4, st, k, (const uint4*)wsplit, CinG, ntx_max, ablate);
+                if (k.kh == 3) hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, 3, 4>), grid4, dim3(512), smem_4, st, k, (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
+                else hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), grid4, dim3(512), smem_4, st, k, (const uint4*)wsplit, CinG, ntx_max);
                 CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
                 return CCVS_OK;
             }
@@ -1531,7 +1391,7 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
                     attr2 = true;
                 }
                 k.ktail = kt ? ktail_r : 0;
-                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 3, 2, 2>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max, ablate);
+                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 3, 2, 2>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
                 k.ktail = 0;
                 CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
                 return CCVS_OK;
@@ -1540,28 +1400,27 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         if (smem_v <= 156 * 1024) {
             if (k.kh == 3) {
                 k.ktail = kt ? ktail_r : 0;
-                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 3>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max, ablate);
+                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 3>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
                 k.ktail = 0;
-            } else CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 1>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)wsplit, CinG, ntx_max, ablate);
+            } else CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 1>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)wsplit, CinG, ntx_max);
             CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
             return CCVS_OK;
         }
     }
+    // Scalar staging: the producer / consumer form with the halo tile in one (NTY 0) or two (NTY -2) pixel passes per tap row.
+    // Never for transposed layers (1-2 taps per row and parity class: little MFMA work per staged tile): they are faster on the
+    // 8-wave synchronous kernel than on the two-pass producer / consumer form, 117 vs 77 TFLOP/s on 128->128 at 128^2.
     const size_t smem_pc = (size_t)(2 * 4 * plane + 2 * ntx_max * 4 * NT) * 16;
-    const int nt_min = (k.transposed ? 1 : k.kh);               // fewest tap rows of any parity class
     const int passes = (plane + 255) / 256;
-    const bool regs_ok = (ntx_max <= (MB == 1 ? 9 : 3)) && (passes <= nt_min);
-    // transposed layers (1-2 taps per row and parity class: little MFMA work per staged tile) are faster on the 8-wave synchronous
-    // kernel than on the two-pass producer / consumer form: 117 vs 77 TFLOP/s on 128->128 at 128^2 (CCVS_CONV_ABLATE=1024 keeps the old routing)
-    const bool regs_ok2 = (ntx_max <= (MB == 1 ? 9 : 3)) && (passes <= 2 * nt_min) && !(ablate & 32) && (!k.transposed || (ablate & 1024));
+    const bool pc_ok = !k.transposed && smem_pc <= 156 * 1024 && ntx_max <= (MB == 1 ? 9 : 3);
     // (8 staging waves for <= 64 output channels were measured slower: the steps are latency- not staging-bound)
-    if (smem_pc <= 156 * 1024 && regs_ok) {  // double-buffered producer / consumer form, scalar staging
-        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 0>), 512, (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max, ablate);
+    if (pc_ok && passes <= k.kh) {  // double-buffered producer / consumer form, scalar staging
+        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 0>), 512, (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
         CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
         return CCVS_OK;
     }
-    if (smem_pc <= 156 * 1024 && regs_ok2) {
-        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -2>), 512, (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max, ablate);
+    if (pc_ok && passes <= 2 * k.kh) {
+        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -2>), 512, (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
         CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
         return CCVS_OK;
     }
@@ -1574,10 +1433,7 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         ccvs_set_error("ccvs_conv2d_bf16x3: %zu bytes of LDS needed", smem);
         return CCVS_ERR_ARG;
     }
-    static const int sync_waves = getenv("CCVS_CONV_SYNC_WAVES") ? atoi(getenv("CCVS_CONV_SYNC_WAVES")) : 8;
-    if (sync_waves == 8) CB_LAUNCH((conv2d_bf16x3_kernel<TW, MB, 8>), 512, smem, (const uint4*)wsplit, CinG);
-    else CB_LAUNCH((conv2d_bf16x3_kernel<TW, MB, 4>), 256, smem, (const uint4*)wsplit, CinG);
+    CB_LAUNCH((conv2d_bf16x3_kernel<TW, MB, 8>), 512, smem, (const uint4*)wsplit, CinG);
     CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
     return CCVS_OK;
 }
-

@@ -38,18 +38,10 @@ __device__ __forceinline__ void pt_tile_coords(const ConvK& p, int w_, int& bx, 
     }
 }
 
-#ifndef PT_DMA_MID
-#define PT_DMA_MID 1   // the weight DMA of the next step between the first and the second tap (0: in front of the step)
-#endif
-#ifndef PT_NUM_VGPR
-#define PT_VGPR_ATTR
-#else
-#define PT_VGPR_ATTR __attribute__((amdgpu_num_vgpr(PT_NUM_VGPR)))
-#endif
 // MB: 32-channel blocks per workgroup; PP: 32-pixel blocks per MFMA wave (2: 8 x 32 pixels, 4: 16 x 32); P8IN: packed split-bf16
 // input (LDS-DMA staging) instead of fp32 rows (aligned dwordx4 + conversion)
 template <int MB, int PP, bool P8IN>
-__global__ __launch_bounds__(512, 2) PT_VGPR_ATTR void conv2d_bf16x3_pt_kernel(ConvK p, const uint4* __restrict__ wsplit, int CinG, int total) {
+__global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const uint4* __restrict__ wsplit, int CinG, int total) {
     constexpr int TW = 32, NPIX = 128 * PP, TH = NPIX / TW, NT = 32 * MB;
     constexpr int IH = TH + 2, IW = TW + 2;
     constexpr int XSH = P8IN ? 0 : 3, NQ = 10;                 // fp32 rows: the LDS image starts 3 pixels left of the halo (a 4-pixel boundary), 10 float4 columns
@@ -440,9 +432,8 @@ __global__ __launch_bounds__(512, 2) PT_VGPR_ATTR void conv2d_bf16x3_pt_kernel(C
                 if (a1 == 3) { a1 = 0; ++c1; }
                 if (s + 1 >= nsteps) { a1 = 0; c1 = 0; n0w = has_next ? n0n : n0; }
                 uint4* const wdst = w_buf + (wp ^ 1) * w_sz;
-                if (!PT_DMA_MID) dma_w(n0w, c1, a1, wdst);
 #define PT_MID_DMA()                                      \
-    if (PT_DMA_MID) {                                     \
+    {                                                     \
         __builtin_amdgcn_sched_barrier(0);                \
         dma_w(n0w, c1, a1, wdst);                         \
         __builtin_amdgcn_sched_barrier(0);                \
@@ -655,7 +646,6 @@ static int conv_pt_cus() {
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
         if (n_cu <= 0) n_cu = 256;
-        if (getenv("CCVS_CONV_PT_CUS") && atoi(getenv("CCVS_CONV_PT_CUS")) > 0) n_cu = atoi(getenv("CCVS_CONV_PT_CUS"));   // experiment: resident workgroups on fewer CUs than the chip has
         n_cu -= n_cu % 8;   // whole rounds over the XCDs: workgroup g and its tiles g + gridDim i stay on one XCD's eighth of the tile order
         if (n_cu < 8) n_cu = 8;
     }
@@ -679,8 +669,7 @@ static int launch_conv_pt(ConvK k, const void* w, int CinG, int gz, hipStream_t 
     k.gy = k.CoutPad / NT;
     const long total = (long)k.gx * k.gy * gz;
     k.nwork = (int)total; k.work0 = 0;
-    static const int xcd_aware = getenv("CCVS_CONV_XCD") ? atoi(getenv("CCVS_CONV_XCD")) : 1;
-    k.xcd_chunk = (xcd_aware && total % 8 == 0 && total >= 64) ? (int)(total / 8) : 0;
+    k.xcd_chunk = conv_xcd_chunk(total);
     const int cus = conv_pt_cus();
     const unsigned grid = (unsigned)(total < cus ? total : cus);
     hipLaunchKernelGGL((conv2d_bf16x3_pt_kernel<MB, PP, P8IN>), dim3(grid), dim3(512), smem, st, k, (const uint4*)w, CinG, (int)total);
@@ -709,9 +698,8 @@ static int conv_pt_try(const ConvK& k_in, const void* wsplit, const void* wktail
     if constexpr (MB == 4) {
         if (!(pt_on & 1)) return CONV_PT_NOT_TAKEN;
         if (conv_pt_ok<4>(k, 2, true) && (long)(k.Wout / 32) * (k.Hout / 8) * (k.CoutPad / 128) * gz >= 2L * cus) {
-            static const int ktail_on = getenv("CCVS_CONV_KTAIL") ? atoi(getenv("CCVS_CONV_KTAIL")) : 1;
             const int ktail_r = k.Cin % CB_CC;
-            const bool kt = ktail_on && wktail && ktail_r >= 1 && ktail_r <= 3 && k.Cin > CB_CC;
+            const bool kt = wktail && ktail_r >= 1 && ktail_r <= 3 && k.Cin > CB_CC;
             k.ktail = kt ? ktail_r : 0;
             return launch_conv_pt<4, 2, false>(k, kt ? wktail : wsplit, CinG, gz, st);
         }
