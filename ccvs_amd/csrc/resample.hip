@@ -170,6 +170,28 @@ __global__ __launch_bounds__(256) void upsample2_kernel(FirK p) {
     }
 }
 
+// The two-pixel form's index math as device functions (also ToRGB's skip up-sampling below).  up2_hpass3x4 reads the 3 x 4
+// neighbourhood (rows iy - 1 .. iy + 1, columns jx - 1 .. jx + 2) of an H x W plane, zeros outside, and runs the horizontal pass:
+// hr[a][b] is column 2 jx + b of the zero-inserted row iy + a - 1.  up2_vpass is output row 2 iy + a (a = 0, 1) before the gain.
+__device__ __forceinline__ void up2_hpass3x4(const float* xp, int H, int W, int iy, int jx, float hr[3][4]) {
+    float v[3][4];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int yy = iy + a - 1, xx = jx + b - 1;
+            const float tv = xp[(long)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)];
+            v[a][b] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? tv : 0.f;
+        }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) { hr[a][2 * b] = v[a][b] + 3.f * v[a][b + 1]; hr[a][2 * b + 1] = 3.f * v[a][b + 1] + v[a][b + 2]; }
+}
+__device__ __forceinline__ float up2_vpass(const float hr[3][4], int a, int b) {
+    return a == 0 ? hr[0][b] + 3.f * hr[1][b] : 3.f * hr[1][b] + hr[2][b];
+}
+
 // The same for TWO input pixels (jx, jx + 1) per thread (W even): the 3 x 4 neighbourhood gives a 2 x 4 output block, written
 // as two 16-byte stores.  Per output the arithmetic is that of upsample2_kernel.
 __global__ __launch_bounds__(256) void upsample2x2_kernel(FirK p) {
@@ -181,20 +203,8 @@ __global__ __launch_bounds__(256) void upsample2x2_kernel(FirK p) {
         const int iy = (int)(t % p.H);
         const long nc = t / p.H;
         const float* xp = p.x + nc * (long)p.H * p.W;
-        float v[3][4];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int yy = iy + a - 1, xx = jx + b - 1;
-                const float tv = xp[(long)min(max(yy, 0), p.H - 1) * p.W + min(max(xx, 0), p.W - 1)];
-                v[a][b] = (yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) ? tv : 0.f;
-            }
         float hr[3][4];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 2; ++b) { hr[a][2 * b] = v[a][b] + 3.f * v[a][b + 1]; hr[a][2 * b + 1] = 3.f * v[a][b + 1] + v[a][b + 2]; }
+        up2_hpass3x4(xp, p.H, p.W, iy, jx, hr);
         const float g = p.gain * (1.f / 64.f);
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
@@ -202,7 +212,7 @@ __global__ __launch_bounds__(256) void upsample2x2_kernel(FirK p) {
             F32Quad o4;
 #pragma unroll
             for (int b = 0; b < 4; ++b) {
-                float r = (a == 0 ? hr[0][b] + 3.f * hr[1][b] : 3.f * hr[1][b] + hr[2][b]) * g;
+                float r = up2_vpass(hr, a, b) * g;
                 if (p.act == CCVS_ACT_LRELU) r = lrelu01(r);
                 o4.v[b] = r;
             }
@@ -574,5 +584,161 @@ extern "C" int ccvs_dwconvT4x4s2(const float* x, int64_t x_sN, const float* w, f
         hipLaunchKernelGGL(dwconvT4x4s2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (long)x_sN, w, y, (long)y_sN, (long)N, C, H, W);
     }
     CCVS_CHECK_LAUNCH("ccvs_dwconvT4x4s2");
+    return CCVS_OK;
+}
+
+// ToRGB of the decoder's skip_rgb head (skip_autoencoder.py:288-306):
+//   y[n, c] = ((sum_k w[c, k] x[n, k] + b_conv[c]) + bias[c]) + up2(skip)[n, c],   c = 0 .. 2,
+// w = EqualConv2d's weight * scale (scaled on the host), up2 = Upsample([1,3,3,1]) = upfirdn2d(skip, outer/64 * 4, up 2, pad (2, 1)).
+// HBM-bound (0.75 FLOP per byte): a lane owns four consecutive pixels of a row and reads them as one 16-byte load per channel plane.
+// A 256-thread workgroup owns 256 / G quads; the G thread groups split the channels into G consecutive ranges and sum them in group
+// order through LDS.  G grows as the launch shrinks (4, 16, 64: `to_rgb_form`), so that the coarse levels -- a few hundred quads at 8 x 8 --
+// still spread their channel loops over many workgroups and keep many loads in flight.
+// The [C] x (w0, w1, w2, 0) weights sit in LDS, read as one 16-byte broadcast per channel.
+struct ToRgbK {
+    const float* x;
+    const float* w;       // [3, C]
+    const float* b_conv;  // [3]
+    const float* bias;    // [3]
+    const float* skip;    // [N, 3, H / 2, W / 2] or NULL
+    float* y;             // [N, 3, H, W]
+    long x_sN, quads;     // quads = N * H * Wq
+    int C, H, W, Wq;
+};
+
+template <int G>
+__global__ __launch_bounds__(256) void to_rgb_kernel(ToRgbK p) {
+    constexpr int Q = 256 / G;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    f32x4* wl = reinterpret_cast<f32x4*>(smem);   // [C]
+    float* red = smem + 4 * p.C;                  // [12][256]: partial sums of groups 1 .. G-1
+    const int tid = threadIdx.x, g = tid / Q, j = tid - g * Q;
+    for (int c = tid; c < p.C; c += 256) wl[c] = f32x4{p.w[c], p.w[p.C + c], p.w[2 * p.C + c], 0.f};
+    const int c0 = (g * p.C) / G, c1 = ((g + 1) * p.C) / G;
+    const long plane = (long)p.H * p.W;
+    const long nblocks = (p.quads + Q - 1) / Q;
+    for (long blk = blockIdx.x; blk < nblocks; blk += gridDim.x) {
+        __syncthreads();   // the weights are staged / the previous block's partials have been read
+        const long r = blk * Q + j;
+        const bool live = r < p.quads;
+        int n = 0, oy = 0, ox0 = 0, nv = 0;
+        if (live) {
+            const long img = (long)p.H * p.Wq;
+            n = (int)(r / img);
+            const int rem = (int)(r - (long)n * img);
+            oy = rem / p.Wq;
+            ox0 = (rem - oy * p.Wq) * 4;
+            nv = min(4, p.W - ox0);
+        }
+        float acc[3][4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int o = 0; o < 4; ++o) acc[c][o] = 0.f;
+        if (live) {
+            const float* xp = p.x + n * p.x_sN + (long)oy * p.W + ox0;
+            if (nv == 4) {
+#pragma unroll 8
+                for (int k = c0; k < c1; ++k) {
+                    const F32Quad v = *reinterpret_cast<const F32Quad*>(xp + k * plane);
+                    const f32x4 wk = wl[k];
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) {
+                        acc[0][o] = fmaf(wk[0], v.v[o], acc[0][o]);
+                        acc[1][o] = fmaf(wk[1], v.v[o], acc[1][o]);
+                        acc[2][o] = fmaf(wk[2], v.v[o], acc[2][o]);
+                    }
+                }
+            } else {   // row tail (W % 4 != 0): nv < 4 columns left; compile-time indices, predicated (no private memory)
+                for (int k = c0; k < c1; ++k) {
+                    const f32x4 wk = wl[k];
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) {
+                        if (o < nv) {
+                            const float v = xp[k * plane + o];
+                            acc[0][o] = fmaf(wk[0], v, acc[0][o]);
+                            acc[1][o] = fmaf(wk[1], v, acc[1][o]);
+                            acc[2][o] = fmaf(wk[2], v, acc[2][o]);
+                        }
+                    }
+                }
+            }
+        }
+        if (G > 1) {
+            if (g > 0) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) red[(c * 4 + o) * 256 + tid] = acc[c][o];
+            }
+            __syncthreads();
+        }
+        if (g == 0 && live) {
+#pragma unroll 1
+            for (int gg = 1; gg < G; ++gg)
+#pragma unroll
+                for (int c = 0; c < 3; ++c)
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) acc[c][o] += red[(c * 4 + o) * 256 + gg * Q + j];
+            float up[3][4];
+            if (p.skip) {
+                const int Hs = p.H >> 1, Ws = p.W >> 1, a = oy & 1;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float hr[3][4];
+                    up2_hpass3x4(p.skip + ((long)n * 3 + c) * Hs * Ws, Hs, Ws, oy >> 1, ox0 >> 1, hr);
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) up[c][o] = up2_vpass(hr, a, o) * (4.f * (1.f / 64.f));
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float bc = p.b_conv[c], bb = p.bias[c];
+                float* yp = p.y + ((long)n * 3 + c) * plane + (long)oy * p.W + ox0;
+                F32Quad o4;
+#pragma unroll
+                for (int o = 0; o < 4; ++o) {
+                    const float v = (acc[c][o] + bc) + bb;
+                    o4.v[o] = p.skip ? v + up[c][o] : v;
+                }
+                if (nv == 4) {
+                    *reinterpret_cast<F32Quad*>(yp) = o4;
+                } else {
+#pragma unroll
+                    for (int o = 0; o < 4; ++o)
+                        if (o < nv) yp[o] = o4.v[o];
+                }
+            }
+        }
+    }
+}
+
+// Channel groups per quad of a launch of `quads` quads: 4 (one wave per channel range, 64 quads per workgroup) from 1024 such workgroups up,
+// 16 from 256 workgroups of 16 quads up, 64 (4 quads per workgroup) below.
+static inline int to_rgb_form(long quads) {
+    if (cdiv64(quads, 64) >= 1024) return 4;
+    if (cdiv64(quads, 16) >= 256) return 16;
+    return 64;
+}
+
+extern "C" int ccvs_to_rgb(const float* x, int64_t x_sN, const float* w, const float* b_conv, const float* bias, const float* skip,
+                           float* y, int32_t N, int32_t C, int32_t H, int32_t W, void* stream) {
+    CCVS_REQUIRE(x && w && b_conv && bias && y, "ccvs_to_rgb: null pointer");
+    CCVS_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "ccvs_to_rgb: empty tensor");
+    CCVS_REQUIRE(C <= 2048, "ccvs_to_rgb: C = %d (at most 2048)", C);
+    CCVS_REQUIRE(x_sN >= (int64_t)C * H * W, "ccvs_to_rgb: batch stride %lld below C H W", (long long)x_sN);
+    CCVS_REQUIRE(!skip || (H % 2 == 0 && W % 2 == 0), "ccvs_to_rgb: a skip input needs an even %d x %d output", H, W);
+    ToRgbK p;
+    p.x = x; p.w = w; p.b_conv = b_conv; p.bias = bias; p.skip = skip; p.y = y;
+    p.x_sN = x_sN; p.C = C; p.H = H; p.W = W; p.Wq = cdiv(W, 4);
+    p.quads = (long)N * H * p.Wq;
+    const size_t lds = (size_t)(4 * C + 12 * 256) * sizeof(float);
+    hipStream_t st = (hipStream_t)stream;
+    switch (to_rgb_form(p.quads)) {
+        case 4: hipLaunchKernelGGL(to_rgb_kernel<4>, dim3(limited_grid(cdiv64(p.quads, 64), stream, 8)), dim3(256), lds, st, p); break;
+        case 16: hipLaunchKernelGGL(to_rgb_kernel<16>, dim3(limited_grid(cdiv64(p.quads, 16), stream, 8)), dim3(256), lds, st, p); break;
+        default: hipLaunchKernelGGL(to_rgb_kernel<64>, dim3(limited_grid(cdiv64(p.quads, 4), stream, 8)), dim3(256), lds, st, p); break;
+    }
+    CCVS_CHECK_LAUNCH("ccvs_to_rgb");
     return CCVS_OK;
 }

@@ -47,6 +47,11 @@ class Generator:
         self.last_cu_limit, self.last_lanes, self.last_chains = 0, 0, 0
         if getattr(self.opt, "layout", False):
             raise NotImplementedError("--layout is not on the MI355X path (SURVEY 8f); --x_state / --x_stft [--keep_state] / --x_cat / --x_deblurring are")
+        q = self.qvid_opt
+        if getattr(q, "skip_rgb", False) and getattr(q, "use_inter", False) and int(self.opt.cond_len) == 0:
+            raise NotImplementedError("--q_skip_rgb with --x_cond_len 0: frame 0 is decoded without context, so its skip_rgb output "
+                                      "stays at the coarsest level's resolution and cannot be stacked with the later frames "
+                                      "(the reference fails there in torch.cat)")
         if getattr(self.opt, "deblurring", False) and self.opt.step_by_step:
             raise NotImplementedError("--step_by_step with --deblurring is not on the MI355X path (the plain synthesis schedule runs the mode)")
 

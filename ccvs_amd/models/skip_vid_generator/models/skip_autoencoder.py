@@ -12,7 +12,10 @@ The flow-decoder variants of Matching (--q_use_masked_flow, --q_use_deformed_con
 --q_no_corr) run on their own kernels (deformable convolution on the matrix cores, grouped x2 transposed
 convolution of the trade-off feature, masked-flow / trade-off epilogue).
 
-Not supported (outside the hot path): layout decoders, skip_rgb / ToRGB, training.
+The StyleGAN2-style output head of --q_skip_rgb (a ToRGB per decoder level, each level's RGB up-sampled into the next) runs one
+`ops.to_rgb` launch per level.
+
+Not supported (outside the hot path): layout decoders, training.
 """
 import math
 
@@ -432,6 +435,47 @@ class InterBlock(nn.Module):
         return out, fo[:, :2], fo[:, 2:3], toff
 
 
+class Upsample(nn.Module):
+    """skip_autoencoder.py:268-285: upfirdn2d(x, make_kernel([1,3,3,1]) * 4, up=2, pad=(2, 1)).  Holds the `kernel` buffer for
+    state-dict parity; ToRGB runs it inside `ops.to_rgb`, `forward` is the standalone form."""
+
+    def __init__(self, kernel, factor=2):
+        super().__init__()
+        if list(kernel) != [1, 3, 3, 1] or factor != 2:
+            raise NotImplementedError("Upsample (HIP): only the x2 [1,3,3,1] form of ToRGB")
+        self.factor = factor
+        kernel = make_kernel(kernel) * (factor ** 2)
+        self.register_buffer("kernel", kernel)
+        p = kernel.shape[0] - factor
+        self.pad = ((p + 1) // 2 + factor - 1, p // 2)
+
+    def forward(self, input):
+        return ops.upfirdn2d(input, up=self.factor, pad=self.pad, gain=float(self.factor ** 2))
+
+
+class ToRGB(nn.Module):
+    """skip_autoencoder.py:288-306: ((1x1 conv to 3 channels + its bias) + bias) + Upsample(skip), one `ops.to_rgb` launch.  The
+    parameters are built in the reference's order; `packed()` caches the conv weight times EqualConv2d's scale as [3, C]."""
+
+    def __init__(self, in_channel, upsample=True, blur_kernel=[1, 3, 3, 1]):
+        super().__init__()
+        if upsample:
+            self.upsample = Upsample(blur_kernel)
+        self.conv = ConvLayer(in_channel, 3, 1, activate=False)
+        self.bias = nn.Parameter(torch.zeros(1, 3, 1, 1))
+        self._packed = None
+
+    def packed(self):
+        w = self.conv.conv.weight
+        key = (w.data_ptr(), w._version, w.device)
+        if self._packed is None or self._packed[0] != key:
+            self._packed = (key, (w.detach() * self.conv.conv.scale).reshape(3, -1).contiguous())
+        return self._packed[1]
+
+    def forward(self, input, skip=None):
+        return ops.to_rgb(input, self.packed(), self.conv.conv.bias.detach(), self.bias.detach(), skip=skip)
+
+
 class SkipGANEncoder(nn.Module):
     """skip_autoencoder.py:309-351."""
 
@@ -471,25 +515,32 @@ class SkipGANEncoder(nn.Module):
 
 
 class SkipGANDecoder(nn.Module):
-    """skip_autoencoder.py:354-476 (mode rgb, no skip_rgb)."""
+    """skip_autoencoder.py:354-476 (mode rgb, with or without skip_rgb)."""
 
     def __init__(self, opt, blur_kernel=[1, 3, 3, 1], mode="rgb"):
         super().__init__()
-        if mode != "rgb" or getattr(opt, "skip_rgb", False):
-            raise NotImplementedError("SkipGANDecoder (HIP): rgb mode without skip_rgb only")
+        if mode != "rgb":
+            raise NotImplementedError("SkipGANDecoder (HIP): rgb mode only (layout decoders are outside the path)")
         necf_mult, necf = opt.necf_mult, opt.necf   # (sic) the reference reads necf, not ndcf: skip_autoencoder.py:357-358
         self.num_resolutions = len(necf_mult)
         self.use_inter, self.z_size, self.skip_tanh, self.mode = opt.use_inter, opt.z_size, getattr(opt, "skip_tanh", False), mode
+        self.skip_rgb = bool(getattr(opt, "skip_rgb", False))
         block_in = necf * necf_mult[-1]
         blocks = [ConvLayer(opt.z_size, block_in, 1)]
+        to_rgb = [ToRGB(block_in, upsample=False)] if self.skip_rgb else None
         inter_sizes = [int(opt.inter_p * block_in)]
         block_out = block_in
         for i in range(1, self.num_resolutions):
             block_out = necf * necf_mult[-1 - i]
             blocks.append(ResBlock(block_in, block_out, blur_kernel, upsample=True))
+            if self.skip_rgb:
+                to_rgb.append(ToRGB(block_out))
             inter_sizes.append(int(opt.inter_p * block_out))
             block_in = block_out
-        blocks.append(ConvLayer(block_out, 3, 1, activate=False))
+        if self.skip_rgb:   # registered ahead of `blocks`, which then has no final 1x1 convolution (skip_autoencoder.py:379-390)
+            self.to_rgb = nn.ModuleList(to_rgb)
+        else:
+            blocks.append(ConvLayer(block_out, 3, 1, activate=False))
         self.blocks = nn.ModuleList(blocks)
         self.last_flow_mult = None
         if self.use_inter:
@@ -521,9 +572,13 @@ class SkipGANDecoder(nn.Module):
             inter_tgts = [[flatten_vid(t)[0] for t in inter_tgt] for inter_tgt in inter_tgts]
         out = self.blocks[0](input)
         inter_flows, inter_occs, inter_dec = [], [], []
-        fo = toff = None
+        fo = toff = rgb = None
         for i in range(self.num_resolutions):
             if i > 0:
+                if self.skip_rgb and not use_inter:
+                    # skip_autoencoder.py:443-458: without the InterBlocks no finer ToRGB runs and the output is level 0's RGB at
+                    # the coarsest resolution; the finer blocks it still runs feed nothing that is returned
+                    break
                 out = self.blocks[i](out)
             if use_inter:
                 s = self.inter_sizes[i]
@@ -535,7 +590,9 @@ class SkipGANDecoder(nn.Module):
                         inter_dec.append(out[:, :s])
                     inter_flows.append(fo[:, :2])
                     inter_occs.append(fo[:, 2:3])
-        out1 = self.blocks[self.num_resolutions](out)
+            if self.skip_rgb:   # to_rgb[0] after level 0 (and its InterBlock), to_rgb[i] only where the InterBlocks run
+                rgb = self.to_rgb[i](out, rgb)
+        out1 = rgb if self.skip_rgb else self.blocks[self.num_resolutions](out)
         if self.skip_tanh:
             out1 = torch.tanh(out1)
         out1 = unflatten_vid(out1, vid_size)

@@ -1,5 +1,6 @@
 """VectorQuantizer with the reference's interface (modules/quantize.py:7-83): inference
-only -- nearest-codebook indices, quantised features, `embed_code`."""
+only -- nearest-codebook indices, quantised features (L2-normalised over the channels with
+`normalize`), `embed_code`."""
 import torch
 import torch.nn as nn
 
@@ -10,8 +11,8 @@ class VectorQuantizer(nn.Module):
     def __init__(self, n_e, e_dim, beta, mult=1, normalize=False):
         super().__init__()
         assert e_dim % mult == 0
-        if mult != 1 or normalize:
-            raise NotImplementedError("VectorQuantizer (HIP): mult > 1 / normalize are outside the hot path")
+        if mult != 1:
+            raise NotImplementedError("VectorQuantizer (HIP): mult > 1 (several codes per position) is outside the hot path")
         self.n_e, self.e_dim, self.beta, self.mult, self.normalize = n_e, e_dim, beta, mult, normalize
         self.embedding = nn.Embedding(n_e, e_dim)
         if e_dim <= 1:
@@ -53,8 +54,10 @@ class VectorQuantizer(nn.Module):
         idx = self.indices(z)
         z4 = self._as_nchw(z)
         hw = z4.shape[2] * z4.shape[3]
-        zq = ops.embed_gather(idx, self.embedding.weight.detach(), z4.shape[0], hw).view(z.shape)
-        return zq, None, (None, None, idx.unsqueeze(1))
+        zq = ops.embed_gather(idx, self.embedding.weight.detach(), z4.shape[0], hw)
+        if self.normalize:   # quantize.py:56-57: z_q / ||z_q||_2 over the channels; embed_code keeps the raw rows (quantize.py:76-83)
+            zq = ops.l2_normalize_channels_(zq.view(z4.shape[0], -1, z4.shape[2], z4.shape[3]))
+        return zq.view(z.shape), None, (None, None, idx.unsqueeze(1))
 
     @torch.no_grad()
     def embed_code(self, code):

@@ -332,6 +332,27 @@ def gaussian_blur(x, k, sigma):
     return out
 
 
+def to_rgb(x, w_scaled, b_conv, bias, skip=None, out=None):
+    """ToRGB.forward(x, skip) of the skip_rgb head (skip_autoencoder.py:298-306), one `ccvs_to_rgb` launch:
+    ((conv1x1(x, w_scaled) + b_conv) + bias) + Upsample(skip).  x [N,C,H,W] (channel planes dense, any batch stride); w_scaled
+    [3,C] = EqualConv2d weight * scale; b_conv [3]; bias [3] or [1,3,1,1]; skip [N,3,H/2,W/2] or None.  Returns [N,3,H,W]."""
+    _need_gpu(x, w_scaled, b_conv, bias, skip, out)
+    assert x.dtype == torch.float32 and x.dim() == 4
+    if not _planes_dense(x):
+        x = x.contiguous()
+    n, c, h, w = x.shape
+    assert w_scaled.shape == (3, c) and w_scaled.is_contiguous() and b_conv.numel() == 3 and bias.numel() == 3
+    if skip is not None:
+        skip = skip.contiguous()
+        assert skip.shape == (n, 3, h // 2, w // 2) and h % 2 == 0 and w % 2 == 0, (tuple(skip.shape), tuple(x.shape))
+    if out is None:
+        out = torch.empty(n, 3, h, w, dtype=torch.float32, device=x.device)
+    assert out.shape == (n, 3, h, w) and out.is_contiguous()
+    _lib.check(_lib.load().ccvs_to_rgb(_p(x), x.stride(0), _p(w_scaled), _p(b_conv.contiguous()), _p(bias.contiguous()), _p(skip),
+                                       _p(out), n, c, h, w, _stream()), "ccvs_to_rgb")
+    return out
+
+
 # ------------------------------------------------------------------ cost volume / warp
 def correlation7x7(first, second, stride, first_div=1, lrelu=False):
     _need_gpu(first, second)

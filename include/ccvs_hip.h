@@ -138,6 +138,14 @@ int ccvs_dwconvT4x4s2(const float* x, int64_t x_sN, const float* w, float* y, in
 int ccvs_gaussian_blur(const float* x, int64_t x_sN, int64_t x_sC, float* y, int32_t N, int32_t C, int32_t H, int32_t W, int32_t k,
                        const float* weights, void* stream);
 
+/* ToRGB of the decoder's skip_rgb head (skip_autoencoder.py:288-306): the 1 x 1 EqualConv2d to 3 channels, its bias, the ToRGB bias,
+ * then the Upsample([1,3,3,1]) of the coarser level's RGB (upfirdn2d(skip, outer([1,3,3,1]) / 64 * 4, up 2, pad (2, 1))):
+ *   y[n, c] = ((sum_k w[c, k] x[n, k] + b_conv[c]) + bias[c]) + up2(skip)[n, c]
+ * x [N,C,H,W] (batch stride x_sN, channel planes dense); w [3,C] = weight * scale (scaled by the caller); b_conv, bias [3]; skip
+ * [N,3,H/2,W/2] dense or NULL (H and W even then); y [N,3,H,W] dense.  C <= 2048. */
+int ccvs_to_rgb(const float* x, int64_t x_sN, const float* w, const float* b_conv, const float* bias, const float* skip, float* y,
+                int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
+
 /* ---- cost volume / warping -----------------------------------------------------------
  * ccvs_correlation7x7 replaces FunctionCorrelation(first, second, stride)
  * (modules/correlation.py:279-338,405-406; kernels :11-100) fused with the

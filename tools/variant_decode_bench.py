@@ -4,7 +4,9 @@ one full-frame decode (`vid_decoder`, random tokens) per variant against the def
 kernel alone at every level's shape: us per launch, algorithmic TFLOP/s and the fraction of the roofline bench.py prices the
 convolutions against (dense bf16 MFMA peak for split-bf16, fp32 MFMA peak for the strict mode).
 
-    python tools/variant_decode_bench.py [--batch 16] [--reps 3] [--out profiles/variant_decode_bench.json]"""
+The `skiprgb` row is the --q_skip_rgb output head (a ToRGB per level) on the default flow decoder.
+
+    python tools/variant_decode_bench.py [--batch 16] [--reps 3] [--variants default skiprgb] [--out profiles/variant_decode_bench.json]"""
 import argparse
 import json
 import os
@@ -27,6 +29,7 @@ VARIANTS = {
     "tradeoff": ["--q_use_tradeoff"],
     "nocorr": ["--q_no_corr"],
     "all": ["--q_use_masked_flow", "--q_use_deformed_conv", "--q_use_tradeoff", "--q_no_corr"],
+    "skiprgb": ["--q_skip_rgb"],
 }
 
 
@@ -94,19 +97,22 @@ def main():
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--variants", nargs="+", default=list(VARIANTS), choices=list(VARIANTS))
     args = ap.parse_args()
     assert torch.cuda.is_available()
     res = {"geometry": "BAIR 256x256 (ccvs_amd.tools.options.BAIR_ARGV), random weights and tokens", "batch": args.batch, "decode_ms": {},
            "deform_alone": []}
     all_shapes = set()
     for name, flags in VARIANTS.items():
+        if name not in args.variants:
+            continue
         t0 = time.time()
         best, times, shapes = decode_ms(flags, args.batch, args.reps)
         all_shapes.update(shapes)
         res["decode_ms"][name] = {"best": best, "all": times}
         print(f"decode {name:9s} {best:9.1f} ms  (runs {', '.join(f'{t:.1f}' for t in times)}; {time.time() - t0:.0f} s wall)", flush=True)
     base = res["decode_ms"]["default"]["best"]
-    for name in VARIANTS:
+    for name in res["decode_ms"]:
         res["decode_ms"][name]["vs_default"] = res["decode_ms"][name]["best"] / base
     largest = {}
     for n, c, h, w in all_shapes:   # one shape per level: the most context pairs
