@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "ccvs_hip.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -65,6 +66,13 @@ static inline unsigned limited_grid(long blocks, void* stream, int per_cu) {
 // ran at 0.6 of what a plain copy reaches on this chip (tools/mem_bench.py).
 struct __attribute__((packed, aligned(4))) F32Pair { float x, y; };
 struct __attribute__((packed, aligned(4))) F32Quad { float v[4]; };
+
+// The library's run-time switches (CCVS_CORR_PAIR, CCVS_WARP_TILED, CCVS_CONV_PT, CCVS_GEMM_SEQ_DENSE, CCVS_GEMM_TILE2: DESIGN.md
+// "Switches") are read here and nowhere else, each once into a function-local static of its launcher.
+static inline int getenv_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

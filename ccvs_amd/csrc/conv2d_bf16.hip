@@ -68,7 +68,7 @@ extern "C" int ccvs_conv2d_bf16x3(const float* x, const void* w_split, const flo
     k.act = d->act; k.accumulate = d->accumulate; k.out_scale = d->out_scale;
     k.pre = d->pre; k.pre_sN = d->pre_sN; k.pre_sC = d->pre_sC; k.pre_div = d->pre_div > 0 ? d->pre_div : 1;
     k.in_p8 = d->in_p8 ? 1 : 0; k.out_p8 = d->out_p8 ? 1 : 0;
-    static const int pt_env = getenv("CCVS_CONV_PT") ? atoi(getenv("CCVS_CONV_PT")) : -1;
+    static const int pt_env = getenv_int("CCVS_CONV_PT", -1);
     k.pt = pt_env >= 0 ? pt_env : __atomic_load_n(&g_conv_pt_mode, __ATOMIC_RELAXED);
     k.ktail = 0; k.nwork = 0; k.gx = k.gy = 1; k.work0 = 0; k.xcd_chunk = 0; k.cu_limit = d->cu_limit > 0 ? d->cu_limit : ccvs_cu_limit_of(stream);
     k.zi = (d->pre && k.pre_div > 1 && !d->transposed && d->N % k.pre_div == 0) ? k.pre_div : 0;

@@ -1,7 +1,6 @@
 // Cost volume, bilinear back-warp and the confidence fusion / occlusion blend of the
 // decoder's InterBlock (reference skip_autoencoder.py:120-128,179-265).  HBM / LDS bound.
 #include "common.h"
-#include <stdlib.h>
 
 // ---------------------------------------------------------------------------------------
 // 7x7 displacement correlation (modules/correlation.py:11-100):
@@ -216,7 +215,7 @@ extern "C" int ccvs_correlation7x7(const float* first, const float* second, floa
     CCVS_REQUIRE(stride == 1 || stride == 2, "ccvs_correlation7x7: stride %d unsupported", stride);
     const int Ho = cdiv(H, stride), Wo = cdiv(W, stride);
     hipStream_t st = (hipStream_t)stream;
-    static const int pair_form = getenv("CCVS_CORR_PAIR") ? atoi(getenv("CCVS_CORR_PAIR")) : 1;
+    static const int pair_form = getenv_int("CCVS_CORR_PAIR", 1);
     if (pair_form && Wo % 2 == 0 && Wo >= 64) {
         const int tiles_x2 = cdiv(Wo, 64), tiles_y2 = cdiv(Ho, 8);
         const GridWalk gw2 = grid_walk((long)tiles_x2 * tiles_y2, N, 1);
@@ -382,7 +381,7 @@ __global__ __launch_bounds__(256) void backwarp_kernel(CtxList ctx, long x_sC,
 // coordinates over the tile, 16-byte row loads, gathers from LDS) was built first and was SLOWER than the plain gathers on the same
 // tiles: 3.0 ms against 1.5 -- two barriers and a dependent load phase per context buy nothing the L1 does not already give.
 static int warp_tiled(int H, int W) {
-    static const int t = getenv("CCVS_WARP_TILED") ? atoi(getenv("CCVS_WARP_TILED")) : 16;   // threads along a tile row; 0: plain
+    static const int t = getenv_int("CCVS_WARP_TILED", 16);   // threads along a tile row; 0: plain
     if (t != 8 && t != 16 && t != 32 && t != 64) return 0;
     return (W % (4 * t) == 0 && H % (256 / t) == 0) ? t : 0;
 }
@@ -796,7 +795,7 @@ __global__ __launch_bounds__(256) void warp_fuse_blend_kernel(float* __restrict_
     GRID_WALK_END
 }
 
-template <int CCH, bool PREF>   // channels per thread; flows of the next context requested one context ahead
+#define FUSE_CCH 8   // channels per thread of the four-pixel form
 __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict__ dec, long dec_sN, long dec_sC, CtxList ctx,
                                                                const float* __restrict__ flows, long flows_sN, const float* __restrict__ occs,
                                                                long occs_sN, float mult, int k, int C, int H, int W, GridWalk gw) {
@@ -804,12 +803,12 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
     GRID_WALK_BEGIN(gw, bx, by, bz)
     const int pix = quad_pixel(gw, bx, W);
     if (pix >= HW) continue;
-    const int n = bz, c0 = by * CCH;
+    const int n = bz, c0 = by * FUSE_CCH;
     const int py = pix / W, px = pix - py * W;
-    const int cn = min(CCH, C - c0);
-    float acc[CCH][4];
+    const int cn = min(FUSE_CCH, C - c0);
+    float acc[FUSE_CCH][4];
 #pragma unroll
-    for (int j = 0; j < CCH; ++j)
+    for (int j = 0; j < FUSE_CCH; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
     float sum_conf[4] = {0.f, 0.f, 0.f, 0.f}, sum_occ[4] = {0.f, 0.f, 0.f, 0.f};
@@ -819,14 +818,8 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
     F32Quad fy_n = *reinterpret_cast<const F32Quad*>(flows + (long)n * k * flows_sN + HW + pix);
     F32Quad oc_n = *reinterpret_cast<const F32Quad*>(occs + (long)n * k * occs_sN + pix);
     for (int kk = 0; kk < k; ++kk) {
-        F32Quad fx = fx_n, fy = fy_n, oc = oc_n;
-        if (!PREF && kk > 0) {
-            const long nk = (long)n * k + kk;
-            fx = *reinterpret_cast<const F32Quad*>(flows + nk * flows_sN + pix);
-            fy = *reinterpret_cast<const F32Quad*>(flows + nk * flows_sN + HW + pix);
-            oc = *reinterpret_cast<const F32Quad*>(occs + nk * occs_sN + pix);
-        }
-        if (PREF && kk + 1 < k) {
+        const F32Quad fx = fx_n, fy = fy_n, oc = oc_n;
+        if (kk + 1 < k) {
             const long nk1 = (long)n * k + kk + 1;
             fx_n = *reinterpret_cast<const F32Quad*>(flows + nk1 * flows_sN + pix);
             fy_n = *reinterpret_cast<const F32Quad*>(flows + nk1 * flows_sN + HW + pix);
@@ -843,7 +836,7 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
         }
         const float* base = ctx.p[kk] + (long)n * ctx.sN[kk] + (long)c0 * HW;
 #pragma unroll
-        for (int j = 0; j < CCH; ++j)
+        for (int j = 0; j < FUSE_CCH; ++j)
             if (j < cn) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) acc[j][i] += conf[i] * bilin_sample_pair(base + (long)j * HW, q[i]);
@@ -853,7 +846,7 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
 #pragma unroll
     for (int i = 0; i < 4; ++i) m[i] = sigmoidf_((k > 1) ? sum_occ[i] / sum_conf[i] : sum_occ[i]);
 #pragma unroll
-    for (int j = 0; j < CCH; ++j) {
+    for (int j = 0; j < FUSE_CCH; ++j) {
         if (j < cn) {
             F32Quad* d = reinterpret_cast<F32Quad*>(dec + (long)n * dec_sN + (long)(c0 + j) * dec_sC + pix);
             F32Quad dv = *d;
@@ -871,16 +864,10 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
 static void launch_warp_fuse_blend(float* dec, long dec_sN, long dec_sC, const CtxList& l, const float* flows, long flows_sN, const float* occs,
                                    long occs_sN, float mult, int N, int k, int C, int H, int W, void* stream) {
     if (W % 4 == 0) {
-        static const int cch = getenv("CCVS_FUSE_CCH") ? atoi(getenv("CCVS_FUSE_CCH")) : 8;
-        static const int pref = getenv("CCVS_FUSE_PREF") ? atoi(getenv("CCVS_FUSE_PREF")) : 1;
-        GridWalk gw = grid_walk(cdiv(H * W / 4, 256), cdiv(C, cch == 4 ? 4 : 8), N);
+        GridWalk gw = grid_walk(cdiv(H * W / 4, 256), cdiv(C, FUSE_CCH), N);
         gw.tiled = warp_tiled(H, W);
-#define WFB_LAUNCH(CCHv, PREFv)                                                                                                         \
-    hipLaunchKernelGGL((warp_fuse_blend4_kernel<CCHv, PREFv>), dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, dec, \
-                       dec_sN, dec_sC, l, flows, flows_sN, occs, occs_sN, mult, k, C, H, W, gw)
-        if (cch == 4) { if (pref) WFB_LAUNCH(4, true); else WFB_LAUNCH(4, false); }
-        else { if (pref) WFB_LAUNCH(8, true); else WFB_LAUNCH(8, false); }
-#undef WFB_LAUNCH
+        hipLaunchKernelGGL(warp_fuse_blend4_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, dec, dec_sN, dec_sC, l,
+                           flows, flows_sN, occs, occs_sN, mult, k, C, H, W, gw);
     } else {
         const GridWalk gw = grid_walk(cdiv(H * W, 256), cdiv(C, WARP_CCH), N);
         hipLaunchKernelGGL(warp_fuse_blend_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, dec, dec_sN, dec_sC, l,

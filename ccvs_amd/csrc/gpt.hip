@@ -3,25 +3,16 @@
 // Reference: models/skip_vid_generator/models/mingpt.py:33-117,186-305 and
 // models/skip_vid_generator/models/transformer_model.py:256-260,395-409.
 #include "common.h"
-#include <stdlib.h>
 
 // ---------------------------------------------------------------------------------------
 // x[(b,t)][:] = tok_emb[idx[b*idx_sB + t]] + pos_table[pos_off[b] + pos0 + t]
 // (mingpt.py:234-236,242-244; the factored s_emb/t_emb (+delta_length) or flat pos_emb rows
 // are pre-summed by the host into pos_table once per call).
 // ---------------------------------------------------------------------------------------
-// -DCCVS_TOKEN_PRIO=n (an experiment, without effect on frames/s: profiles/r05_inrun_trace_anatomy.txt): the kernels of a decode step raise their waves' issue priority --
-// they are few, short and mostly waiting on memory, beside convolution waves that issue MFMAs back to back.
-#ifdef CCVS_TOKEN_PRIO
-#define TOKEN_PRIO() __builtin_amdgcn_s_setprio(CCVS_TOKEN_PRIO)
-#else
-#define TOKEN_PRIO() ((void)0)
-#endif
 __global__ __launch_bounds__(256) void gpt_embed_kernel(const int64_t* __restrict__ idx, long idx_sB, const int32_t* __restrict__ pos_off,
                                                         int pos0, const int32_t* __restrict__ pos_dev, int grp_rows, int Tq,
                                                         const float* __restrict__ tok, const float* __restrict__ pos,
                                                         float* __restrict__ x, long total, int C, int vocab) {
-    TOKEN_PRIO();
     // device-resident position: lets a captured hipGraph replay at advancing positions; with row groups (grp_rows > 0)
     // batch row b reads the word of its group, pos_dev[b / grp_rows]
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
@@ -112,7 +103,7 @@ __device__ __forceinline__ void ln_accum(const f32x4& v, float& sx, float& sxx) 
 
 // 16 bytes at descriptor `r`, per-lane byte offset `voff` + wave-uniform byte offset `soff` (buffer_load_dwordx4 ... offen)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-template <int AUX = 0>   // AUX = 2: non-temporal (streamed once: do not displace what other kernels keep in L2 / the Infinity Cache)
+template <int AUX = 0>   // AUX = 16: sc1 (see below)
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX);
     return __builtin_bit_cast(f32x4, v);
@@ -177,6 +168,8 @@ struct Gemm16 {
 #define GEMM_U 4  // one-block form: K steps (of 16) whose loads are issued together (4 float4 of W + 4 of x per lane: the 48-VGPR budget)
 #define GEMM_U_RB 8  // the same for the prefill form (512 threads, its own CU)
 #define GEMM_WS_TILES 1024  // 16 x 16 output tiles a workspace covers (64 column tiles x 16 row blocks: every split-K launch fits)
+#define GEMM_KZ_MAX 4       // cap of the split-K depth of the decode GEMMs (the workspace holds GEMM_KZ_MAX slabs per tile)
+#define GEMM_KZ_MIN_K 2048  // the shallowest K that is split over workgroups
 #define GEMM_DECODE_MAX_M 256  // up to this many rows the weight-stream kernel below runs; beyond, the prefill form
 
 // LayerNorm statistics -> (mean, rstd) and the epilogue of one output value: single definitions with floating-point
@@ -243,7 +236,7 @@ __device__ __forceinline__ float gemm_epilogue(float v, bool ln, float rstd, flo
 // PT: `Gemm16` (the kernel's own argument block) or `__attribute__((address_space(4))) Gemm16` (an entry of the persistent step's phase
 // table in constant memory: every `p.field` is then a scalar load at its point of use -- the epilogue's operands are not held
 // in registers across the K loop -- and the pointers read from it are generic, hence GP() = the cast through the global address space).
-template <int WNT, int RB, int CB, int U, bool COH, typename PT>   // WNT = 2: weights with the non-temporal policy
+template <int RB, int CB, int U, bool COH, typename PT>
 __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const float* __restrict__ w_, long ldx_, int K_, int N_, int M_, int ks_,
                                             int kz_, const PT& p, int bx_, int by_, int bz_, float* __restrict__ red, float* __restrict__ stat,
                                             float* __restrict__ fin) {
@@ -290,7 +283,7 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-                for (int u = 0; u < U; ++u) wv[cb][u] = buf_load4<WNT>(wr, wofs[cb], k0 * 4 + 64 * u);
+                for (int u = 0; u < U; ++u) wv[cb][u] = buf_load4(wr, wofs[cb], k0 * 4 + 64 * u);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -311,7 +304,7 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
         for (; k0 < kper; k0 += 16) {  // remainder (small K only)
             f32x4 w1[CB], x1[RB];
 #pragma unroll
-            for (int cb = 0; cb < CB; ++cb) w1[cb] = buf_load4<WNT>(wr, wofs[cb], k0 * 4);
+            for (int cb = 0; cb < CB; ++cb) w1[cb] = buf_load4(wr, wofs[cb], k0 * 4);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) x1[rb] = buf_load4<XAUX>(xr, xofs[rb], k0 * 4);
 #pragma unroll
@@ -417,21 +410,13 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
 #undef GP
 }
 
-// -DCCVS_GEMM16_NUM_VGPR=48 (an experiment, tools/r06/run3.sh): hipcc then allocates the one-block form 46 registers and no AGPRs
-// instead of 50 + 4 (56 allocated: it does not fit beside two 232-register convolution waves), the 2 x 2 form 48 + 0 instead of 32 + 16.
-#ifdef CCVS_GEMM16_NUM_VGPR
-#define GEMM16_ATTR __attribute__((amdgpu_num_vgpr(CCVS_GEMM16_NUM_VGPR)))
-#else
-#define GEMM16_ATTR
-#endif
-template <int WNT, int RB, int CB, int U>
-__global__ __launch_bounds__(64 * GEMM_WAVES) GEMM16_ATTR void gemm16_kernel(const float* __restrict__ x_, const float* __restrict__ w_, long ldx_, int K_, int N_,
+template <int RB, int CB, int U>
+__global__ __launch_bounds__(64 * GEMM_WAVES) void gemm16_kernel(const float* __restrict__ x_, const float* __restrict__ w_, long ldx_, int K_, int N_,
                                                                 int M_, int ks_, int kz_, Gemm16 p) {
-    TOKEN_PRIO();
     __shared__ __attribute__((aligned(16))) float red[GEMM16_RED_WORDS(RB * CB)];
     __shared__ float stat[GEMM16_STAT_WORDS(RB)];
     __shared__ float fin[GEMM16_FIN_WORDS(RB)];
-    gemm16_tile<WNT, RB, CB, U, false>(x_, w_, ldx_, K_, N_, M_, ks_, kz_, p, blockIdx.x, blockIdx.y, blockIdx.z, red, stat, fin);
+    gemm16_tile<RB, CB, U, false>(x_, w_, ldx_, K_, N_, M_, ks_, kz_, p, blockIdx.x, blockIdx.y, blockIdx.z, red, stat, fin);
 }
 
 // Prefill form (M > GEMM_DECODE_MAX_M rows): one workgroup computes RB row blocks of 16 against the SAME 16 output columns,
@@ -696,28 +681,20 @@ __global__ __launch_bounds__(256, 4) void gemm_seq_kernel(Gemm16 p, int row_tile
 
 // K slices across workgroups (split-K): spreads GEMMs with few output columns over the chip.  Pays only for deep K:
 // the release/acquire hand-off costs ~3-4 us (measured).
-static int getenv_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
-// K slices across workgroups.  A function of N and K only -- never of M -- so that a row's K partition, hence its rounding,
+// A function of N and K only -- never of M -- so that a row's K partition, hence its rounding,
 // does not depend on how many rows share the launch.
-// Cache policy of the decode step's once-read streams (CCVS_DECODE_NT: bit 0 = keys / values of the attention, bit 1 = weights)
-static int decode_nt() {
-    static const int v = getenv_int("CCVS_DECODE_NT", 1);
-    return v;
-}
-
 static int gemm_kz(const Gemm16& g) {
-    static int kz_max = -1;
-    if (kz_max < 0) { const char* e = getenv("CCVS_GEMM_KZ_MAX"); kz_max = e ? atoi(e) : 4; }
-    static const int kz_min_k = getenv_int("CCVS_GEMM_KZ_MINK", 2048);   // the shallowest K that is split over workgroups
     const int tiles = cdiv(g.N, 16);
     int kz = 1;
     if (g.ws_slabs && !g.ln_s)
-        while (g.K >= kz_min_k && kz < kz_max && tiles * kz * 2 <= 256 && g.K % (16 * GEMM_WAVES * kz * 2) == 0) kz *= 2;
+        while (g.K >= GEMM_KZ_MIN_K && kz < GEMM_KZ_MAX && tiles * kz * 2 <= 256 && g.K % (16 * GEMM_WAVES * kz * 2) == 0) kz *= 2;
     return kz;
+}
+
+// CCVS_GEMM_TILE2=0 (a test hook: tests/gemm_tile_worker.py): one 16 x 16 block per workgroup (rounds 3-4) whatever M is -- same bits
+static bool gemm_tile2() {
+    static const bool v = getenv_int("CCVS_GEMM_TILE2", 1) != 0;
+    return v;
 }
 
 static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
@@ -741,7 +718,7 @@ static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
     if (g.kz > 1 && cdiv(g.N, 16) * cdiv(g.M, 16) > GEMM_WS_TILES) g.kz = 1;   // cannot happen for M <= 256 (kz > 1 needs <= 64 column tiles)
     g.ks = decode_form ? GEMM_WAVES : 8;
     while (g.ks > 1 && g.K % (16 * g.ks * g.kz) != 0) g.ks >>= 1;
-    static const int seq_dense = getenv_int("CCVS_GEMM_SEQ_DENSE", 1);   // 0: the row-blocked weight-stream form of rounds 2-3
+    static const int seq_dense = getenv_int("CCVS_GEMM_SEQ_DENSE", 1);   // 0 (a test hook: tests/gemm_seq_worker.py): the row-blocked weight-stream form of rounds 2-3
     if (!decode_form && g.seq && seq_dense && (long)g.M * g.ldx * 4 < (1L << 31) && (long)g.N * g.K * 4 < (1L << 31)) {   // (buffer descriptors: 32-bit byte offsets)
         const int rt = cdiv(g.M, GS_BM), ct = cdiv(g.N, GS_BM);
         hipLaunchKernelGGL(gemm_seq_kernel, dim3(rt * ct), dim3(256), 0, st, g, rt, ct);
@@ -749,22 +726,20 @@ static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
         hipLaunchKernelGGL((gemm16_rb_kernel<4>), dim3(cdiv(g.N, 16), cdiv(g.M, 64), 1), dim3(512), 0, st, g);
     else {
         // 2 x 2 blocks of 16 x 16 per workgroup once there are two row blocks (stacked batches) -- the blocks' bits do not depend on the tile
-        static const int tile2 = getenv_int("CCVS_GEMM_TILE2", 1);   // 0: one block per workgroup (rounds 3-4)
-        const bool t2 = tile2 && g.M > 32 && g.N >= 32;   // from three row blocks on: with two, N / 32 workgroups are too few alone (2.03 against 1.53 ms per step)
-#define GEMM16_LAUNCH(WNTv, RBv, CBv, Uv)                                                                                                         \
-    hipLaunchKernelGGL((gemm16_kernel<WNTv, RBv, CBv, Uv>), dim3(cdiv(g.N, 16 * CBv), cdiv(g.M, 16 * RBv), g.kz), dim3(64 * GEMM_WAVES), 0, st, g.x, \
+        const bool t2 = gemm_tile2() && g.M > 32 && g.N >= 32;   // from three row blocks on: with two, N / 32 workgroups are too few alone (2.03 against 1.53 ms per step)
+#define GEMM16_LAUNCH(RBv, CBv, Uv)                                                                                                         \
+    hipLaunchKernelGGL((gemm16_kernel<RBv, CBv, Uv>), dim3(cdiv(g.N, 16 * CBv), cdiv(g.M, 16 * RBv), g.kz), dim3(64 * GEMM_WAVES), 0, st, g.x, \
                        g.w, g.ldx, g.K, g.N, g.M, g.ks, g.kz, g)
-        if (decode_nt() & 2) { if (t2) GEMM16_LAUNCH(2, 2, 2, 1); else GEMM16_LAUNCH(2, 1, 1, GEMM_U); }
-        else { if (t2) GEMM16_LAUNCH(0, 2, 2, 1); else GEMM16_LAUNCH(0, 1, 1, GEMM_U); }
+        if (t2) GEMM16_LAUNCH(2, 2, 1); else GEMM16_LAUNCH(1, 1, GEMM_U);
 #undef GEMM16_LAUNCH
     }
     CCVS_CHECK_LAUNCH(name);
     return CCVS_OK;
 }
 
-// Workspace layout: [GEMM_WS_TILES x kz<=4 x 256 floats of split-K slabs][GEMM_WS_TILES arrival counters][StepBar: the grid barrier of
+// Workspace layout: [GEMM_WS_TILES x kz<=GEMM_KZ_MAX x 256 floats of split-K slabs][GEMM_WS_TILES arrival counters][StepBar: the grid barrier of
 // the persistent decode step, below] -- zeroed once by the caller, left consistent by every launch.
-#define GEMM_WS_SLAB_BYTES ((size_t)GEMM_WS_TILES * 4 * 256 * sizeof(float))
+#define GEMM_WS_SLAB_BYTES ((size_t)GEMM_WS_TILES * GEMM_KZ_MAX * 256 * sizeof(float))
 #define GEMM_WS_BAR_OFFSET (GEMM_WS_SLAB_BYTES + (size_t)GEMM_WS_TILES * sizeof(int))   // 4 MB + 4 KB: 128-byte aligned
 #define GEMM_WS_BAR_BYTES 2048
 extern "C" int64_t ccvs_gemm_workspace_bytes(void) { return (int64_t)(GEMM_WS_BAR_OFFSET + GEMM_WS_BAR_BYTES); }
@@ -1013,11 +988,9 @@ __global__ __launch_bounds__(256) void attention_prefill_kernel(const float* __r
     }
 }
 
-// 16 bytes, optionally with the non-temporal policy (a stream read once: keys / values of a decode step)
-template <bool NT>
-__device__ __forceinline__ f32x4 ld_f4(const float* p) {
-    const f32x4* q = reinterpret_cast<const f32x4*>(p);
-    return NT ? __builtin_nontemporal_load(q) : *q;
+// 16 bytes with the non-temporal policy (a stream read once: keys / values of a decode step)
+__device__ __forceinline__ f32x4 ld_f4_nt(const float* p) {
+    return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
 }
 
 // Decode form (Tq = 1): one workgroup per (batch, head) streams that head's K and V rows once.
@@ -1032,7 +1005,7 @@ __device__ __forceinline__ f32x4 ld_f4(const float* p) {
 // (bh = the (batch row, head) pair; smem = 16 + 1024 + Tmax floats.  COH: the persistent decode step -- q, the cache row of the
 //  CURRENT position (written by the QKV phase of the same launch) and the output are handed between workgroups of one launch:
 //  sc1 accesses; the older cache rows were written by earlier launches and stay on the plain / non-temporal stream.)
-template <int D, bool NT, bool COH>
+template <int D, bool COH>
 __device__ __forceinline__ void attention_decode_item(const float* __restrict__ q, long q_sB, const float* __restrict__ kc,
                                                       const float* __restrict__ vc, float* __restrict__ out, int H, int pos0,
                                                       const int32_t* __restrict__ pos_dev, int grp_rows, int Tmax, float scale, int bh,
@@ -1071,7 +1044,7 @@ __device__ __forceinline__ void attention_decode_item(const float* __restrict__ 
     }
 #define ATT_LOAD(dst, base, bi, fresh)                                                                                   \
     _Pragma("unroll") for (int u = 0; u < AU; ++u) {                                                                     \
-        dst[u] = ld_f4<NT>(base + (long)min((bi) * BATCH + jw + u * NW * KPI, L - 1) * D);                                \
+        dst[u] = ld_f4_nt(base + (long)min((bi) * BATCH + jw + u * NW * KPI, L - 1) * D);                                \
         if constexpr (COH) { if ((bi) * BATCH + jw + u * NW * KPI >= L - 1) dst[u] = fresh; }                            \
     }
 
@@ -1146,20 +1119,15 @@ __device__ __forceinline__ void attention_decode_item(const float* __restrict__ 
     }
 }
 
-template <int D, bool NT>
+template <int D>
 __global__ __launch_bounds__(256) void attention_decode_kernel(const float* __restrict__ q, long q_sB, const float* __restrict__ kc,
                                                                const float* __restrict__ vc, float* __restrict__ out, int H, int pos0,
                                                                const int32_t* __restrict__ pos_dev, int grp_rows, int Tmax, float scale) {
-    TOKEN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    attention_decode_item<D, NT, false>(q, q_sB, kc, vc, out, H, pos0, pos_dev, grp_rows, Tmax, scale, blockIdx.x, smem);
+    attention_decode_item<D, false>(q, q_sB, kc, vc, out, H, pos0, pos_dev, grp_rows, Tmax, scale, blockIdx.x, smem);
 }
 
-#define ATT_DECODE_LAUNCH(Dv, grid_, smem_, ...)                                                                       \
-    do {                                                                                                               \
-        if (decode_nt() & 1) hipLaunchKernelGGL((attention_decode_kernel<Dv, true>), grid_, dim3(256), smem_, st, __VA_ARGS__); \
-        else hipLaunchKernelGGL((attention_decode_kernel<Dv, false>), grid_, dim3(256), smem_, st, __VA_ARGS__);     \
-    } while (0)
+#define ATT_DECODE_LAUNCH(Dv, grid_, smem_, ...) hipLaunchKernelGGL((attention_decode_kernel<Dv>), grid_, dim3(256), smem_, st, __VA_ARGS__)
 
 extern "C" int ccvs_attention(const float* q, int64_t q_sB, int64_t ldq, const float* kcache, const float* vcache, float* out, int32_t B,
                               int32_t H, int32_t Tq, int32_t pos0, const int32_t* pos_dev, int32_t Tmax, int32_t D, void* stream) {
@@ -1357,7 +1325,6 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
 __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restrict__ logits, long ld, const float* __restrict__ noise,
                                                           int64_t* __restrict__ out, long out_stride, int V, int top_k, float temperature,
                                                           Advance adv) {
-    TOKEN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     sample_topk_row<false>(logits, ld, noise, out, out_stride, V, top_k, temperature, adv, blockIdx.x, gridDim.x, smem);
 }
@@ -1605,7 +1572,7 @@ __device__ __forceinline__ void step_gemm(const __attribute__((address_space(4))
     // of 8, so with workgroups dealt to the XCDs round-robin they meet in one L2, as in the launch chain
     for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
         const int bx = vb % gx, r = vb / gx;
-        gemm16_tile<0, RB, CB, U, true>(x, w, ldx, K, N, M, ks, kz, g, bx, r % gy, r / gy, red, stat, fin);
+        gemm16_tile<RB, CB, U, true>(x, w, ldx, K, N, M, ks, kz, g, bx, r % gy, r / gy, red, stat, fin);
         __syncthreads();   // the tile's LDS is the next tile's
     }
 }
@@ -1631,7 +1598,6 @@ __device__ __forceinline__ T* as_global(T* p) {
 // the decoder's time: 208 / 214), not beside the 1 x 1 forms' 225 -- there the step's workgroup waits for one to retire, once per step.
 template <int D, bool T2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void gpt_step_kernel(const StepArgs* __restrict__ ap_) {
-    TOKEN_PRIO();
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int RB = T2 ? 2 : 1, CB = T2 ? 2 : 1, U = T2 ? 1 : GEMM_U;
     const unsigned G = gridDim.x;
@@ -1673,7 +1639,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             float* att = as_global(g.y);
             const int32_t* len = as_global(g.pos_dev);
             for (int bh = blockIdx.x; bh < n_bh; bh += G) {   // attention over the cache
-                attention_decode_item<D, true, true>(q, q_sB, kc, vc, att, H, 0, len, grp_rows, Tmax, att_scale, bh, smem);
+                attention_decode_item<D, true>(q, q_sB, kc, vc, att, H, 0, len, grp_rows, Tmax, att_scale, bh, smem);
                 __syncthreads();
             }
         } else {
@@ -1727,7 +1693,7 @@ static int step_check(const ccvs_gpt_decode* d, const char* who) {
     // what the persistent step covers -- what the pipelined generation uses -- and says so otherwise: no silent fall-back
     if (!(d->workspace && d->program)) { ccvs_set_error("%s: the persistent step needs `workspace` (ccvs_gemm_workspace_bytes, zeroed once) and `program` (ccvs_gpt_program_bytes)", who); return CCVS_ERR_ARG; }
     if (d->B > GEMM_DECODE_MAX_M) { ccvs_set_error("%s: the persistent step takes at most %d rows", who, GEMM_DECODE_MAX_M); return CCVS_ERR_ARG; }
-    if (!(decode_nt() == 1 && getenv_int("CCVS_GEMM_TILE2", 1) == 1)) { ccvs_set_error("%s: the persistent step is built for the default cache policies and tile (CCVS_DECODE_NT=1, CCVS_GEMM_TILE2=1)", who); return CCVS_ERR_ARG; }
+    if (!gemm_tile2()) { ccvs_set_error("%s: the persistent step is built for the default tile (CCVS_GEMM_TILE2=1)", who); return CCVS_ERR_ARG; }
     if (!(d->C >= 32 && d->F >= 32 && d->V >= 32 && d->C % 16 == 0 && d->F % 16 == 0)) { ccvs_set_error("%s: the persistent step needs >= 32 output columns per GEMM and K %% 16 == 0", who); return CCVS_ERR_ARG; }
     if (!((long)d->V * d->C * 4 < (1L << 31) && (long)d->F * d->C * 4 < (1L << 31) && (long)d->B * d->F * 4 < (1L << 31))) { ccvs_set_error("%s: operand beyond 2^31 bytes (32-bit buffer offsets)", who); return CCVS_ERR_ARG; }
     return CCVS_OK;
@@ -1828,9 +1794,8 @@ static int launch_step_persistent(const ccvs_gpt_decode* d, int D, hipStream_t s
         n_cu = prop.multiProcessorCount;
     }
     const StepArgs* a = (const StepArgs*)d->program;   // written by ccvs_gpt_decode_prepare
-    // workgroups per CU (an experiment, CCVS_STEP_WGS_PER_CU; default 1): more of them are all resident only with the chip to the step
-    // itself -- beside the frame decoder a CU has room for one -- and every grid barrier then waits for 2-4 x the arrivals
-    static const int per_cu = getenv_int("CCVS_STEP_WGS_PER_CU", 1) < 1 ? 1 : (getenv_int("CCVS_STEP_WGS_PER_CU", 1) > 4 ? 4 : getenv_int("CCVS_STEP_WGS_PER_CU", 1));
+    // one workgroup per CU: more of them are all resident only with the chip to the step itself -- beside the frame decoder a CU has
+    // room for one -- and every grid barrier then waits for 2-4 x the arrivals (profiles/r06_persistent_step.txt)
     const bool t2 = d->B > 32;
     size_t words = t2 ? STEP_GEMM_WORDS(2, 2) : STEP_GEMM_WORDS(1, 1);
     const size_t w_att = 16 + 4 * 256 + (size_t)d->Tmax, w_pick = PICK_SMEM_WORDS(d->V);
@@ -1844,7 +1809,7 @@ static int launch_step_persistent(const ccvs_gpt_decode* d, int D, hipStream_t s
             (void)hipFuncSetAttribute((const void*)gpt_step_kernel<Dv, T2v>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             attr_set = true;                                                                                                          \
         }                                                                                                                             \
-        hipLaunchKernelGGL((gpt_step_kernel<Dv, T2v>), dim3(n_cu * per_cu), dim3(256), smem, st, a);                                  \
+        hipLaunchKernelGGL((gpt_step_kernel<Dv, T2v>), dim3(n_cu), dim3(256), smem, st, a);                                           \
     } while (0)
     if (D == 64) { if (t2) STEP_LAUNCH(64, true); else STEP_LAUNCH(64, false); }
     else if (D == 32) { if (t2) STEP_LAUNCH(32, true); else STEP_LAUNCH(32, false); }

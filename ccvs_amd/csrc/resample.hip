@@ -571,8 +571,7 @@ extern "C" int ccvs_dwconvT4x4s2(const float* x, int64_t x_sN, const float* w, f
     CCVS_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "ccvs_dwconvT4x4s2: empty tensor");
     const long work = (long)N * C * H * W;
     const unsigned blocks = limited_grid(cdiv64(work, 256) < 65536 * 16 ? cdiv64(work, 256) : 65536 * 16, stream, 8);
-    static const int quad_form = getenv("CCVS_DWCONVT_X4") ? atoi(getenv("CCVS_DWCONVT_X4")) : 1;
-    if (quad_form && W % 4 == 0 && x_sN % 4 == 0) {
+    if (W % 4 == 0 && x_sN % 4 == 0) {
         const long work4 = (long)N * C * H * (W / 4);
         const unsigned blocks4 = limited_grid(cdiv64(work4, 256) < 65536 * 16 ? cdiv64(work4, 256) : 65536 * 16, stream, 8);
         hipLaunchKernelGGL(dwconvT4x4s2x4_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, x, (long)x_sN, w, y, (long)y_sN, (long)N, C, H, W);

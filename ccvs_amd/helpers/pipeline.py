@@ -295,16 +295,10 @@ class PipelinedRun:
             gen._dec_streams = have + [torch.cuda.Stream(device=self.dev, priority=prio[1]) for _ in range(n_dec - len(have))]
             gen._dec_stream = gen._dec_streams[0]
         self.dec_streams = gen._dec_streams[:n_dec]
+        # All encodes on the first decode stream.  Measured and rejected: a stream of their own (199 against 214 frames/s), and the
+        # encode of batch i on the decode stream that does not decode batch i (+-0, profiles/r05_enc_spread_ab.txt: an encode beside
+        # the other stream's decode takes 146-204 ms instead of 83 -- the chip, not the longer stream, is what is full).
         self.s_enc = self.dec_streams[0]
-        if env("CCVS_PIPELINE_ENC_STREAM", "0") == "1":    # the encodes on a stream of their own (slower: 199 against 214 frames/s)
-            if getattr(gen, "_enc_stream", None) is None:
-                gen._enc_stream = torch.cuda.Stream(device=self.dev, priority=prio[1])
-            self.s_enc = gen._enc_stream
-        # CCVS_PIPELINE_ENC_SPREAD=1 (experiments): the encode of batch i on the decode stream that does NOT decode batch i ((i + 1) % D),
-        # so that every decode stream carries the same share of encodes.  Measured +-0 (profiles/r05_enc_spread_ab.txt: 203.8 / 207.0
-        # against 206.8 / 206.7 frames/s): an encode beside the other stream's decode takes 146-204 ms instead of 83 -- the chip, not the
-        # longer stream, is what is full.  Default: all encodes on the first decode stream.
-        self.enc_spread = env("CCVS_PIPELINE_ENC_SPREAD", "0") == "1" and self.s_enc is self.dec_streams[0] and len(self.dec_streams) > 1
         self.chain_list = [gen._token_chain(k) for k in range(self.chains)]
         self.entry = torch.cuda.current_stream()
         self.index = first_iter
@@ -512,8 +506,7 @@ class PipelinedRun:
             if other_draw:
                 self.noise_feed.drain()        # `condition` draws the labels from the same generator: behind the previous batch's noise
             ev = {k: torch.cuda.Event(enable_timing=True) for k in ("e0", "e1", "d0", "d1")}
-            s_enc = self.dec_streams[(self.index - self.first_iter + 1) % len(self.dec_streams)] if self.enc_spread else self.s_enc
-            with torch.cuda.stream(s_enc):
+            with torch.cuda.stream(self.s_enc):
                 ev["e0"].record()
                 ws = gen.condition(data)
                 ev["e1"].record()
@@ -522,7 +515,7 @@ class PipelinedRun:
             for t in (ws["cropped"]["code"], ws["cropped"].get("cond_code"), ws["cropped"].get("state_code")):
                 if torch.is_tensor(t) and t.is_cuda:
                     t.record_stream(s_tok)
-            m = {"i": self.index, "ws": ws, "ev": ev, "batch": data["vid"].shape[0], "noise": None, "s_enc": s_enc}
+            m = {"i": self.index, "ws": ws, "ev": ev, "batch": data["vid"].shape[0], "noise": None}
             if self.noise_feed is not None:    # this batch's draws, in batch order: one [B, V] block per new token
                 n_cond = ws["cropped"]["cond_code"].shape[1] if "cond_code" in ws["cropped"] else 0
                 add_len = int(ws["total_len"]) - ws["cropped"]["code"].shape[1] - n_cond
@@ -648,7 +641,7 @@ class PipelinedRun:
 
         m = task["m"]
         m["segs"] = []
-        if st is not m["s_enc"]:     # encoded on one stream, decoded on this one
+        if st is not self.s_enc:     # encoded on one stream, decoded on this one
             st.wait_event(m["ev"]["e1"])
             for holder in (m["ws"]["cropped"], m["ws"]["encoded"], m["ws"]["data"]):
                 for v in holder.values():

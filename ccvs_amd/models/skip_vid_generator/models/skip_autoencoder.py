@@ -284,7 +284,7 @@ class InterBlock(nn.Module):
         split first Subpixel convolution, the stacked flow / occlusion up-sampling filter), on the current stream."""
         self._m_heads.packed()
         self._s_heads.packed()
-        if self.matching.proj is not None and ops.FUSE_WARP_PROJ:
+        if self.matching.proj is not None:
             self._proj_weight()
         if self.matching.upsample_flow is not None:
             self._upsample_fo_weight()
@@ -314,20 +314,14 @@ class InterBlock(nn.Module):
         # for the k contexts of a frame, so its share of the first Subpixel conv is computed ONCE per frame
         # (`pre`) and broadcast inside the conv epilogue; only [warped | flow | occ] is materialised per pair.
         p8 = ops.CONV_PRECISION == "bf16x3" and ops.CONV_P8   # conv -> conv intermediates stay in the kernel's packed split-bf16 form
-        # ... and the back-warp writes the Subpixel input in that form too (`ops.backwarp_p8`: [warped | flow | occ | 0 x 5], s + 8
-        # channels): the 99-channel convolution, the largest of the level, then stages by LDS-DMA like the layers behind it
-        p8_warp = p8 and ops.P8_WARP and s % 8 == 0 and w % 4 == 0
-        if p8_warp:
-            sp_in = None
-            fo = torch.empty(n * k, 3, h, w, dtype=torch.float32, device=dec.device)
-        else:
-            sp_in = torch.empty(n * k, s + 3, h, w, dtype=torch.float32, device=dec.device)
-            fo = sp_in[:, s:]
+        sp_in = torch.empty(n * k, s + 3, h, w, dtype=torch.float32, device=dec.device)
+        fo = sp_in[:, s:]
         inter_w = None
         variant = m.use_masked_flow or m.use_deformed_conv or m.use_tradeoff or not m.use_corr
         if fo_prev is not None:
             ops.dwconvT4x4s2(fo_prev, self._upsample_fo_weight(), out=fo)       # learned x2 of flow and occ
-            proj_w = self._proj_weight() if (m.proj is not None and ops.FUSE_WARP_PROJ and not variant) else None
+            # warp + 1x1 projection of the contexts in one kernel (`backwarp_proj`) instead of backwarp followed by the convolution
+            proj_w = self._proj_weight() if (m.proj is not None and not variant) else None
             # Matching variants (skip_autoencoder.py:182-195): deformable conv instead of the back-warp, then * (1 - sigmoid(occ)),
             # + the up-sampled trade-off feature, LeakyReLU -- fused into the deform kernel's epilogue or one pass behind the warp
             occ_mask = fo[:, 2:3] if m.use_masked_flow else None
@@ -354,7 +348,7 @@ class InterBlock(nn.Module):
             feat = m.convs[2](m.convs[1](feat, out_p8=p8), out_p8=p8)
             self._m_heads(feat, fo, accumulate=fo_prev is not None)
             del feat, pre, inter_w
-            return self._subpixel_and_blend(dec, ctxs, fo, sp_in, p8, p8_warp)
+            return self._subpixel_and_blend(dec, ctxs, fo, sp_in, p8)
         if m.proj is not None:
             pa = m.proj(dec)                                                     # input projected once per n, not k times
             if inter_w is None:   # warp and projection in one pass: the warped s-channel tensor is never written
@@ -370,22 +364,17 @@ class InterBlock(nn.Module):
         feat = m.convs[2](m.convs[1](m.convs[0](corr, out_p8=p8), out_p8=p8), out_p8=p8)
         self._m_heads(feat, fo, accumulate=fo_prev is not None)
         del corr, feat, pa, pb, inter_w
-        return self._subpixel_and_blend(dec, ctxs, fo, sp_in, p8, p8_warp)
+        return self._subpixel_and_blend(dec, ctxs, fo, sp_in, p8)
 
-    def _subpixel_and_blend(self, dec, ctxs, fo, sp_in, p8, p8_warp):
+    def _subpixel_and_blend(self, dec, ctxs, fo, sp_in, p8):
         """Subpixel refinement into `fo`, then the warp / fusion / blend of the contexts into `dec`; returns (fo, toff)."""
         s, k = dec.shape[1], len(ctxs)
         sp = self.subpixel
-        w_dec, w_rest, w_rest8 = self._sub0_split()
+        w_dec, w_rest = self._sub0_split()
         conv0 = sp.convs[0].conv
         pre = ops.conv2d(dec, w_dec, None, conv0.out_channel, 3, pad=1)          # [N,128,H,W], before dec is blended
-        if p8_warp:
-            sp_p8 = ops.backwarp_p8(ctxs, fo, self.flow_mult)
-            feat = ops.conv2d(sp_p8, w_rest8, conv0.bias, conv0.out_channel, 3, pad=1, act=True, pre=pre, pre_div=k, out_p8=p8)
-            del sp_p8
-        else:
-            ops.backwarp(ctxs, fo[:, :2], self.flow_mult, out=sp_in[:, :s])
-            feat = ops.conv2d(sp_in, w_rest, conv0.bias, conv0.out_channel, 3, pad=1, act=True, pre=pre, pre_div=k, out_p8=p8)
+        ops.backwarp(ctxs, fo[:, :2], self.flow_mult, out=sp_in[:, :s])
+        feat = ops.conv2d(sp_in, w_rest, conv0.bias, conv0.out_channel, 3, pad=1, act=True, pre=pre, pre_div=k, out_p8=p8)
         # with the trade-off variant the last feature is the next level's `toff` (skip_autoencoder.py:227): written as fp32
         feat = sp.convs[2](sp.convs[1](feat, out_p8=p8), out_p8=p8 and not sp.use_tradeoff)
         self._s_heads(feat, fo, accumulate=True)
@@ -418,14 +407,11 @@ class InterBlock(nn.Module):
         with the FULL fan-in scale 1/sqrt((2s+3)*9) of the unsplit layer."""
         conv = self.subpixel.convs[0].conv
         w = conv.weight
-        key = (w.data_ptr(), w._version, w.device, ops.CONV_PRECISION, ops.P8_WARP)
+        key = (w.data_ptr(), w._version, w.device, ops.CONV_PRECISION)
         if getattr(self, "_sub0", None) is None or self._sub0[0] != key:
             s = self.feat_size
-            w8 = None
-            if ops.P8_WARP:   # third form, only for the packed back-warp (off by default): the same block with five zero channels behind [warped | flow | occ]
-                w8 = ops.pack_conv_weight(torch.cat([w[:, s:].detach(), w.new_zeros(w.shape[0], 5, w.shape[2], w.shape[3])], dim=1), scale=conv.scale)
-            self._sub0 = (key, ops.pack_conv_weight(w[:, :s], scale=conv.scale), ops.pack_conv_weight(w[:, s:], scale=conv.scale), w8)
-        return self._sub0[1], self._sub0[2], self._sub0[3]
+            self._sub0 = (key, ops.pack_conv_weight(w[:, :s], scale=conv.scale), ops.pack_conv_weight(w[:, s:], scale=conv.scale))
+        return self._sub0[1], self._sub0[2]
 
     def forward(self, input, inters, flows=None, occs=None, toffs=None, eps=1e-6):
         """Reference signature (skip_autoencoder.py:246): returns (fused input, flows, occs, toffs)."""

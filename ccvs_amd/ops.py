@@ -52,16 +52,15 @@ class KernelTimer:
 
 KERNEL_TIMER = None  # set to a KernelTimer() to time conv launches
 # Packed split-bf16 intermediates in the conv -> conv chains of the InterBlocks (P8Act): 49|99 -> 128 -> 64 -> 32 -> heads.  Bit-identical
-# to fp32 intermediates.  ON since round 4 (CCVS_CONV_P8=0: fp32): the consumers stage by LDS-DMA with no conversion (128->64 at
+# to fp32 intermediates.  ON since round 4: the consumers stage by LDS-DMA with no conversion (128->64 at
 # 256^2 298 -> 382 TFLOP/s on the 512-pixel tile, 64->32 205 -> 250), the producers' packed epilogue no longer waits on vector memory
 # between its stores (it cost them 20 % in round 3: that, not the format, made P8 a net loss then); a BAIR batch's convolutions 617 ->
 # 570 ms alone, the default bench line 190.7 -> 200.4 frames/s on one box (profiles/r04_conv_p8_ab.txt).
-CONV_P8 = __import__("os").environ.get("CCVS_CONV_P8", "1") == "1"
-# ... and the back-warp in front of the first Subpixel convolution can write that convolution's packed input (`backwarp_p8`).  OFF:
-# the convolution gains (99->128 at 256^2 268 -> 306 TFLOP/s, 13 ms per decode) what the packed back-warp loses (3.85 against 2.9 ms
-# per 120 x 96 x 256^2 call in its best form of three -- one pixel per lane, four pixels per lane, four pixels + LDS transposition);
-# the default line 197.0 against 197.1 frames/s (profiles/r04_p8_warp_ab.txt)
-P8_WARP = __import__("os").environ.get("CCVS_P8_WARP", "0") == "1"
+CONV_P8 = True
+# The back-warp in front of the first Subpixel convolution does NOT write that convolution's packed input (`backwarp_p8`, an entry
+# point the decoder does not call): the convolution gains (99->128 at 256^2 268 -> 306 TFLOP/s, 13 ms per decode) what the packed
+# back-warp loses (3.85 against 2.9 ms per 120 x 96 x 256^2 call in its best form of three -- one pixel per lane, four pixels per
+# lane, four pixels + LDS transposition); the line 197.0 against 197.1 frames/s (profiles/r04_p8_warp_ab.txt)
 
 
 def conv_persistent_tiles(mode=-1):
@@ -98,8 +97,6 @@ def _as_rows_dense(t):
 #   "bf16x3": split-bf16, 3 products per fp32 product on v_mfma_f32_32x32x16_bf16 (default)
 #   "f32"   : exact fp32 on v_mfma_f32_32x32x2_f32
 CONV_PRECISION = "bf16x3"
-# Matching: warp + 1x1 projection of the contexts in one kernel (`backwarp_proj`) instead of backwarp followed by the convolution.
-FUSE_WARP_PROJ = __import__("os").environ.get("CCVS_FUSE_WARP_PROJ", "1") == "1"
 # Explicit `ccvs_conv_desc.cu_limit` of the convolution launches (0 = the budget of the stream, see `stream_cu_limit`); tests.
 CONV_CU_LIMIT = 0
 
