@@ -8,23 +8,22 @@
 // Both are HBM-bound reductions: every pixel is read once (the SSIM tile re-reads a 3-pixel halo through L2).
 #include "common.h"
 
-// ---- PSNR -------------------------------------------------------------------------------------
-// one workgroup per image: sum (x - y)^2 over C*H*W in float64, score = -10 log10(mse / R^2 + 1e-8)
-__global__ __launch_bounds__(1024) void psnr_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, long per_image,
-                                                     double inv_range) {
-    const long base = (long)blockIdx.x * per_image;
+// ---- PSNR / MSE ------------------------------------------------------------------------------
+// sum ((x - y) * inv_range)^2 over `count` elements by one 1024-thread workgroup, in float64: per lane, per wave, then the 16 waves
+// in index order (the same bits on every run).  The total is valid in thread 0.
+__device__ __forceinline__ double block_sum_sq_diff(const float* __restrict__ x, const float* __restrict__ y, long count, double inv_range) {
     double acc = 0.0;
-    const long n4 = ((reinterpret_cast<uintptr_t>(x + base) | reinterpret_cast<uintptr_t>(y + base)) & 15) == 0 ? per_image / 4 : 0;
-    const float4* x4 = reinterpret_cast<const float4*>(x + base);
-    const float4* y4 = reinterpret_cast<const float4*>(y + base);
+    const long n4 = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 ? count / 4 : 0;
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    const float4* y4 = reinterpret_cast<const float4*>(y);
     for (long i = threadIdx.x; i < n4; i += 1024) {
         const float4 a = x4[i], b = y4[i];
         const double d0 = ((double)a.x - (double)b.x) * inv_range, d1 = ((double)a.y - (double)b.y) * inv_range;
         const double d2 = ((double)a.z - (double)b.z) * inv_range, d3 = ((double)a.w - (double)b.w) * inv_range;
         acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
     }
-    for (long i = 4 * n4 + threadIdx.x; i < per_image; i += 1024) {
-        const double d = ((double)x[base + i] - (double)y[base + i]) * inv_range;
+    for (long i = 4 * n4 + threadIdx.x; i < count; i += 1024) {
+        const double d = ((double)x[i] - (double)y[i]) * inv_range;
         acc += d * d;
     }
 #pragma unroll
@@ -32,11 +31,25 @@ __global__ __launch_bounds__(1024) void psnr_kernel(const float* __restrict__ x,
     __shared__ double part[16];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = 0.0;
+    double s = 0.0;
+    if (threadIdx.x == 0)
         for (int w = 0; w < 16; ++w) s += part[w];   // fixed order: the same bits on every run
-        out[blockIdx.x] = (float)(-10.0 * log10(s / (double)per_image + 1e-8));
-    }
+    return s;
+}
+
+// one workgroup per image: score = -10 log10(mse / R^2 + 1e-8)
+__global__ __launch_bounds__(1024) void psnr_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ out, long per_image,
+                                                     double inv_range) {
+    const long base = (long)blockIdx.x * per_image;
+    const double s = block_sum_sq_diff(x + base, y + base, per_image, inv_range);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)(-10.0 * log10(s / (double)per_image + 1e-8));
+}
+
+// F.mse_loss(a, b) (reduction 'mean') of n fp32 elements into one fp32: the float64 sum rounded once.  One workgroup -- the figures
+// this serves are validation scalars over a clip's spectrograms or states, a few MB at most.
+__global__ __launch_bounds__(1024) void mse_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, long n) {
+    const double s = block_sum_sq_diff(a, b, n, 1.0);
+    if (threadIdx.x == 0) out[0] = (float)(s / (double)n);
 }
 
 extern "C" int ccvs_psnr(const float* x, const float* y, float* out, int64_t N, int64_t per_image, float data_range, void* stream) {
@@ -44,6 +57,14 @@ extern "C" int ccvs_psnr(const float* x, const float* y, float* out, int64_t N, 
     CCVS_REQUIRE(N > 0 && N < 2147483647L && per_image > 0 && data_range > 0.f, "ccvs_psnr: bad arguments");
     hipLaunchKernelGGL(psnr_kernel, dim3((unsigned)N), dim3(1024), 0, (hipStream_t)stream, x, y, out, (long)per_image, 1.0 / (double)data_range);
     CCVS_CHECK_LAUNCH("ccvs_psnr");
+    return CCVS_OK;
+}
+
+extern "C" int ccvs_mse(const float* a, const float* b, float* out, int64_t n, void* stream) {
+    CCVS_REQUIRE(a && b && out, "ccvs_mse: null pointer");
+    CCVS_REQUIRE(n > 0, "ccvs_mse: no elements");
+    hipLaunchKernelGGL(mse_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a, b, out, (long)n);
+    CCVS_CHECK_LAUNCH("ccvs_mse");
     return CCVS_OK;
 }
 

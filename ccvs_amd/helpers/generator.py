@@ -52,6 +52,11 @@ class Generator:
             raise NotImplementedError("--q_skip_rgb with --x_cond_len 0: frame 0 is decoded without context, so its skip_rgb output "
                                       "stays at the coarsest level's resolution and cannot be stacked with the later frames "
                                       "(the reference fails there in torch.cat)")
+        self.decode_stft = bool(getattr(self.opt, "decode_stft", False))
+        if self.decode_stft and not self.opt.stft:
+            raise ValueError("--decode_stft decodes the STFT token stream of the audio-conditioned configuration: it needs --x_stft")
+        if self.decode_stft and self.opt.step_by_step:
+            raise NotImplementedError("--step_by_step with --decode_stft is not on the MI355X path (the plain synthesis schedule runs it)")
         if getattr(self.opt, "deblurring", False) and self.opt.step_by_step:
             raise NotImplementedError("--step_by_step with --deblurring is not on the MI355X path (the plain synthesis schedule runs the mode)")
 
@@ -226,6 +231,8 @@ class Generator:
             fake_data["vid"] = torch.cat([fake_data["vid"], ws["data"]["vid"][:, -1:]], dim=1)
         if opt.state and state_code is not None:                            # generator.py:168-169
             fake_data.update(self.state_model({"state_code": state_code}, mode='vid_decoder'))
+        if self.decode_stft:                                                # (ccvs_amd) the clip's sound: its final STFT tokens as spectrograms
+            fake_data.update(self._decode_stft_tokens(state_code))
         return fake_data
 
     def _decode_codes_stream(self, ws, code_of, final):
@@ -240,7 +247,15 @@ class Generator:
             fake_data["vid"] = torch.cat([fake_data["vid"], ws["data"]["vid"][:, -1:]], dim=1)
         if opt.state and state_code is not None:                            # generator.py:168-169
             fake_data.update(self.state_model({"state_code": state_code}, mode='vid_decoder'))
+        if self.decode_stft:                                                # (ccvs_amd) the clip's sound: its final STFT tokens as spectrograms
+            fake_data.update(self._decode_stft_tokens(state_code))
         return fake_data
+
+    def _decode_stft_tokens(self, state_code):
+        """--decode_stft promises `stft` beside the clip: a token stage that returns no ancillary stream is an error, not an omission."""
+        if state_code is None or 0 in state_code.size():
+            raise RuntimeError("--decode_stft: the token stage returned no STFT token stream to decode")
+        return self.stft_model({"state_code": state_code}, mode='vid_decoder')
 
     @torch.no_grad()
     def reconstruct(self, ws):
@@ -261,6 +276,8 @@ class Generator:
             rec_data["vid"] = torch.cat([rec_data["vid"], data["vid"][:, -1:]], dim=1)
         if opt.state:
             rec_data["state"] = data["state"]
+        if self.decode_stft:                                                # (ccvs_amd) the real clip's own STFT tokens, decoded
+            rec_data.update(self._decode_stft_tokens(encoded_data["state_code"]))
         return rec_data
 
     @torch.no_grad()
@@ -512,6 +529,9 @@ class Generator:
             vid = item["vid"] if isinstance(item, dict) else item
             save_video_batch(vid, bs, global_iter, os.path.join(self.opt.result_path, name), self.opt.fps, True,
                              self.opt.imagenet_norm, [-1, 1], self.opt.dataset)
+            stft = item.get("stft") if self.decode_stft and isinstance(item, dict) else None
+            if stft is not None:                                            # (ccvs_amd) --decode_stft: one float32 [T, H, W] .npy per clip
+                save_stft_batch(stft, bs, global_iter, os.path.join(self.opt.result_path, name + "_stft"))
             state = out.get("real_state") if name == "real" else (item.get("state") if isinstance(item, dict) else None)
             if self.opt.state and state is not None:                        # generator.py:213-223: clips with the state marker
                 save_video_batch(vid, bs, global_iter, os.path.join(self.opt.result_path, name + "_state"), self.opt.fps, True,
@@ -645,6 +665,15 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
             import numpy as np
             np.save(stem + ".npy", u8[i].numpy())
     return u8
+
+
+def save_stft_batch(stft, bs, global_iter, path):
+    """(ccvs_amd) The decoded spectrograms [B, T, 1, H, W] of a batch as float32 .npy files [T, H, W], named like the clips' own files."""
+    import numpy as np
+    arr = stft.detach().float().cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    for i in range(arr.shape[0]):
+        np.save(os.path.join(path, f"vid_{bs * global_iter + i:05d}.npy"), arr[i, :, 0])
 
 
 def draw_cross(img, x, y):

@@ -425,8 +425,8 @@ class PipelinedRun:
         with torch.cuda.stream(self.s_enc):
             gen.vid_model.prepare_packed()
             for model in (gen.state_model, gen.stft_model):
-                if model is not None:
-                    prepare_packed_modules(model)
+                if model is not None:   # (the STFT decoder runs with --decode_stft only)
+                    prepare_packed_modules(model, skip=None if getattr(gen, "decode_stft", False) else getattr(model, "net_d", None))
             packed = torch.cuda.Event()
             packed.record()
         for st in set(self.dec_streams + [st_ for _, st_ in self.chain_list]):
@@ -745,7 +745,8 @@ class PipelinedRun:
                     out["rec"] = self.gen.reconstruct(ws)
                 out["finished"] = self.finish(m["i"], fake) if self.finish is not None else None
                 for t in ((fake["vid"], fake["code"]) + ((out["rec"]["vid"],) if out["rec"] is not None else ())
-                          + ((out["blur"],) if out["blur"] is not None else ())):   # handed to the caller's stream
+                          + ((out["blur"],) if out["blur"] is not None else ())
+                          + tuple(d["stft"] for d in (fake, out["rec"]) if d is not None and d.get("stft") is not None)):   # handed to the caller's stream
                     t.record_stream(self.entry)
                 if self.consume is not None:   # a long run: the caller takes every batch as it comes, nothing is kept here
                     self.consume(out)

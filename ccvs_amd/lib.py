@@ -17,7 +17,7 @@ EXPORTS = [
     "ccvs_correlation7x7", "ccvs_backwarp", "ccvs_backwarp_ctx", "ccvs_backwarp_p8_ctx", "ccvs_backwarp_proj_ctx", "ccvs_warp_fuse_blend", "ccvs_warp_fuse_blend_ctx", "ccvs_tap_shift_add", "ccvs_vq_argmin", "ccvs_embed_gather", "ccvs_l2_normalize_channels",
     "ccvs_gpt_embed", "ccvs_layernorm", "ccvs_gemm_workspace_bytes", "ccvs_gemm_nt", "ccvs_gemm_ln", "ccvs_gemm_ln_qkv", "ccvs_attention", "ccvs_kv_append", "ccvs_sample_topk", "ccvs_sample_topk_philox", "ccvs_sample_topn",
     "ccvs_gpt_decode_step", "ccvs_gpt_decode_status", "ccvs_gpt_program_bytes", "ccvs_gpt_decode_prepare", "ccvs_pack_u8", "ccvs_pack_u8_norm", "ccvs_stream_cu_limit", "ccvs_psnr", "ccvs_ssim_workspace_bytes", "ccvs_ssim", "ccvs_resize_bilinear",
-    "ccvs_deform_conv3x3_ctx", "ccvs_gconvT4x4s2", "ccvs_flow_mask_toff", "ccvs_gaussian_blur", "ccvs_to_rgb",
+    "ccvs_deform_conv3x3_ctx", "ccvs_gconvT4x4s2", "ccvs_flow_mask_toff", "ccvs_gaussian_blur", "ccvs_to_rgb", "ccvs_channel_head", "ccvs_mse",
 ]
 
 
@@ -139,6 +139,8 @@ def load():
         "ccvs_flow_mask_toff": [vp, i64, i64, vp, i64, vp, i64, i64, i32, i32, i32, i32, i32, vp],
         "ccvs_gaussian_blur": [vp, i64, i64, vp, i32, i32, i32, i32, i32, C.POINTER(C.c_float), vp],
         "ccvs_to_rgb": [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
+        "ccvs_channel_head": [vp, i64, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+        "ccvs_mse": [vp, vp, vp, i64, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

@@ -15,6 +15,9 @@ convolution of the trade-off feature, masked-flow / trade-off epilogue).
 The StyleGAN2-style output head of --q_skip_rgb (a ToRGB per decoder level, each level's RGB up-sampled into the next) runs one
 `ops.to_rgb` launch per level.
 
+The STFT decoder (`StftDecoder`, audio tokens -> spectrogram frames) ends in `ops.channel_head`: the 1x1 convolution to one channel, its
+LeakyReLU and the tanh in one pass.
+
 Not supported (outside the hot path): layout decoders, training.
 """
 import math
@@ -588,11 +591,13 @@ class SkipGANDecoder(nn.Module):
         return out1, out2
 
 
-def prepare_packed_modules(root):
+def prepare_packed_modules(root, skip=None):
     """Fill the lazily built weight caches of every sub-module of `root` on the current stream: `packed()` of the convolutions /
-    linears, `prepare_packed()` of the InterBlocks, the transposed codebook of a VectorQuantizer (`QVidModel.prepare_packed`)."""
+    linears, `prepare_packed()` of the InterBlocks, the transposed codebook of a VectorQuantizer (`QVidModel.prepare_packed`).
+    `skip`: a sub-module whose tree is left alone (a network this run never calls)."""
+    skipped = set(skip.modules()) if skip is not None else ()
     for mod in root.modules():
-        if mod is root:
+        if mod is root or mod in skipped:
             continue
         if hasattr(mod, "prepare_packed"):
             mod.prepare_packed()
@@ -679,3 +684,26 @@ class StftEncoder(nn.Module):
         for conv in self.convs:
             x = conv(x.contiguous())
         return unflatten_vid(x, vid_size)
+
+
+class StftDecoder(nn.Module):
+    """skip_autoencoder.py:544-556: quantised STFT map [stft_size, h, w] -> spectrogram frame [1, 8h, 8w] in (-1, 1): one 3x3 conv, three
+    transposed 3x3 stride-2 convs + blur (all ConvLayers with bias + LeakyReLU(0.1)) on the convolution kernels, then the 1x1 ConvLayer to
+    one channel, its LeakyReLU and the tanh as one `ops.channel_head` launch."""
+
+    def __init__(self, opt):
+        super().__init__()
+        convs = [ConvLayer(opt.stft_size, opt.stft_hsize, 3, upsample=False)]
+        for _ in range(3):
+            convs.append(ConvLayer(opt.stft_hsize, opt.stft_hsize, 3, upsample=True))
+        convs.append(ConvLayer(opt.stft_hsize, 1, 1, upsample=False))
+        self.convs = nn.Sequential(*convs)
+
+    @torch.no_grad()
+    def forward(self, input):
+        x, vid_size = flatten_vid(input)
+        for conv in self.convs[:-1]:
+            x = conv(x.contiguous())
+        head = self.convs[-1].conv
+        out = ops.channel_head(x, head.weight.detach(), head.scale, head.bias.detach(), act=self.convs[-1].activate, tanh=True)
+        return unflatten_vid(out, vid_size)

@@ -5,8 +5,8 @@ robot-arm position) from the quantised latent map of every frame, and a scalar V
 
 Host-side mirror of the inference half of the reference's
 `models/skip_vid_generator/models/state_model.py` (forward mode dispatch :22-46, preprocess_input :48-52,
-initialize_networks :54-62, encode :109-117, decode :119-124): same constructor, modes, dict keys,
-`ValueError` on an unknown mode; the training modes raise.
+initialize_networks :54-62, eval loss :99-107, encode :109-117, decode :119-124): same constructor, modes, dict keys,
+`ValueError` on an unknown mode; the training mode (`state_estimator`) raises.
 """
 import torch
 
@@ -14,6 +14,7 @@ from ..models.skip_autoencoder import StateEstimator
 from ..modules.quantize import VectorQuantizer
 from ccvs_amd.tools.utils import to_cuda
 from ccvs_amd.models import load_network
+from ccvs_amd import ops
 
 
 class StateModel(torch.nn.Module):
@@ -27,11 +28,13 @@ class StateModel(torch.nn.Module):
         self.logger = logger if self.is_main else None
 
     def forward(self, data, mode='', log=False, global_iter=None):
-        if mode in ('state_estimator', 'eval_state_estimator'):
+        if mode == 'state_estimator':
             raise NotImplementedError(f"mode '{mode}' (training loss) is outside the MI355X hot path")
-        if mode not in ('img_encoder', 'vid_encoder', 'img_decoder', 'vid_decoder'):
+        if mode not in ('eval_state_estimator', 'img_encoder', 'vid_encoder', 'img_decoder', 'vid_decoder'):
             raise ValueError(f"mode '{mode}' is invalid")
         z, state, state_code = self.preprocess_input(data)
+        if mode == 'eval_state_estimator':
+            return self.compute_eval_state_estimator_loss(z, state, log, global_iter)
         if mode in ('img_encoder', 'vid_encoder'):
             return self.encode(state, z)
         return self.decode(state_code, "img" if mode == 'img_decoder' else "vid")
@@ -50,6 +53,13 @@ class StateModel(torch.nn.Module):
         if self.is_main:
             self.net_s = load_network(self.net_s, "state_s", self.opt) if self.net_s is not None else None
             self.net_q = load_network(self.net_q, "state_q", self.opt)
+
+    @torch.no_grad()
+    def compute_eval_state_estimator_loss(self, z, state, log, global_iter):
+        """state_model.py:99-107: F.mse_loss(quantise(estimated or given state), given state) as a 0-dim fp32 tensor on the device."""
+        pred_state = self.net_s(z) if self.net_s is not None else state
+        pred_state_q, _, _ = self.net_q(pred_state.contiguous())
+        return ops.mse(pred_state_q, state)
 
     @torch.no_grad()
     def encode(self, state, z):

@@ -1,16 +1,18 @@
 """STFT auto-encoder, inference side (reference: models/skip_vid_generator/models/stft_model.py).
 
-Only what the synthesis path uses: `encode` turns the spectrogram frames of a clip into the ancillary token stream
-(`state_code`) that conditions the transformer in the audio-conditioned configuration (SURVEY 8f row f2,
-scripts/drums/save_videos_audio_on.sh).  The decoder half (`StftDecoder`, tokens -> spectrogram) and the training
-losses are outside the path and raise.
+`encode` turns the spectrogram frames of a clip into the ancillary token stream (`state_code`) that conditions the
+transformer in the audio-conditioned configuration (scripts/drums/save_videos_audio_on.sh); `decode`
+turns a token stream -- given, or predicted by the transformer (scripts/drums/save_videos_audio_off.sh) -- back into
+spectrogram frames; `eval_stft_reconstruction` is the validation figure of an `stft_ae` checkpoint.  The training loss
+(`stft_reconstruction`, with its VGG term) is outside the path and raises.
 """
 import torch
 
-from ..models.skip_autoencoder import StftEncoder
+from ..models.skip_autoencoder import StftEncoder, StftDecoder
 from ..modules.quantize import VectorQuantizer
 from ccvs_amd.tools.utils import to_cuda
 from ccvs_amd.models import load_network
+from ccvs_amd import ops
 
 
 class StftModel(torch.nn.Module):
@@ -27,8 +29,14 @@ class StftModel(torch.nn.Module):
         stft, stft_code = self.preprocess_input(data)
         if mode in ('img_encoder', 'vid_encoder'):
             return self.encode(stft)
-        if mode in ('stft_reconstruction', 'eval_stft_reconstruction', 'img_decoder', 'vid_decoder'):
-            raise NotImplementedError(f"mode '{mode}' (STFT decoder / losses) is outside the MI355X hot path")
+        if mode == 'eval_stft_reconstruction':
+            return self.compute_eval_stft_reconstruction_loss(stft, log, global_iter)
+        if mode == 'img_decoder':
+            return self.decode(stft_code, "img")
+        if mode == 'vid_decoder':
+            return self.decode(stft_code, "vid")
+        if mode == 'stft_reconstruction':
+            raise NotImplementedError(f"mode '{mode}' (training loss) is outside the MI355X hot path")
         raise ValueError(f"mode '{mode}' is invalid")
 
     def preprocess_input(self, data):
@@ -38,11 +46,13 @@ class StftModel(torch.nn.Module):
         return data["stft"], data["state_code"]
 
     def initialize_networks(self, is_train):
-        """stft_model.py:55-66 (encoder and quantiser only)."""
+        """stft_model.py:55-66: encoder, decoder, quantiser, built in the reference's order (a seeded constructor draws the same values)."""
         self.net_e = StftEncoder(self.opt).cuda()
+        self.net_d = StftDecoder(self.opt).cuda()
         self.net_q = VectorQuantizer(self.opt.stft_num, self.opt.stft_size, beta=0.25).cuda()
         if self.is_main:
             self.net_e = load_network(self.net_e, "stft_e", self.opt)
+            self.net_d = load_network(self.net_d, "stft_d", self.opt)
             self.net_q = load_network(self.net_q, "stft_q", self.opt)
 
     @torch.no_grad()
@@ -51,3 +61,18 @@ class StftModel(torch.nn.Module):
         z = self.net_e(stft)
         _, _, info = self.net_q(z)
         return {"state_code": info[2].view(stft.shape[0], -1)}
+
+    @torch.no_grad()
+    def decode(self, state_code, dtype):
+        """stft_model.py:127-133: state_code [B, (T*) h*w] -> {"stft": [B, (T,) 1, 8h, 8w]} in (-1, 1)."""
+        h, w = self.opt.stft_shape
+        n = state_code.numel() // (h * w)
+        z = self.net_q.embed_code_nchw(state_code, n, h, w)
+        lead = [state_code.size(0)] if dtype == "img" else [state_code.size(0), -1]
+        return {"stft": self.net_d(z.view(*lead, self.opt.stft_size, h, w))}
+
+    @torch.no_grad()
+    def compute_eval_stft_reconstruction_loss(self, stft, log, global_iter):
+        """stft_model.py:112-118: F.mse_loss(stft, decode(quantise(encode(stft)))) as a 0-dim fp32 tensor on the device."""
+        z_q, _, _ = self.net_q(self.net_e(stft))
+        return ops.mse(stft, self.net_d(z_q))

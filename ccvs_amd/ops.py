@@ -350,6 +350,25 @@ def to_rgb(x, w_scaled, b_conv, bias, skip=None, out=None):
     return out
 
 
+def channel_head(x, weight, scale, bias=None, act=True, tanh=False, out=None):
+    """A 1 x 1 EqualConv2d to ONE channel with its epilogue, one `ccvs_channel_head` launch (the StftDecoder's last ConvLayer and the
+    tanh behind it, skip_autoencoder.py:550,555): tanh(lrelu(bias + sum_c (weight[c] * scale) x[:, c])), the LeakyReLU(0.1) with `act`,
+    the tanh with `tanh`.  x [N,C,H,W] (channel planes dense, any batch stride); weight: C values ([1,C,1,1] or [C]); bias [1] or None.
+    Returns [N,1,H,W]."""
+    _need_gpu(x, weight, bias, out)
+    assert x.dtype == torch.float32 and x.dim() == 4 and weight.dtype == torch.float32
+    if not _planes_dense(x):
+        x = x.contiguous()
+    n, c, h, w = x.shape
+    assert weight.numel() == c and weight.is_contiguous() and (bias is None or bias.numel() == 1), (tuple(weight.shape), c)
+    if out is None:
+        out = torch.empty(n, 1, h, w, dtype=torch.float32, device=x.device)
+    assert out.shape == (n, 1, h, w) and out.is_contiguous() and out.dtype == torch.float32
+    _lib.check(_lib.load().ccvs_channel_head(_p(x), x.stride(0), _p(weight), float(scale), _p(bias), _p(out), n, c, h, w,
+                                             1 if act else 0, 1 if tanh else 0, _stream()), "ccvs_channel_head")
+    return out
+
+
 # ------------------------------------------------------------------ cost volume / warp
 def correlation7x7(first, second, stride, first_div=1, lrelu=False):
     _need_gpu(first, second)
@@ -845,6 +864,17 @@ def psnr(x, y, data_range=1.0):
     x, y = x.contiguous(), y.contiguous()
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().ccvs_psnr(_p(x), _p(y), _p(out), x.shape[0], x[0].numel(), float(data_range), _stream()), "ccvs_psnr")
+    return out
+
+
+def mse(a, b):
+    """F.mse_loss(a, b): mean((a - b)^2) of two fp32 tensors of one shape, float64 inside, as a 0-dim fp32 tensor on the device
+    (`ccvs_mse`; nothing is synchronised)."""
+    _need_gpu(a, b)
+    assert a.shape == b.shape and a.dtype == b.dtype == torch.float32 and a.numel() > 0, (a.shape, b.shape)
+    a, b = a.contiguous(), b.contiguous()
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    _lib.check(_lib.load().ccvs_mse(_p(a), _p(b), _p(out), a.numel(), _stream()), "ccvs_mse")
     return out
 
 

@@ -24,8 +24,8 @@ def str2bool(v):
     raise argparse.ArgumentTypeError("Boolean value expected.")
 
 
-def _flag(parser, name, default=False):
-    parser.add_argument(name, type=str2bool, nargs="?", const=True, default=default)
+def _flag(parser, name, default=False, help=None):
+    parser.add_argument(name, type=str2bool, nargs="?", const=True, default=default, help=help)
 
 
 # dataset presets applied after a first parse (tools/options.py:396-450)
@@ -71,6 +71,8 @@ class Options:
         # (helpers/generator.py:172-189); on by default like the reference, switchable because it is not part of the
         # synthesized-frames metric
         _flag(p, "--rec_pass", default=True)
+        _flag(p, "--decode_stft", help="(ccvs_amd) with --x_stft: decode the clip's final STFT token stream (and, with the rec pass, the real "
+                                      "clip's) back to spectrogram frames -- out['fake'|'rec']['stft'], fake_stft/ and rec_stft/ .npy files")
         # (ccvs_amd) the reference encodes EVERY frame of the input clip (helpers/generator.py:69) although synthesis reads the
         # conditioning frames only -- the other codes feed its rec pass and `enc_code`.  `--encode_all false`: with the rec pass
         # off and no state / audio / point-to-point conditioning, encode just the frames the conditioning crop keeps (the same

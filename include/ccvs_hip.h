@@ -146,6 +146,15 @@ int ccvs_gaussian_blur(const float* x, int64_t x_sN, int64_t x_sC, float* y, int
 int ccvs_to_rgb(const float* x, int64_t x_sN, const float* w, const float* b_conv, const float* bias, const float* skip, float* y,
                 int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
 
+/* Output head of StftDecoder (skip_autoencoder.py:550,555): ConvLayer(hsize, 1, 1) -- the 1 x 1 EqualConv2d to ONE channel, its bias,
+ * LeakyReLU(0.1) -- and the F.tanh behind the stack, in one pass:
+ *   y[n, h, w] = tanh(lrelu(bias[0] + sum_c (w[c] * scale) x[n, c, h, w]))
+ * with the LeakyReLU only when `act` and the tanh only when `tanh_out`.  x [N,C,H,W] (batch stride x_sN, channel planes dense);
+ * w [C] = the EqualConv2d weight, multiplied by `scale` in fp32 as skip_autoencoder.py:55,58 does; bias [1] or NULL; y [N,1,H,W]
+ * dense.  C <= 8192. */
+int ccvs_channel_head(const float* x, int64_t x_sN, const float* w, float scale, const float* bias, float* y, int32_t N, int32_t C,
+                      int32_t H, int32_t W, int32_t act, int32_t tanh_out, void* stream);
+
 /* ---- cost volume / warping -----------------------------------------------------------
  * ccvs_correlation7x7 replaces FunctionCorrelation(first, second, stride)
  * (modules/correlation.py:279-338,405-406; kernels :11-100) fused with the
@@ -425,6 +434,9 @@ int ccvs_pack_u8_norm(const float* vid, uint8_t* out, int64_t N, int32_t H, int3
  * tools/pytorch_metrics/metrics.py:24-25 get_psnr = piq.psnr(x, y, data_range=1., reduction='mean') (piq 0.5.4): per image
  * -10 log10(mean((x/R - y/R)^2) + 1e-8); out[N] fp32 (the caller takes the mean).  x, y: [N, per_image] fp32. */
 int ccvs_psnr(const float* x, const float* y, float* out, int64_t N, int64_t per_image, float data_range, void* stream);
+/* F.mse_loss(a, b) of stft_model.py:117 (eval_stft_reconstruction) and state_model.py:106 (eval_state_estimator): mean((a - b)^2)
+ * over n fp32 elements, differences and sums in float64, into out[1] fp32 on the device (no host synchronisation). */
+int ccvs_mse(const float* a, const float* b, float* out, int64_t n, void* stream);
 /* tools/pytorch_metrics/metrics.py:15-22 get_ssim = skimage.metrics.structural_similarity on every 2-D plane x[i, c], y[i, c]
  * with scikit-image 0.17.2's defaults: 7 x 7 uniform window, sample covariance, K1 = 0.01, K2 = 0.03, float64 arithmetic,
  * mean over the windows inside the plane; data_range is the caller's (the reference passes float planes and no data_range,
