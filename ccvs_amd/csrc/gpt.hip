@@ -697,40 +697,51 @@ static bool gemm_tile2() {
     return v;
 }
 
+// How a GEMM runs, as a function of its descriptor alone: the form (below), and into g the K slicing -- kz workgroups x ks waves --
+// that a row's rounding depends on.  launch_gemm16 and the phase table of the persistent decode step both take it from here.
+// Which kernel runs is a property of the CALL KIND, never of how many rows share the launch: the two forms partition K
+// differently (4 waves x kz slices and one accumulator chain vs 8 waves and two chains), so their low bits differ, and a
+// row must come out the same whether its batch is prefilled alone or stacked with the other batches of a token group
+// (B t0 <= 256 alone, G B t0 > 256 stacked).  Whole-sequence calls (prefill, teacher-forced forward, re-prefill of a slid
+// window: CCVS_GEMM_SEQ in the epilogue word, Tq > 1 for the QKV form) always take the row-blocked form; single-position
+// calls (decode steps) take the weight-stream form up to GEMM_DECODE_MAX_M rows and the row-blocked one beyond.
+// weight-stream form with one 16 x 16 block / 2 x 2 blocks per workgroup (the blocks' bits do not depend on the tile) | row-blocked | dense whole-sequence
+enum GemmForm { GEMM_FORM_TILE1, GEMM_FORM_TILE2, GEMM_FORM_RB, GEMM_FORM_SEQ };
+static GemmForm gemm16_plan(Gemm16& g) {
+    const bool decode_form = !g.seq && g.M <= GEMM_DECODE_MAX_M;
+    g.kz = decode_form ? gemm_kz(g) : 1;
+    if (g.kz > 1 && cdiv(g.N, 16) * cdiv(g.M, 16) > GEMM_WS_TILES) g.kz = 1;   // cannot happen for M <= 256 (kz > 1 needs <= 64 column tiles)
+    g.ks = decode_form ? GEMM_WAVES : 8;
+    while (g.ks > 1 && g.K % (16 * g.ks * g.kz) != 0) g.ks >>= 1;
+    // 2 x 2 blocks from three row blocks on (stacked batches): with two, N / 32 workgroups are too few alone (2.03 against 1.53 ms per step)
+    if (decode_form) return gemm_tile2() && g.M > 32 && g.N >= 32 ? GEMM_FORM_TILE2 : GEMM_FORM_TILE1;
+    static const int seq_dense = getenv_int("CCVS_GEMM_SEQ_DENSE", 1);   // 0 (a test hook: tests/gemm_seq_worker.py): the row-blocked weight-stream form of rounds 2-3
+    const bool fits = (long)g.M * g.ldx * 4 < (1L << 31) && (long)g.N * g.K * 4 < (1L << 31);   // (buffer descriptors: 32-bit byte offsets)
+    return g.seq && seq_dense && fits ? GEMM_FORM_SEQ : GEMM_FORM_RB;
+}
+
 static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
     if (!(g.x && g.w && g.y)) { ccvs_set_error("%s: null pointer", name); return CCVS_ERR_ARG; }
     if (!(g.M > 0 && g.N > 0 && g.K > 0)) { ccvs_set_error("%s: empty tensor", name); return CCVS_ERR_ARG; }
     if (g.K % 16 != 0 || g.ldx % 4 != 0) { ccvs_set_error("%s: K=%d must be a multiple of 16 (ldx %% 4 == 0)", name, g.K); return CCVS_ERR_ARG; }
     if (g.epi < 0 || g.epi > 2 || (g.epi == 2 && !g.res)) { ccvs_set_error("%s: bad epilogue", name); return CCVS_ERR_ARG; }
-    // Which kernel runs is a property of the CALL KIND, never of how many rows share the launch: the two forms partition K
-    // differently (4 waves x kz slices and one accumulator chain vs 8 waves and two chains), so their low bits differ, and a
-    // row must come out the same whether its batch is prefilled alone or stacked with the other batches of a token group
-    // (B t0 <= 256 alone, G B t0 > 256 stacked).  Whole-sequence calls (prefill, teacher-forced forward, re-prefill of a slid
-    // window: CCVS_GEMM_SEQ in the epilogue word, Tq > 1 for the QKV form) always take the row-blocked form; single-position
-    // calls (decode steps) take the weight-stream form up to GEMM_DECODE_MAX_M rows and the row-blocked one beyond.
-    const bool decode_form = !g.seq && g.M <= GEMM_DECODE_MAX_M;
+    const GemmForm form = gemm16_plan(g);
+    const bool decode_form = form == GEMM_FORM_TILE1 || form == GEMM_FORM_TILE2;
     if (decode_form && ((long)g.N * g.K * 4 >= (1L << 31) || (long)g.M * g.ldx * 4 >= (1L << 31))) {
         ccvs_set_error("%s: operand beyond 2^31 bytes (32-bit buffer offsets)", name);
         return CCVS_ERR_ARG;
     }
     if (!decode_form && g.grp_rows > 0) { ccvs_set_error("%s: row groups need M <= %d", name, GEMM_DECODE_MAX_M); return CCVS_ERR_ARG; }
-    g.kz = decode_form ? gemm_kz(g) : 1;
-    if (g.kz > 1 && cdiv(g.N, 16) * cdiv(g.M, 16) > GEMM_WS_TILES) g.kz = 1;   // cannot happen for M <= 256 (kz > 1 needs <= 64 column tiles)
-    g.ks = decode_form ? GEMM_WAVES : 8;
-    while (g.ks > 1 && g.K % (16 * g.ks * g.kz) != 0) g.ks >>= 1;
-    static const int seq_dense = getenv_int("CCVS_GEMM_SEQ_DENSE", 1);   // 0 (a test hook: tests/gemm_seq_worker.py): the row-blocked weight-stream form of rounds 2-3
-    if (!decode_form && g.seq && seq_dense && (long)g.M * g.ldx * 4 < (1L << 31) && (long)g.N * g.K * 4 < (1L << 31)) {   // (buffer descriptors: 32-bit byte offsets)
+    if (form == GEMM_FORM_SEQ) {
         const int rt = cdiv(g.M, GS_BM), ct = cdiv(g.N, GS_BM);
         hipLaunchKernelGGL(gemm_seq_kernel, dim3(rt * ct), dim3(256), 0, st, g, rt, ct);
-    } else if (!decode_form)
+    } else if (form == GEMM_FORM_RB)
         hipLaunchKernelGGL((gemm16_rb_kernel<4>), dim3(cdiv(g.N, 16), cdiv(g.M, 64), 1), dim3(512), 0, st, g);
     else {
-        // 2 x 2 blocks of 16 x 16 per workgroup once there are two row blocks (stacked batches) -- the blocks' bits do not depend on the tile
-        const bool t2 = gemm_tile2() && g.M > 32 && g.N >= 32;   // from three row blocks on: with two, N / 32 workgroups are too few alone (2.03 against 1.53 ms per step)
 #define GEMM16_LAUNCH(RBv, CBv, Uv)                                                                                                         \
     hipLaunchKernelGGL((gemm16_kernel<RBv, CBv, Uv>), dim3(cdiv(g.N, 16 * CBv), cdiv(g.M, 16 * RBv), g.kz), dim3(64 * GEMM_WAVES), 0, st, g.x, \
                        g.w, g.ldx, g.K, g.N, g.M, g.ks, g.kz, g)
-        if (t2) GEMM16_LAUNCH(2, 2, 1); else GEMM16_LAUNCH(1, 1, GEMM_U);
+        if (form == GEMM_FORM_TILE2) GEMM16_LAUNCH(2, 2, 1); else GEMM16_LAUNCH(1, 1, GEMM_U);
 #undef GEMM16_LAUNCH
     }
     CCVS_CHECK_LAUNCH(name);
@@ -1127,7 +1138,16 @@ __global__ __launch_bounds__(256) void attention_decode_kernel(const float* __re
     attention_decode_item<D, false>(q, q_sB, kc, vc, out, H, pos0, pos_dev, grp_rows, Tmax, scale, blockIdx.x, smem);
 }
 
-#define ATT_DECODE_LAUNCH(Dv, grid_, smem_, ...) hipLaunchKernelGGL((attention_decode_kernel<Dv>), grid_, dim3(256), smem_, st, __VA_ARGS__)
+// one workgroup per (batch row, head), `smem` bytes of LDS for the scores; the caller checks the launch under its own name
+static void launch_attention_decode(int D, int n_bh, size_t smem, hipStream_t st, const float* q, long q_sB, const float* kc, const float* vc,
+                                    float* out, int H, int pos0, const int32_t* pos_dev, int grp_rows, int Tmax, float scale) {
+#define ATT_DECODE_LAUNCH(Dv) \
+    hipLaunchKernelGGL((attention_decode_kernel<Dv>), dim3((unsigned)n_bh), dim3(256), smem, st, q, q_sB, kc, vc, out, H, pos0, pos_dev, grp_rows, Tmax, scale)
+    if (D == 64) ATT_DECODE_LAUNCH(64);
+    else if (D == 32) ATT_DECODE_LAUNCH(32);
+    else ATT_DECODE_LAUNCH(16);
+#undef ATT_DECODE_LAUNCH
+}
 
 extern "C" int ccvs_attention(const float* q, int64_t q_sB, int64_t ldq, const float* kcache, const float* vcache, float* out, int32_t B,
                               int32_t H, int32_t Tq, int32_t pos0, const int32_t* pos_dev, int32_t Tmax, int32_t D, void* stream) {
@@ -1142,10 +1162,7 @@ extern "C" int ccvs_attention(const float* q, int64_t q_sB, int64_t ldq, const f
     if (Tq == 1) {
         const size_t smem = (size_t)(16 + 4 * 256 + maxL) * sizeof(float);
         CCVS_REQUIRE(smem <= 64 * 1024, "ccvs_attention: sequence too long for the LDS score buffer");
-        const dim3 grid((unsigned)(B * H));
-        if (D == 64) ATT_DECODE_LAUNCH(64, grid, smem, q, (long)q_sB, kcache, vcache, out, H, pos0, pos_dev, 0, Tmax, scale);
-        else if (D == 32) ATT_DECODE_LAUNCH(32, grid, smem, q, (long)q_sB, kcache, vcache, out, H, pos0, pos_dev, 0, Tmax, scale);
-        else ATT_DECODE_LAUNCH(16, grid, smem, q, (long)q_sB, kcache, vcache, out, H, pos0, pos_dev, 0, Tmax, scale);
+        launch_attention_decode(D, B * H, smem, st, q, (long)q_sB, kcache, vcache, out, H, pos0, pos_dev, 0, Tmax, scale);
     } else {
         const dim3 grid((unsigned)(B * H), (unsigned)cdiv(Tq, 128));
         if (D == 64) hipLaunchKernelGGL((attention_prefill_kernel<64>), grid, dim3(256), 0, st, q, (long)q_sB, (long)ldq, kcache, vcache, out, H, Tq, pos0, pos_dev, Tmax, scale);
@@ -1330,17 +1347,21 @@ __global__ __launch_bounds__(256) void sample_topk_kernel(const float* __restric
 }
 
 #define PICK_SMEM_WORDS(V) ((V) + 16 + 256)
+// the pick keeps a row's logits in dynamic LDS: up to 160 KB, allowed once per process
+static void pick_allow_big_lds() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)sample_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+}
 
 extern "C" int ccvs_sample_topk(const float* logits, int64_t ld, const float* noise, int64_t* out, int64_t out_stride, int32_t B, int32_t V,
                                 int32_t top_k, float temperature, void* stream) {
     CCVS_REQUIRE(logits && out, "ccvs_sample_topk: null pointer");
     CCVS_REQUIRE(B > 0 && V > 0 && temperature > 0.f, "ccvs_sample_topk: bad arguments");
     const size_t smem = (size_t)PICK_SMEM_WORDS(V) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sample_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    pick_allow_big_lds();
     CCVS_REQUIRE(smem <= 160 * 1024, "ccvs_sample_topk: vocabulary %d too large", V);
     hipLaunchKernelGGL(sample_topk_kernel, dim3(B), dim3(256), smem, (hipStream_t)stream, logits, (long)ld, noise, out, (long)out_stride, V,
                        top_k, temperature, Advance{});
@@ -1354,11 +1375,7 @@ extern "C" int ccvs_sample_topk_philox(const float* logits, int64_t ld, int64_t*
     CCVS_REQUIRE(logits && out, "ccvs_sample_topk_philox: null pointer");
     CCVS_REQUIRE(B > 0 && V > 0 && temperature > 0.f, "ccvs_sample_topk_philox: bad arguments");
     const size_t smem = (size_t)PICK_SMEM_WORDS(V) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sample_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    pick_allow_big_lds();
     CCVS_REQUIRE(smem <= 160 * 1024, "ccvs_sample_topk_philox: vocabulary %d too large", V);
     Advance adv = {};
     adv.rng = 2;
@@ -1699,17 +1716,81 @@ static int step_check(const ccvs_gpt_decode* d, const char* who) {
     return CCVS_OK;
 }
 
-// The phase table of d's persistent step, written to d->program (device memory): the Gemm16 of every launch of the chain, K slicing
-// exactly as launch_gemm16 decides it.  A synchronous copy on `stream`: once per descriptor, outside graph capture.
+// rows per group of a grouped step; 0: one group (widx / len / state are single words)
+static int step_grp_rows(const ccvs_gpt_decode* d) { return d->groups > 1 ? d->B / d->groups : 0; }
+
+// the bookkeeping block of the step's pick
+static Advance step_advance(const ccvs_gpt_decode* d, int grp_rows) {
+    Advance adv = {};
+    adv.codes = d->codes; adv.codes_sB = (long)d->codes_sB; adv.widx = d->widx; adv.len = d->len;
+    adv.rng = (d->rng && !d->noise && !d->noise_stream) ? 1 : 0; adv.state = d->state; adv.grp_rows = grp_rows;
+    adv.noise_stream = d->noise ? nullptr : d->noise_stream;
+    return adv;
+}
+
+// ln_f + head, the step's last GEMM
+static Gemm16 step_head_gemm(const ccvs_gpt_decode* d) {
+    Gemm16 g = {};
+    g.x = d->x; g.ldx = d->C; g.w = d->head_w; g.bias = d->head_b; g.y = d->logits; g.ldy = d->V; g.M = d->B; g.N = d->V; g.K = d->C;
+    g.ln_s = d->head_s; g.ln_eps = d->ln_eps;
+    return g;
+}
+
+// The tile of the persistent kernel's GEMM phases: the one gemm16_plan gives the step's last GEMM.  ccvs_gpt_decode_prepare checks that
+// every GEMM phase of the table plans to it (they all have d->B rows and, by step_check, >= 32 columns).
+static bool step_tile2(const ccvs_gpt_decode* d) {
+    Gemm16 g = step_head_gemm(d);
+    return gemm16_plan(g) == GEMM_FORM_TILE2;
+}
+
+// The step of d between its embedding and its pick, phase by phase in execution order: per layer ln1+QKV+scatter | attention | proj+res |
+// ln2+fc+GELU | fc2+res, then ln_f+head.  BOTH forms of the step are produced by this one walk: the launch chain launches each phase,
+// ccvs_gpt_decode_prepare plans it (gemm16_plan) and stores it in the persistent step's table.  visit(kind, g, name): `g` the phase's
+// descriptor (STEP_ATTENTION: x = q, y = att, kcache / vcache, H, Tmax, M = rows), `name` its launch name in error texts; a result
+// other than CCVS_OK ends the walk and is returned.  `who` names the caller in the layers' null-pointer check.
+template <typename Visit>
+static int step_phases(const ccvs_gpt_decode* d, const char* who, Visit visit) {
+    const int D = d->C / d->H, grp_rows = step_grp_rows(d);
+    float* ws_slabs = (float*)d->workspace;
+    int* ws_count = d->workspace ? (int*)((char*)d->workspace + GEMM_WS_SLAB_BYTES) : nullptr;
+    int rc;
+    for (int l = 0; l < d->n_layer; ++l) {
+        const ccvs_gpt_layer& L = d->layers[l];
+        CCVS_REQUIRE(L.qkv_w && L.qkv_b && L.qkv_s && L.proj_w && L.proj_b && L.fc_w && L.fc_b && L.fc_s && L.fc2_w && L.fc2_b && L.kcache && L.vcache,
+                     "%s: null pointer in layer %d", who, l);
+        Gemm16 g = {};  // ln1 + QKV + cache scatter
+        g.x = d->x; g.ldx = d->C; g.w = L.qkv_w; g.bias = L.qkv_b; g.y = d->q; g.ldy = d->C; g.M = d->B; g.N = 3 * d->C; g.K = d->C;
+        g.ln_s = L.qkv_s; g.ln_eps = d->ln_eps;
+        g.kcache = L.kcache; g.vcache = L.vcache; g.C = d->C; g.H = d->H; g.D = D; g.Tq = 1; g.Tmax = d->Tmax; g.pos0 = 0; g.pos_dev = d->len; g.grp_rows = grp_rows;
+        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(qkv)")) != CCVS_OK) return rc;
+        g = Gemm16{};  // attention over the cache
+        g.x = d->q; g.ldx = d->C; g.y = d->att; g.kcache = L.kcache; g.vcache = L.vcache; g.H = d->H; g.M = d->B; g.Tmax = d->Tmax;
+        g.pos_dev = d->len; g.grp_rows = grp_rows;
+        if ((rc = visit(STEP_ATTENTION, g, "ccvs_gpt_decode_step(attention)")) != CCVS_OK) return rc;
+        g = Gemm16{};  // proj + residual (in place on x)
+        g.x = d->att; g.ldx = d->C; g.w = L.proj_w; g.bias = L.proj_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->C; g.epi = 2;
+        g.ws_slabs = ws_slabs; g.ws_count = ws_count;
+        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(proj)")) != CCVS_OK) return rc;
+        g = Gemm16{};  // ln2 + fc + GELU
+        g.x = d->x; g.ldx = d->C; g.w = L.fc_w; g.bias = L.fc_b; g.y = d->h; g.ldy = d->F; g.M = d->B; g.N = d->F; g.K = d->C; g.epi = 1;
+        g.ln_s = L.fc_s; g.ln_eps = d->ln_eps;
+        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(fc)")) != CCVS_OK) return rc;
+        g = Gemm16{};  // fc2 + residual (in place on x)
+        g.x = d->h; g.ldx = d->F; g.w = L.fc2_w; g.bias = L.fc2_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->F; g.epi = 2;
+        g.ws_slabs = ws_slabs; g.ws_count = ws_count;
+        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(fc2)")) != CCVS_OK) return rc;
+    }
+    Gemm16 g = step_head_gemm(d);
+    return visit(STEP_GEMM, g, "ccvs_gpt_decode_step(head)");
+}
+
+// The phase table of d's persistent step, written to d->program (device memory): the phases of step_phases, each GEMM planned by
+// gemm16_plan -- the walk and the plan that the launch chain runs.  A synchronous copy on `stream`: once per descriptor, outside graph capture.
 extern "C" int ccvs_gpt_decode_prepare(const ccvs_gpt_decode* d, void* stream) {
     CCVS_REQUIRE(d && d->layers && d->n_layer > 0 && d->C > 0 && d->H > 0 && d->C % d->H == 0, "ccvs_gpt_decode_prepare: bad descriptor");
     int rc = step_check(d, "ccvs_gpt_decode_prepare");
     if (rc != CCVS_OK) return rc;
-    const int D = d->C / d->H;
-    const int grp_rows = d->groups > 1 ? d->B / d->groups : 0;
-    float* ws_slabs = (float*)d->workspace;
-    int* ws_count = (int*)((char*)d->workspace + GEMM_WS_SLAB_BYTES);
-    const int n_ph = 5 * d->n_layer + 1;
+    const int grp_rows = step_grp_rows(d), n_ph = 5 * d->n_layer + 1;
     const size_t bytes = (size_t)ccvs_gpt_program_bytes(d->n_layer);
     char* host = (char*)calloc(1, bytes);
     CCVS_REQUIRE(host, "ccvs_gpt_decode_prepare: out of host memory");
@@ -1720,64 +1801,22 @@ extern "C" int ccvs_gpt_decode_prepare(const ccvs_gpt_decode* d, void* stream) {
         a.tok_emb = d->tok_emb; a.pos_table = d->pos_table; a.tok = d->tok; a.len = d->len; a.x = d->x; a.logits = d->logits;
         a.bar = (StepBar*)((char*)d->workspace + GEMM_WS_BAR_OFFSET);
         a.prog = (const StepPhase*)((const char*)d->program + STEP_HEAD_BYTES);
-        a.scale = 1.0f / sqrtf((float)D);
+        a.scale = 1.0f / sqrtf((float)(d->C / d->H));
         a.noise = d->noise; a.top_k = d->top_k; a.temperature = d->temperature;
-        a.adv.codes = d->codes; a.adv.codes_sB = (long)d->codes_sB; a.adv.widx = d->widx; a.adv.len = d->len;
-        a.adv.rng = (d->rng && !d->noise && !d->noise_stream) ? 1 : 0; a.adv.state = d->state; a.adv.grp_rows = grp_rows;
-        a.adv.noise_stream = d->noise ? nullptr : d->noise_stream;
+        a.adv = step_advance(d, grp_rows);
     }
-    auto slice = [&](Gemm16& g) {
-        g.kz = gemm_kz(g);
-        if (g.kz > 1 && cdiv(g.N, 16) * cdiv(g.M, 16) > GEMM_WS_TILES) g.kz = 1;
-        g.ks = GEMM_WAVES;
-        while (g.ks > 1 && g.K % (16 * g.ks * g.kz) != 0) g.ks >>= 1;
-    };
+    // The kernel runs ONE tile (step_tile2) for all its GEMM phases and the table has n_ph slots: a walk or a plan that disagrees with
+    // either is a bug in this file, never a caller's error -- reported all the same, before anything is written to d->program.
+    const GemmForm tile = step_tile2(d) ? GEMM_FORM_TILE2 : GEMM_FORM_TILE1;
     int n = 0;
-    for (int l = 0; l < d->n_layer; ++l) {
-        const ccvs_gpt_layer& L = d->layers[l];
-        if (!(L.qkv_w && L.qkv_b && L.qkv_s && L.proj_w && L.proj_b && L.fc_w && L.fc_b && L.fc_s && L.fc2_w && L.fc2_b && L.kcache && L.vcache)) {
-            free(host);
-            ccvs_set_error("ccvs_gpt_decode_prepare: null pointer in layer %d", l);
-            return CCVS_ERR_ARG;
-        }
-        {   // ln1 + QKV + cache scatter
-            Gemm16& g = prog[n].g; prog[n++].kind = STEP_GEMM;
-            g.x = d->x; g.ldx = d->C; g.w = L.qkv_w; g.bias = L.qkv_b; g.y = d->q; g.ldy = d->C; g.M = d->B; g.N = 3 * d->C; g.K = d->C;
-            g.ln_s = L.qkv_s; g.ln_eps = d->ln_eps;
-            g.kcache = L.kcache; g.vcache = L.vcache; g.C = d->C; g.H = d->H; g.D = D; g.Tq = 1; g.Tmax = d->Tmax; g.pos0 = 0; g.pos_dev = d->len;
-            g.grp_rows = grp_rows;
-            slice(g);
-        }
-        {   // attention over the cache
-            Gemm16& g = prog[n].g; prog[n++].kind = STEP_ATTENTION;
-            g.x = d->q; g.ldx = d->C; g.y = d->att; g.kcache = L.kcache; g.vcache = L.vcache; g.H = d->H; g.M = d->B; g.Tmax = d->Tmax;
-            g.pos_dev = d->len; g.grp_rows = grp_rows;
-        }
-        {   // proj + residual (in place on x)
-            Gemm16& g = prog[n].g; prog[n++].kind = STEP_GEMM;
-            g.x = d->att; g.ldx = d->C; g.w = L.proj_w; g.bias = L.proj_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->C; g.epi = 2;
-            g.ws_slabs = ws_slabs; g.ws_count = ws_count;
-            slice(g);
-        }
-        {   // ln2 + fc + GELU
-            Gemm16& g = prog[n].g; prog[n++].kind = STEP_GEMM;
-            g.x = d->x; g.ldx = d->C; g.w = L.fc_w; g.bias = L.fc_b; g.y = d->h; g.ldy = d->F; g.M = d->B; g.N = d->F; g.K = d->C; g.epi = 1;
-            g.ln_s = L.fc_s; g.ln_eps = d->ln_eps;
-            slice(g);
-        }
-        {   // fc2 + residual (in place on x)
-            Gemm16& g = prog[n].g; prog[n++].kind = STEP_GEMM;
-            g.x = d->h; g.ldx = d->F; g.w = L.fc2_w; g.bias = L.fc2_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->F; g.epi = 2;
-            g.ws_slabs = ws_slabs; g.ws_count = ws_count;
-            slice(g);
-        }
-    }
-    {   // ln_f + head
-        Gemm16& g = prog[n].g; prog[n++].kind = STEP_GEMM;
-        g.x = d->x; g.ldx = d->C; g.w = d->head_w; g.bias = d->head_b; g.y = d->logits; g.ldy = d->V; g.M = d->B; g.N = d->V; g.K = d->C;
-        g.ln_s = d->head_s; g.ln_eps = d->ln_eps;
-        slice(g);
-    }
+    rc = step_phases(d, "ccvs_gpt_decode_prepare", [&](int kind, Gemm16& g, const char* name) -> int {
+        if (n == n_ph || (kind == STEP_GEMM && gemm16_plan(g) != tile)) { ccvs_set_error("ccvs_gpt_decode_prepare: %s does not fit the persistent step's table", name); return CCVS_ERR_ARG; }
+        prog[n].kind = kind;
+        prog[n++].g = g;
+        return CCVS_OK;
+    });
+    if (rc == CCVS_OK && n != n_ph) { ccvs_set_error("ccvs_gpt_decode_prepare: %d phases, the table holds %d", n, n_ph); rc = CCVS_ERR_ARG; }
+    if (rc != CCVS_OK) { free(host); return rc; }
     hipError_t e = hipMemcpyAsync(d->program, host, bytes, hipMemcpyHostToDevice, (hipStream_t)stream);
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     free(host);
@@ -1796,7 +1835,7 @@ static int launch_step_persistent(const ccvs_gpt_decode* d, int D, hipStream_t s
     const StepArgs* a = (const StepArgs*)d->program;   // written by ccvs_gpt_decode_prepare
     // one workgroup per CU: more of them are all resident only with the chip to the step itself -- beside the frame decoder a CU has
     // room for one -- and every grid barrier then waits for 2-4 x the arrivals (profiles/r06_persistent_step.txt)
-    const bool t2 = d->B > 32;
+    const bool t2 = step_tile2(d);
     size_t words = t2 ? STEP_GEMM_WORDS(2, 2) : STEP_GEMM_WORDS(1, 1);
     const size_t w_att = 16 + 4 * 256 + (size_t)d->Tmax, w_pick = PICK_SMEM_WORDS(d->V);
     if (w_att > words) words = w_att;
@@ -1836,7 +1875,7 @@ extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
     CCVS_REQUIRE(d->groups >= 0 && (d->groups <= 1 || d->B % d->groups == 0), "ccvs_gpt_decode_step: %d rows do not split into %d groups", d->B, d->groups);
     // (more rows than the weight-stream form takes run the row-blocked form inside launch_gemm16; row groups cannot)
     CCVS_REQUIRE(d->groups <= 1 || d->B <= GEMM_DECODE_MAX_M, "ccvs_gpt_decode_step: at most %d rows per grouped step", GEMM_DECODE_MAX_M);
-    const int grp_rows = d->groups > 1 ? d->B / d->groups : 0;   // 0: one group (widx / len / state are single words)
+    const int grp_rows = step_grp_rows(d);
     const size_t smem_att = (size_t)(16 + 4 * 256 + d->Tmax) * sizeof(float);
     const size_t smem_pick = (size_t)PICK_SMEM_WORDS(d->V) * sizeof(float);
     CCVS_REQUIRE(smem_att <= 64 * 1024, "ccvs_gpt_decode_step: sequence too long for the LDS score buffer");
@@ -1847,11 +1886,7 @@ extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
         if (rc_ != CCVS_OK) return rc_;
         return launch_step_persistent(d, D, st);
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)sample_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
+    pick_allow_big_lds();
 
     {   // embedding of the last picked token at row pos_off + *len
         const long total = (long)d->B * d->C;
@@ -1859,54 +1894,17 @@ extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
                            (const int32_t*)d->len, grp_rows, 1, d->tok_emb, d->pos_table, d->x, total, d->C, d->vocab);
         CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(embed)");
     }
-    float* ws_slabs = (float*)d->workspace;
-    int* ws_count = d->workspace ? (int*)((char*)d->workspace + GEMM_WS_SLAB_BYTES) : nullptr;
     const float scale = 1.0f / sqrtf((float)D);
-    int rc;
-    for (int l = 0; l < d->n_layer; ++l) {
-        const ccvs_gpt_layer& L = d->layers[l];
-        CCVS_REQUIRE(L.qkv_w && L.qkv_b && L.qkv_s && L.proj_w && L.proj_b && L.fc_w && L.fc_b && L.fc_s && L.fc2_w && L.fc2_b && L.kcache && L.vcache,
-                     "ccvs_gpt_decode_step: null pointer in layer %d", l);
-        Gemm16 g = {};  // ln1 + QKV + cache scatter
-        g.x = d->x; g.ldx = d->C; g.w = L.qkv_w; g.bias = L.qkv_b; g.y = d->q; g.ldy = d->C; g.M = d->B; g.N = 3 * d->C; g.K = d->C;
-        g.ln_s = L.qkv_s; g.ln_eps = d->ln_eps;
-        g.kcache = L.kcache; g.vcache = L.vcache; g.C = d->C; g.H = d->H; g.D = D; g.Tq = 1; g.Tmax = d->Tmax; g.pos0 = 0; g.pos_dev = d->len;
-        g.grp_rows = grp_rows;
-        if ((rc = launch_gemm16(g, st, "ccvs_gpt_decode_step(qkv)")) != CCVS_OK) return rc;
-        {   // attention over the cache
-            const dim3 grid((unsigned)(d->B * d->H));
-            if (D == 64) ATT_DECODE_LAUNCH(64, grid, smem_att, d->q, (long)d->C, L.kcache, L.vcache, d->att, d->H, 0, (const int32_t*)d->len, grp_rows, d->Tmax, scale);
-            else if (D == 32) ATT_DECODE_LAUNCH(32, grid, smem_att, d->q, (long)d->C, L.kcache, L.vcache, d->att, d->H, 0, (const int32_t*)d->len, grp_rows, d->Tmax, scale);
-            else ATT_DECODE_LAUNCH(16, grid, smem_att, d->q, (long)d->C, L.kcache, L.vcache, d->att, d->H, 0, (const int32_t*)d->len, grp_rows, d->Tmax, scale);
-            CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(attention)");
-        }
-        g = Gemm16{};  // proj + residual (in place on x)
-        g.x = d->att; g.ldx = d->C; g.w = L.proj_w; g.bias = L.proj_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->C; g.epi = 2;
-        g.ws_slabs = ws_slabs; g.ws_count = ws_count;
-        if ((rc = launch_gemm16(g, st, "ccvs_gpt_decode_step(proj)")) != CCVS_OK) return rc;
-        g = Gemm16{};  // ln2 + fc + GELU
-        g.x = d->x; g.ldx = d->C; g.w = L.fc_w; g.bias = L.fc_b; g.y = d->h; g.ldy = d->F; g.M = d->B; g.N = d->F; g.K = d->C; g.epi = 1;
-        g.ln_s = L.fc_s; g.ln_eps = d->ln_eps;
-        if ((rc = launch_gemm16(g, st, "ccvs_gpt_decode_step(fc)")) != CCVS_OK) return rc;
-        g = Gemm16{};  // fc2 + residual (in place on x)
-        g.x = d->h; g.ldx = d->F; g.w = L.fc2_w; g.bias = L.fc2_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->F; g.epi = 2;
-        g.ws_slabs = ws_slabs; g.ws_count = ws_count;
-        if ((rc = launch_gemm16(g, st, "ccvs_gpt_decode_step(fc2)")) != CCVS_OK) return rc;
-    }
-    {   // ln_f + head
-        Gemm16 g = {};
-        g.x = d->x; g.ldx = d->C; g.w = d->head_w; g.bias = d->head_b; g.y = d->logits; g.ldy = d->V; g.M = d->B; g.N = d->V; g.K = d->C;
-        g.ln_s = d->head_s; g.ln_eps = d->ln_eps;
-        if ((rc = launch_gemm16(g, st, "ccvs_gpt_decode_step(head)")) != CCVS_OK) return rc;
-    }
-    {   // pick + bookkeeping
-        Advance adv = {};
-        adv.codes = d->codes; adv.codes_sB = (long)d->codes_sB; adv.widx = d->widx; adv.len = d->len;
-        adv.rng = (d->rng && !d->noise && !d->noise_stream) ? 1 : 0; adv.state = d->state; adv.grp_rows = grp_rows;
-        adv.noise_stream = d->noise ? nullptr : d->noise_stream;
-        hipLaunchKernelGGL(sample_topk_kernel, dim3(d->B), dim3(256), smem_pick, st, d->logits, (long)d->V, d->noise, d->tok, 1L, d->V,
-                           d->top_k, d->temperature, adv);
-        CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(pick)");
-    }
+    const int rc = step_phases(d, "ccvs_gpt_decode_step", [&](int kind, Gemm16& g, const char* name) -> int {
+        if (kind == STEP_GEMM) return launch_gemm16(g, st, name);
+        launch_attention_decode(D, g.M * g.H, smem_att, st, g.x, g.ldx, g.kcache, g.vcache, g.y, g.H, 0, g.pos_dev, g.grp_rows, g.Tmax, scale);
+        CCVS_CHECK_LAUNCH(name);
+        return CCVS_OK;
+    });
+    if (rc != CCVS_OK) return rc;
+    // pick + bookkeeping
+    hipLaunchKernelGGL(sample_topk_kernel, dim3(d->B), dim3(256), smem_pick, st, d->logits, (long)d->V, d->noise, d->tok, 1L, d->V,
+                       d->top_k, d->temperature, step_advance(d, grp_rows));
+    CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(pick)");
     return CCVS_OK;
 }
