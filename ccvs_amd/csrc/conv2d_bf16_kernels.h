@@ -16,43 +16,20 @@
 #pragma once
 #include "common.h"
 #include "conv_common.h"
+#include "conv2d_bf16_core.h"   // what this file's producer / consumer kernel shares with the persistent-tiles kernel (conv2d_bf16_pt.h)
 #include <stdlib.h>
 #include <stdio.h>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-// the 16-byte stores of the epilogues
-__device__ __forceinline__ void cb_store16(void* dst, f32x4 v) { *reinterpret_cast<f32x4*>(dst) = v; }
-__device__ __forceinline__ void cb_store16(void* dst, uint4 v) { cb_store16(dst, f32x4{__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)}); }
 
 #define CB_CC 16      // input channels per chunk = one MFMA K step
 #define CB_MAX_E 5
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void glb_void;
 
 // source of halo pixels outside the image when a packed (P8) activation tile is staged by LDS-DMA
 static __device__ uint4 g_conv_zero16 = {0u, 0u, 0u, 0u};
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// two floats -> two bf16 (round to nearest even) in one v_cvt_pk_bf16_f32; element 0 in the low half
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-
-// 8 floats -> 8 bf16 hi (uint4) + 8 bf16 lo (uint4),  v = hi + lo + O(2^-17 |v|)
-__device__ __forceinline__ void split8(const float (&v)[8], uint4& hi, uint4& lo) {
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = pk_bf16(v[2 * i], v[2 * i + 1]);
-        l[i] = pk_bf16(v[2 * i] - __uint_as_float(h[i] << 16), v[2 * i + 1] - __uint_as_float(h[i] & 0xffff0000u));
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
 
 // Stage `n_iter`-strided elements of one 16-channel chunk of the input halo tile: NCHW fp32 ->
 // [half][hi|lo][pixel][8 bf16].  Loads are unconditional from clamped addresses (a predicated load
@@ -313,6 +290,7 @@ __global__ __launch_bounds__(64 * NW) void conv2d_bf16x3_kernel(ConvK p, const u
 // ONE workgroup -- timing ablations: 14.5 us of the 36 us a 49->128 tile takes, 40 % -- so layers with few input channels
 // per output byte gain from a second resident workgroup whose K loop runs meanwhile, although its activations are then
 // staged once per 64 output channels instead of once per 128.
+#define CB_PC_OFF(tb) (xd0 + (tb) * xdd)   // LDS offset of tap column tb of a tap row: the row's tap table (ax)
 template <int TW, int MB, int NTY, int PP = 2, int WPC = 1>
 __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) void conv2d_bf16x3_pc_kernel(ConvK p, const uint4* __restrict__ wsplit, int CinG, int ntx_max) {
     static_assert(WPC == 1 || (WPC == 2 && MB == 2 && PP == 2 && NTY == 3), "two workgroups per CU: the 64-channel 3 x 3 form only");
@@ -681,7 +659,7 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
 #pragma unroll
             for (int a = 0; a < NTYc; ++a) {
                 if (a > 0 && ktail && ci == nchunks - 1) break;   // the packed tail chunk is one step
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                CB_LDS_BARRIER();
             }
             if (ci + 1 >= nchunks) break;
             // set 1 holds chunk ci + 2
@@ -691,7 +669,7 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
 #pragma unroll
             for (int a = 0; a < NTYc; ++a) {
                 if (a > 0 && ktail && ci + 1 == nchunks - 1) break;
-                asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                CB_LDS_BARRIER();
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the trailing (never stored) requests
@@ -731,59 +709,22 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
             const uint4* it0 = in_buf + (ci & 1) * in_sz + (khalf * 2) * plane + (ay.d0 + a * ay.dd - ay.lo) * IWS;
             const uint4* wt0 = w_buf + (s & 1) * w_sz + (khalf * 2) * NT + (lane & 31);
             if constexpr (PP == 4) {
-                // Four pixel blocks of a tap stay in registers (fq); the weight fragments of the tap's MB output-channel blocks
-                // sit in one of two sets (fw): the next tap's are read above the current tap's 12 MB MFMAs (the tap loop is
-                // unrolled by two so that the sets stay statically indexed).  There is no second set for the pixels: in the
-                // pass over the LAST channel block each pixel block is re-read for the next tap right after its last MFMA --
-                // 9 to 0 MFMAs before the next tap needs it, the earliest-needed block first.
+                // the 512-pixel tap (CB_TAP4, conv2d_bf16_core.h): four pixel blocks held in registers, the weight sets alternating
                 const int ntx = ax.nt, xd0 = ax.d0 - ax.lo, xdd = ax.dd;
                 bf16x8 fq[4][2], fw[2][MB][2];
-#pragma unroll
-                for (int pp = 0; pp < 4; ++pp) {
-                    fq[pp][0] = __builtin_bit_cast(bf16x8, it0[xd0 + bofs[pp]]);
-                    fq[pp][1] = __builtin_bit_cast(bf16x8, it0[xd0 + plane + bofs[pp]]);
-                }
-#pragma unroll
-                for (int m = 0; m < MB; ++m) {
-                    fw[0][m][0] = __builtin_bit_cast(bf16x8, wt0[m * 32]);
-                    fw[0][m][1] = __builtin_bit_cast(bf16x8, wt0[NT + m * 32]);
-                }
-#define CB_TAP4(CUR, tb, more)                                                                                         \
-    {                                                                                                                  \
-        const uint4* itn_ = it0 + (xd0 + ((tb) + 1) * xdd);                                                            \
-        if (more) {                                                                                                    \
-            const uint4* wtn_ = wt0 + ((tb) + 1) * 4 * NT;                                                             \
-            _Pragma("unroll") for (int m = 0; m < MB; ++m) {                                                           \
-                fw[(CUR) ^ 1][m][0] = __builtin_bit_cast(bf16x8, wtn_[m * 32]);                                        \
-                fw[(CUR) ^ 1][m][1] = __builtin_bit_cast(bf16x8, wtn_[NT + m * 32]);                                   \
-            }                                                                                                          \
-        }                                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        _Pragma("unroll") for (int m = 0; m < MB; ++m) {                                                               \
-            _Pragma("unroll") for (int pp = 0; pp < 4; ++pp) {                                                         \
-                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[CUR][m][1], fq[pp][0], acc[m][pp], 0, 0, 0);   \
-                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[CUR][m][0], fq[pp][1], acc[m][pp], 0, 0, 0);   \
-                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[CUR][m][0], fq[pp][0], acc[m][pp], 0, 0, 0);   \
-                if (m == MB - 1 && (more)) {                                                                           \
-                    fq[pp][0] = __builtin_bit_cast(bf16x8, itn_[bofs[pp]]);                                            \
-                    fq[pp][1] = __builtin_bit_cast(bf16x8, itn_[plane + bofs[pp]]);                                    \
-                }                                                                                                      \
-            }                                                                                                          \
-        }                                                                                                              \
-    }
-                if constexpr (TAP3) {   // (written out: see the 256-pixel form below)
-                    CB_TAP4(0, 0, true)
-                    CB_TAP4(1, 1, true)
-                    CB_TAP4(0, 2, false)
+                CB_TAP4_PRIME(CB_PC_OFF)
+                if constexpr (TAP3) {   // (written out: see CB_TAP, conv2d_bf16_core.h)
+                    CB_TAP4(0, 0, true, CB_PC_OFF)
+                    CB_TAP4(1, 1, true, CB_PC_OFF)
+                    CB_TAP4(0, 2, false, CB_PC_OFF)
                 } else {
                     int tb = 0;
                     for (; tb + 2 <= ntx; tb += 2) {
-                        CB_TAP4(0, tb, true)
-                        CB_TAP4(1, tb + 1, (tb + 2 < ntx))
+                        CB_TAP4(0, tb, true, CB_PC_OFF)
+                        CB_TAP4(1, tb + 1, (tb + 2 < ntx), CB_PC_OFF)
                     }
-                    if (tb < ntx) { CB_TAP4(0, tb, false) }
+                    if (tb < ntx) { CB_TAP4(0, tb, false, CB_PC_OFF) }
                 }
-#undef CB_TAP4
             } else if constexpr (WPC == 2) {
                 // two workgroups per CU: every SIMD hosts two MFMA waves, one of which computes while the other waits for its
                 // fragments -- plain reads (no second register set: the 128-VGPR budget), weights one block ahead
@@ -817,66 +758,24 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
                     }
                 }
             } else {
-            // Software-pipelined fragment reads: the ds_reads of the NEXT 32-cout block (and, on a tap's last block,
-            // of the next tap's pixels) are issued before the current block's 6 MFMAs, into the other register
-            // set -- hipcc does not do this by itself and the lone MFMA wave of a SIMD then idles a full LDS
-            // latency after every 6 MFMAs.  Taps are unrolled by two so both sets stay statically indexed.
+            // the 256-pixel tap (CB_LD_B / CB_LD_A / CB_TAP, conv2d_bf16_core.h): fragment reads software-pipelined by hand
             bf16x8 fa[2][2];     // [set][0 hi | 1 lo]       weights of one 32-cout block
             bf16x8 fb[2][2][2];  // [set][pp][0 hi | 1 lo]   the two pixel blocks of one tap
             const int ntx = ax.nt, xd0 = ax.d0 - ax.lo, xdd = ax.dd;
-#define CB_LD_B(SET, tb)                                                                        \
-    {                                                                                           \
-        const uint4* it_ = it0 + (xd0 + (tb) * xdd);                                            \
-        _Pragma("unroll") for (int pp = 0; pp < 2; ++pp) {                                      \
-            fb[SET][pp][0] = __builtin_bit_cast(bf16x8, it_[bofs[pp]]);                         \
-            fb[SET][pp][1] = __builtin_bit_cast(bf16x8, it_[plane + bofs[pp]]);                 \
-        }                                                                                       \
-    }
-#define CB_LD_A(SET, tb, m_)                                                                    \
-    {                                                                                           \
-        const uint4* wt_ = wt0 + (tb) * 4 * NT + (m_) * 32;                                     \
-        fa[SET][0] = __builtin_bit_cast(bf16x8, wt_[0]);                                        \
-        fa[SET][1] = __builtin_bit_cast(bf16x8, wt_[NT]);                                       \
-    }
-#define CB_TAP(BSET, A0, tb, has_next)                                                          \
-    _Pragma("unroll") for (int m = 0; m < MB; ++m) {                                            \
-        if (m + 1 < MB) {                                                                       \
-            CB_LD_A(((A0) + m + 1) & 1, tb, m + 1)                                              \
-        } else if (has_next) {                                                                  \
-            CB_LD_A(((A0) + m + 1) & 1, (tb) + 1, 0)                                            \
-            CB_LD_B((BSET) ^ 1, (tb) + 1)                                                       \
-        }                                                                                       \
-        __builtin_amdgcn_sched_barrier(0); /* keep the prefetch ABOVE the MFMAs it is meant to hide under */ \
-        _Pragma("unroll") for (int pp = 0; pp < 2; ++pp) {                                      \
-            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[((A0) + m) & 1][1], fb[BSET][pp][0], acc[m][pp], 0, 0, 0); \
-            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[((A0) + m) & 1][0], fb[BSET][pp][1], acc[m][pp], 0, 0, 0); \
-            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[((A0) + m) & 1][0], fb[BSET][pp][0], acc[m][pp], 0, 0, 0); \
-        }                                                                                       \
-    }
-            CB_LD_B(0, 0)
+            CB_LD_B(0, 0, CB_PC_OFF)
             CB_LD_A(0, 0, 0)
-            if constexpr (TAP3) {
-                // 3 x 3 kernels (three taps per row, known at compile time): the tap loop is written out, so that no
-                // run-time branch sits between the fragment reads and the MFMAs.  In the loop form hipcc's wait-count pass
-                // puts `s_waitcnt lgkmcnt(0)` directly behind every prefetch (`ds_read x2; s_waitcnt lgkmcnt(0); v_mfma x6`:
-                // it waits for the reads it has JUST issued); written out, the waits sit 4-6 MFMAs behind the reads
-                // (+1...+3 % per shape).  Hand-counted waits with the reads as asm statements were tried and are 2.4 x
-                // SLOWER: with an LDS-DMA in flight (the next step's weights) hipcc drains vmcnt in front of every asm
-                // statement that might touch LDS.
-                CB_TAP(0, 0, 0, true)
-                CB_TAP(1, (MB & 1), 1, true)
-                CB_TAP(0, 0, 2, false)
+            if constexpr (TAP3) {   // three taps per row, known at compile time: written out (why: at CB_TAP)
+                CB_TAP(0, 0, 0, true, CB_PC_OFF)
+                CB_TAP(1, (MB & 1), 1, true, CB_PC_OFF)
+                CB_TAP(0, 0, 2, false, CB_PC_OFF)
             } else {
                 int tb = 0;
                 for (; tb + 2 <= ntx; tb += 2) {
-                    CB_TAP(0, 0, tb, true)
-                    CB_TAP(1, (MB & 1), tb + 1, (tb + 2 < ntx))
+                    CB_TAP(0, 0, tb, true, CB_PC_OFF)
+                    CB_TAP(1, (MB & 1), tb + 1, (tb + 2 < ntx), CB_PC_OFF)
                 }
-                if (tb < ntx) { CB_TAP(0, 0, tb, false) }
+                if (tb < ntx) { CB_TAP(0, 0, tb, false, CB_PC_OFF) }
             }
-#undef CB_LD_B
-#undef CB_LD_A
-#undef CB_TAP
             }
         }
         __syncthreads();
@@ -884,57 +783,17 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
       }
       if constexpr (NTY == 3) {
         if (ktail) {
-            // Packed K tail: the last chunk holds r = Cin % 16 <= 3 real channels.  Its nine taps x r channels are contracted
-            // in ceil(9 r / 16) MFMA steps whose K index runs over (tap, channel): position q = 16 j + 8 khalf + i of step j
-            // is tap q / r, channel q % r.  The weights arrive in that order (tap slots 0 .. nj-1 of tap row 0 of the chunk,
-            // requested by the last iteration of the loop above); the pixel operand is gathered from the chunk's staged
-            // tile, 2 bytes per (tap, channel) -- once per tile, against 9 - nj tap steps of 6 MB MFMAs saved.  Outside the
-            // loop on purpose: inside it hipcc hoists the gather's address arithmetic over the whole loop and spills.
+            // packed K tail (CB_KTAIL, conv2d_bf16_core.h): the last chunk's nine taps x r channels in ceil(9 r / 16) steps; its weights
+            // were requested by the last iteration of the loop above.  Outside the loop on purpose (see there).
             const int s = nsteps - 1;
-            const int r_ = p.ktail, nq_ = 9 * r_, nj_ = (nq_ + 15) >> 4;
-            const unsigned short* ih = reinterpret_cast<const unsigned short*>(in_buf + ((nchunks - 1) & 1) * in_sz);
-            const uint4* wtl = w_buf + (s & 1) * w_sz + (khalf * 2) * NT + (lane & 31);
-            for (int j = 0; j < nj_; ++j) {
-                bf16x8 gb[PP][2];
-#pragma unroll
-                for (int pp = 0; pp < PP; ++pp) {
-                    unsigned hw[4], lw[4];
-#pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const int q = 16 * j + 8 * khalf + i;
-                        const int qc = min(q, nq_ - 1);
-                        const int t = qc / r_, c = qc - t * r_;
-                        const int tyy = t / 3, txx = t - 3 * tyy;
-                        const int e = (bofs[pp] + tyy * IWS + txx) * 8 + c;   // bf16 index inside the [pixel][8] plane
-                        unsigned hv = ih[e], lv = ih[plane * 8 + e];
-                        if (q >= nq_) { hv = 0; lv = 0; }
-                        if (i & 1) { hw[i >> 1] |= hv << 16; lw[i >> 1] |= lv << 16; }
-                        else { hw[i >> 1] = hv; lw[i >> 1] = lv; }
-                    }
-                    gb[pp][0] = __builtin_bit_cast(bf16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
-                    gb[pp][1] = __builtin_bit_cast(bf16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
-                }
-#pragma unroll
-                for (int m = 0; m < MB; ++m) {
-                    const bf16x8 ah = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + m * 32]);
-                    const bf16x8 al = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + NT + m * 32]);
-#pragma unroll
-                    for (int pp = 0; pp < PP; ++pp) {
-                        acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gb[pp][0], acc[m][pp], 0, 0, 0);
-                        acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][1], acc[m][pp], 0, 0, 0);
-                        acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][0], acc[m][pp], 0, 0, 0);
-                    }
-                }
-            }
+            CB_KTAIL(reinterpret_cast<const unsigned short*>(in_buf + ((nchunks - 1) & 1) * in_sz), w_buf + (s & 1) * w_sz + (khalf * 2) * NT + (lane & 31))
             __syncthreads();
         }
       }
     }
     // ---- epilogue ------------------------------------------------------------------------------
-    // Dense convolutions: the accumulators (one pixel column per lane, 16 couts in registers) go
-    // through LDS so that ALL 8 waves write 16-byte pieces along x (a lane then owns 4 consecutive
-    // pixels of one channel) instead of 128 scalar stores per consumer lane: the store tail was
-    // issue-bound.  32 couts x 256 pixels per pass, MB passes.
+    // Dense convolutions: the accumulators go through LDS (CB_STAGE_PASS, conv2d_bf16_core.h), then all 8 waves write 16-byte pieces
+    // along x.  32 couts x NPIX pixels per pass, MB passes.
     float* stage = reinterpret_cast<float*>(smem4);
     constexpr int NIT = (8 * NPIX + 255 + NP) / (256 + NP);   // 16-byte pieces of a 32-channel pass per thread
     constexpr bool LEANK = MB == 1 || WPC == 2;   // kernels capped at 128 registers: the fast path below or the plain piece-by-piece one
@@ -947,96 +806,24 @@ __global__ __launch_bounds__(512, ((MB == 1 && PP == 2) || WPC == 2) ? 4 : 2) vo
 #pragma unroll
     for (int m = 0; m < MB; ++m) {
         const bool p8_out = (PP == 2 || P8IN) && p.out_p8;
-        if (!producer) {
-            if (p8_out) {
-                // packed output: the pass is staged [pixel][32 channels] (36 floats apart: conflict-free 16-byte accesses) -- a
-                // lane writes its four groups of 4 consecutive channels as ds_write_b128, a reader fetches the 8 channels of its
-                // pixel as two ds_read_b128 (channel-major staging cost the packed epilogue 8 ds_read_b32 per item: the
-                // 128-channel producers ran 20 % slower than with fp32 output)
-#pragma unroll
-                for (int pp = 0; pp < PP; ++pp) {
-                    float* sp = stage + ((rw * PP + pp) * 32 + (lane & 31)) * 36 + 4 * khalf;
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 q4 = {acc[m][pp][4 * g], acc[m][pp][4 * g + 1], acc[m][pp][4 * g + 2], acc[m][pp][4 * g + 3]};
-                        *reinterpret_cast<f32x4*>(sp + 8 * g) = q4;
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int pp = 0; pp < PP; ++pp)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r)
-                        stage[((r & 3) + 8 * (r >> 2) + 4 * khalf) * NPIX + (rw * PP + pp) * 32 + (lane & 31)] = acc[m][pp][r];
-            }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: the previous pass's stores stay in flight
+        if (!producer) { CB_STAGE_PASS(acc[m], p8_out, rw, lane, khalf) }
+        CB_LDS_BARRIER();   // LDS only: the previous pass's stores stay in flight
         if (p8_out) {   // (the 512-pixel tile writes packed output only in its packed-input form)
-            // packed output: a thread takes one pixel x 8 output channels of the staged 32 x 256 block, applies the
-            // epilogue, splits to hi / lo and writes two 16-byte units (lanes = consecutive pixels: coalesced)
+            // the packed-output epilogue (CB_EPI_P8, conv2d_bf16_core.h) with its bounds guard and channel clamp: ragged tiles too
             uint4* y4 = reinterpret_cast<uint4*>(p.y);
             const int gout = (p.Cout + 7) >> 3;
             const long hw_out = (long)p.Hout * p.Wout;
-            // (bias from LDS; with a pre-activation image its values for all items are fetched first, WITHOUT one the code path holds
-            //  no vector-memory load at all: a load that is merely conditional still makes hipcc wait, vmcnt(0), where its value
-            //  would be used -- i.e. for the stores of the item before; see the fp32 epilogue below)
             constexpr int NI8 = 4 * NPIX / 512;   // (pixel, 8 channels) items of a 32-channel pass per thread
-#define CB_P8_ITEM(i)                                                                          \
-    const int item_ = tid + 512 * (i);                                                         \
-    const int gq_ = item_ / NPIX, px_ = item_ - gq_ * NPIX;                                    \
-    const int co0_ = n0 + m * 32 + gq_ * 8;                                                    \
-    const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                                      \
-    const int vy_ = ty * TH + prow_, vx_ = tx * TW + pcol_;                                    \
-    const bool ok_ = co0_ < p.Cout && vy_ < ay.V && vx_ < ax.V;                                \
-    const long opix_ = ok_ ? (long)vy_ * p.Wout + vx_ : 0;
-#define CB_P8_FINISH(PRE)                                                                      \
-_Pragma("unroll") for (int i = 0; i < NI8; ++i) {                                              \
-    CB_P8_ITEM(i)                                                                              \
-    if (ok_) {                                                                                 \
-        float v[8];                                                                            \
-        const f32x4 s0 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8);          \
-        const f32x4 s1 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8 + 4);      \
-        _Pragma("unroll") for (int c = 0; c < 8; ++c) {                                        \
-            float t = c < 4 ? s0[c] : s1[c - 4];                                               \
-            t += (PRE);                                                                        \
-            t += bias_s[m * 32 + gq_ * 8 + c];                                                 \
-            if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                       \
-            v[c] = t * p.out_scale;                                                            \
-        }                                                                                      \
-        uint4 hi, lo;                                                                          \
-        split8(v, hi, lo);                                                                     \
-        uint4* dst = y4 + ((long)n * gout + (co0_ >> 3)) * 2 * hw_out + opix_;                 \
-        cb_store16(dst, hi);                                                                   \
-        cb_store16(dst + hw_out, lo);                                                          \
-    }                                                                                          \
-}
-            if (p.pre) {
-                float pv[NI8][8];
-                const float* pb = p.pre + (long)(n / p.pre_div) * p.pre_sN;
-#pragma unroll
-                for (int i = 0; i < NI8; ++i) {
-                    CB_P8_ITEM(i)
-#pragma unroll
-                    for (int c = 0; c < 8; ++c) pv[i][c] = pb[(long)min(co0_ + c, p.Cout - 1) * p.pre_sC + opix_];
-                }
-                CB_P8_FINISH(pv[i][c])
-            } else {
-                CB_P8_FINISH(0.f)
-            }
-#undef CB_P8_ITEM
-#undef CB_P8_FINISH
-            if (m + 1 < MB) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#define CB_PC_CLAMP(c) min((c), p.Cout - 1)
+            CB_EPI_P8(tid, (co0_ < p.Cout && vy_ < ay.V && vx_ < ax.V), (ok_ ? (long)vy_ * p.Wout + vx_ : 0), CB_PC_CLAMP, bias_s[m * 32 + gq_ * 8 + c])
+#undef CB_PC_CLAMP
+            if (m + 1 < MB) CB_LDS_BARRIER();
             continue;
         }
         if constexpr (P8IN && PP == 4) {   // this instantiation writes packed output only (the launcher sees to it): its fp32
             continue;                        // epilogue, compiled in as well, keeps hipcc from unrolling the pass loop
         } else {
-        // No wait on vector memory inside the store loop: `s_waitcnt vmcnt` counts stores too, so a wait for a load issued
-        // after a store -- the bias value, the residual of the next piece -- also waits until that store has been
-        // acknowledged by memory (~0.6 us).  With the loads of every piece interleaved with its store the tile's 131 KB left
-        // the CU one round trip at a time: 9.9 us per 128-channel tile (timing ablations), a quarter of the time a
-        // 49->128 tile takes.  The bias values are fetched once in front of the first pass; a layer without addends
-        // (most of them) issues no load at all here, the others fetch the addends of ALL pieces of a pass first.
+        // (no wait on vector memory between the stores of any of the forms below: why, at CB_EPI_FAST in conv2d_bf16_core.h)
         auto piece = [&](int i, int& co, long& opix, int& nv, int& col, int& px) -> bool {
             const int idx4 = tid + (256 + NP) * i;
             col = idx4 / (NPIX / 4);
@@ -1049,49 +836,11 @@ _Pragma("unroll") for (int i = 0; i < NI8; ++i) {                               
             return idx4 < 8 * NPIX && co < p.Cout && vy < ay.V && vx < ax.V;
         };
         if (fast_epi) {
-            // The whole tile inside the image, every output channel real, every row 16-byte aligned (the layers that matter):
-            // straight-line code -- hipcc can then COUNT its waits (vmcnt(n) for the addend of piece i leaves the stores of
-            // the pieces before it in flight; behind a per-piece branch it falls back to vmcnt(0))
+            // the whole tile inside the image, every output channel real, every row 16-byte aligned: CB_EPI_FAST (conv2d_bf16_core.h)
             const float* abase = add_kind == 1 ? p.pre + (long)(n / p.pre_div) * p.pre_sN : add_kind == 2 ? p.res + (long)n * p.res_sN : p.y + (long)n * p.out_sN;
             const long a_sC = add_kind == 1 ? p.pre_sC : add_kind == 2 ? p.res_sC : p.out_sC;
             float* ybase = p.y + (long)n * p.out_sN;
-            // (offsets are recomputed where they are used: kept in arrays across the two phases they cost the 32-channel kernels,
-            //  capped at 128 registers, a spill)
-#define CB_EPI_OFFS(i)                                                                               \
-    const int idx4_ = tid + (256 + NP) * (i);                                                        \
-    const int col_ = idx4_ / (NPIX / 4), px_ = (idx4_ % (NPIX / 4)) * 4;                             \
-    const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                                            \
-    const long opix_ = (long)(ty * TH + prow_) * p.Wout + tx * TW + pcol_;                           \
-    const int co_ = n0 + m * 32 + col_;
-#define CB_EPI_FINISH(ADD1, ADD2, ADD3)                                                              \
-_Pragma("unroll") for (int i = 0; i < NIT; ++i) {                                                    \
-    CB_EPI_OFFS(i)                                                                                   \
-    const float4 a4 = *reinterpret_cast<const float4*>(stage + col_ * NPIX + px_);                  \
-    float v[4] = {a4.x, a4.y, a4.z, a4.w};                                                           \
-    const float bv = bias_s[m * 32 + col_];                                                          \
-    _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                  \
-        float t = (v[j] + (ADD1)) + bv;                                                              \
-        if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                                 \
-        t = (t + (ADD2)) * p.out_scale;                                                              \
-        v[j] = t + (ADD3);                                                                           \
-    }                                                                                                \
-    cb_store16(ybase + (long)co_ * p.out_sC + opix_, f32x4{v[0], v[1], v[2], v[3]});               \
-}
-            if (add_kind == 0) {
-                CB_EPI_FINISH(0.f, 0.f, 0.f)
-            } else {
-                f32x4 ad[NIT];
-#pragma unroll
-                for (int i = 0; i < NIT; ++i) {
-                    CB_EPI_OFFS(i)
-                    ad[i] = *reinterpret_cast<const f32x4*>(abase + (long)co_ * a_sC + opix_);
-                }
-                if (add_kind == 1) { CB_EPI_FINISH(ad[i][j], 0.f, 0.f) }
-                else if (add_kind == 2) { CB_EPI_FINISH(0.f, ad[i][j], 0.f) }
-                else { CB_EPI_FINISH(0.f, 0.f, ad[i][j]) }
-            }
-#undef CB_EPI_OFFS
-#undef CB_EPI_FINISH
+            CB_EPI_FAST(tid, 256 + NP, bias_s[m * 32 + col_])
         } else if (!LEANK && add_kind == 0) {
             // no addend (most layers): a code path of its own WITHOUT any vector-memory load, so that hipcc has no reason to
             // put a wait between the stores (a conditional load makes it wait with vmcnt(0) at the first use of the value)
@@ -1204,7 +953,7 @@ _Pragma("unroll") for (int i = 0; i < NIT; ++i) {                               
                 }
             }
         }
-        if (m + 1 < MB) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // (LDS only: the stores stay in flight)
+        if (m + 1 < MB) CB_LDS_BARRIER();   // (LDS only: the stores stay in flight)
         }
     }
 }
@@ -1215,6 +964,15 @@ _Pragma("unroll") for (int i = 0; i < NIT; ++i) {                               
     do {                                                                                                                    \
         const hipError_t e_ = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, BYTES);   \
         if (e_ != hipSuccess) fprintf(stderr, "ccvs_conv2d_bf16x3: LDS limit of %s refused: %s\n", #KERNEL, hipGetErrorString(e_)); \
+    } while (0)
+// ... once per kernel (the static belongs to the expansion site, i.e. to one kernel of one launcher instantiation), before its first launch
+#define CB_SET_LDS_ONCE(KERNEL, BYTES)      \
+    do {                                    \
+        static bool attr_set_ = false;      \
+        if (!attr_set_) {                   \
+            CB_SET_LDS(KERNEL, BYTES);      \
+            attr_set_ = true;               \
+        }                                   \
     } while (0)
 
 // ConvK::xcd_chunk of a launch of n workgroups: the XCD-aware tile order (CONV_TILE_COORDS) where n splits into 8 runs of >= 8
@@ -1247,16 +1005,6 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         ccvs_set_error("ccvs_conv2d_bf16x3: halo tile %dx%d too large", halo_h, halo_w);
         return CCVS_ERR_ARG;
     }
-    static bool attr_set = false;
-    if (!attr_set) {
-        CB_SET_LDS((conv2d_bf16x3_kernel<TW, MB, 8>), 159 * 1024);
-        CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 0>), 159 * 1024);   // (+ the static bias block)
-        CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -2>), 159 * 1024);   // (+ the static bias block)
-        CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -8>), 159 * 1024);   // (+ the static bias block)
-        CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 1>), 159 * 1024);   // (+ the static bias block)
-        CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 3>), 159 * 1024);   // (+ the static bias block)
-        attr_set = true;
-    }
     ConvK k = k_in;
     if constexpr (TW == 32 && (MB == 4 || MB == 2)) {
         // persistent tiles (conv2d_bf16_pt.h): resident workgroups walk the tiles, a tile's prologue runs under the step loop of the tile before
@@ -1270,36 +1018,42 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
     // cu_limit > 0: the tiles go out as consecutive 1-D chunks of cu_limit x (workgroups of this instantiation that fit one
     // CU) workgroups -- launches on one stream run one after the other, so the convolution never holds more than cu_limit
     // CUs and work on another stream (the token loop of the next batch) always finds the remaining ones free.
-    long n_chunk = 1, cap = 0;
-    const long total = (long)grid3.x * grid3.y * grid3.z;
-    auto plan = [&](const void* fn, int threads, size_t smem_bytes) {
+    long n_chunk = 1, cap = 0, total = 0;
+    auto plan = [&](const dim3& grid, const void* fn, size_t smem_bytes) {
+        total = (long)grid.x * grid.y * grid.z;
         k.nwork = 0; k.work0 = 0;
-        k.gx = (int)grid3.x; k.gy = (int)grid3.y;
+        k.gx = (int)grid.x; k.gy = (int)grid.y;
         k.xcd_chunk = conv_xcd_chunk(total);
         n_chunk = 1;
-        if (k.cu_limit <= 0) return;
-        cap = (long)k.cu_limit * conv_occupancy(fn, threads, smem_bytes);
+        if (k.cu_limit <= 0) return;   // one launch over the whole chip
+        cap = (long)k.cu_limit * conv_occupancy(fn, 512, smem_bytes);
         if (total <= cap) return;  // fits as it is
         cap -= cap % 8;            // chunks of whole rounds over the XCDs
         if (cap < 8) cap = 8;
         k.nwork = (int)total;
         n_chunk = (total + cap - 1) / cap;
     };
-    auto chunk_grid = [&](long c) -> dim3 {
-        if (k.nwork == 0) return grid3;
+    auto chunk_grid = [&](const dim3& grid, long c) -> dim3 {
+        if (k.nwork == 0) return grid;
         k.work0 = (int)(c * cap);
         const long n = (total - c * cap < cap) ? total - c * cap : cap;
         k.xcd_chunk = conv_xcd_chunk(n);   // within the chunk
         return dim3((unsigned)n);
     };
-#define CB_LAUNCH(KERNEL, THREADS, SMEM, ...)                                                    \
+    // The tail of every form: the kernel's LDS limit (159 KB + the static bias block; set before its first launch), plan / chunk /
+    // launch over GRID with 512 threads, check, RETURN from the launcher.  CB_LAUNCH_RETURN: over the 256-pixel tiling.
+#define CB_LAUNCH_RETURN_ON(GRID, KERNEL, SMEM, ...)                                                      \
     do {                                                                                          \
-        plan((const void*)KERNEL, THREADS, SMEM);                                                 \
+        CB_SET_LDS_ONCE(KERNEL, 159 * 1024);                                                      \
+        plan(GRID, (const void*)KERNEL, SMEM);                                                    \
         for (long c_ = 0; c_ < n_chunk; ++c_) {                                                   \
-            const dim3 g_ = chunk_grid(c_);                                                       \
-            hipLaunchKernelGGL((KERNEL), g_, dim3(THREADS), SMEM, st, k, __VA_ARGS__);            \
+            const dim3 g_ = chunk_grid(GRID, c_);                                                 \
+            hipLaunchKernelGGL((KERNEL), g_, dim3(512), SMEM, st, k, __VA_ARGS__);                \
         }                                                                                         \
+        CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");                                                  \
+        return CCVS_OK;                                                                           \
     } while (0)
+#define CB_LAUNCH_RETURN(KERNEL, SMEM, ...) CB_LAUNCH_RETURN_ON(grid3, KERNEL, SMEM, __VA_ARGS__)
     if (k.in_p8) {  // packed input: LDS-DMA staging (validated by the caller: stride 1, not transposed, Cin % 8 == 0)
         const size_t smem_p = (size_t)(2 * 4 * plane + 2 * ntx_max * 4 * NT) * 16;
         if (4 * plane > 8 * 256 || ntx_max > (MB == 1 ? 9 : 3) || smem_p > 156 * 1024) {
@@ -1313,35 +1067,17 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
                 smem_4 >= (size_t)32 * 512 * 4) {
                 k.tiles_y = cdiv(k.Hout, th4);
                 const dim3 grid4(k.tiles_x * k.tiles_y, k.CoutPad / NT, gz);
-                const long total4 = (long)grid4.x * grid4.y * grid4.z;
-                k.nwork = 0; k.work0 = 0; k.gx = (int)grid4.x; k.gy = (int)grid4.y;
-                k.xcd_chunk = conv_xcd_chunk(total4);
-                static bool attr4p = false;
-                if (!attr4p) {
-                    CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), 159 * 1024);
-                    attr4p = true;
-                }
-                hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), grid4, dim3(512), (smem_4 > p8s4 ? smem_4 : p8s4), st, k, (const uint4*)wsplit, CinG, ntx_max);
-                CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-                return CCVS_OK;
+                // (cu_limit <= 0: one launch over the whole chip)
+                CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), (smem_4 > p8s4 ? smem_4 : p8s4), (const uint4*)wsplit, CinG, ntx_max);
             }
         }
         const size_t smem_p2 = smem_p > p8s2 ? smem_p : p8s2;
         if constexpr (MB != 4) {   // (128 output channels per workgroup: the written-out form spills; no layer of the models needs it)
             if (k.kh == 3 && k.kw == 3 && k.pad == 1) {
-                static bool attr_p = false;
-                if (!attr_p) {
-                    CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, -83>), 159 * 1024);
-                    attr_p = true;
-                }
-                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -83>), 512, smem_p2, (const uint4*)wsplit, CinG, ntx_max);
-                CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-                return CCVS_OK;
+                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -83>), smem_p2, (const uint4*)wsplit, CinG, ntx_max);
             }
         }
-        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -8>), 512, smem_p2, (const uint4*)wsplit, CinG, ntx_max);
-        CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-        return CCVS_OK;
+        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -8>), smem_p2, (const uint4*)wsplit, CinG, ntx_max);
     }
     // aligned float4 staging: dense stride-1 rows on 16-byte boundaries, one item per staging thread
     const int xsh = ((-k.pad % 4) + 4) % 4, nq = (xsh + halo_w + 3) / 4;
@@ -1361,22 +1097,11 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         if (!wpc2 && vec_ok && !k.out_p8 && k.Hout >= 2 * th4 && halo_h4 * ((nq + 1) / 2) * 4 <= 512 && smem_4 <= 156 * 1024 && smem_4 >= (size_t)32 * 512 * 4) {
             k.tiles_y = cdiv(k.Hout, th4);
             const dim3 grid4(k.tiles_x * k.tiles_y, k.CoutPad / NT, gz);
-            const long total4 = (long)grid4.x * grid4.y * grid4.z;
             // (one launch over the whole chip; with a CU budget the 256-pixel form below runs in chunks)
             if (k.cu_limit <= 0) {
-                k.nwork = 0; k.work0 = 0; k.gx = (int)grid4.x; k.gy = (int)grid4.y;
-                k.xcd_chunk = conv_xcd_chunk(total4);
-                static bool attr4 = false;
-                if (!attr4) {
-                    CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), 159 * 1024);   // (+ the static bias block)
-                    CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 3, 4>), 159 * 1024);   // (+ the static bias block)
-                    attr4 = true;
-                }
                 k.ktail = kt ? ktail_r : 0;
-                if (k.kh == 3) hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, 3, 4>), grid4, dim3(512), smem_4, st, k, (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
-                else hipLaunchKernelGGL((conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), grid4, dim3(512), smem_4, st, k, (const uint4*)wsplit, CinG, ntx_max);
-                CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-                return CCVS_OK;
+                if (k.kh == 3) CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, 3, 4>), smem_4, (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
+                else CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), smem_4, (const uint4*)wsplit, CinG, ntx_max);
             }
             k.tiles_y = k_in.tiles_y;
         }
@@ -1385,26 +1110,15 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         const size_t smem_v = (size_t)(2 * 4 * halo_h * (nq * 4 + 1) + 2 * ntx_max * 4 * NT) * 16;
         if constexpr (TW == 32 && MB == 2) {
             if (wpc2 && k.kh == 3 && k.kw == 3 && smem_v <= 80 * 1024 && k.cu_limit <= 0) {   // two workgroups per CU (see the kernel)
-                static bool attr2 = false;
-                if (!attr2) {
-                    CB_SET_LDS((conv2d_bf16x3_pc_kernel<TW, MB, 3, 2, 2>), 159 * 1024);   // (+ the static bias block)
-                    attr2 = true;
-                }
                 k.ktail = kt ? ktail_r : 0;
-                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 3, 2, 2>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
-                k.ktail = 0;
-                CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-                return CCVS_OK;
+                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 3, 2, 2>), (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
             }
         }
         if (smem_v <= 156 * 1024) {
             if (k.kh == 3) {
                 k.ktail = kt ? ktail_r : 0;
-                CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 3>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
-                k.ktail = 0;
-            } else CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 1>), 512, (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)wsplit, CinG, ntx_max);
-            CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-            return CCVS_OK;
+                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 3>), (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
+            } else CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 1>), (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)wsplit, CinG, ntx_max);
         }
     }
     // Scalar staging: the producer / consumer form with the halo tile in one (NTY 0) or two (NTY -2) pixel passes per tap row.
@@ -1415,14 +1129,10 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
     const bool pc_ok = !k.transposed && smem_pc <= 156 * 1024 && ntx_max <= (MB == 1 ? 9 : 3);
     // (8 staging waves for <= 64 output channels were measured slower: the steps are latency- not staging-bound)
     if (pc_ok && passes <= k.kh) {  // double-buffered producer / consumer form, scalar staging
-        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, 0>), 512, (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
-        CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-        return CCVS_OK;
+        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 0>), (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
     }
     if (pc_ok && passes <= 2 * k.kh) {
-        CB_LAUNCH((conv2d_bf16x3_pc_kernel<TW, MB, -2>), 512, (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
-        CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-        return CCVS_OK;
+        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -2>), (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
     }
     if (k.out_p8) {
         ccvs_set_error("ccvs_conv2d_bf16x3: packed output is not available for this shape (synchronous kernel)");
@@ -1433,7 +1143,7 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         ccvs_set_error("ccvs_conv2d_bf16x3: %zu bytes of LDS needed", smem);
         return CCVS_ERR_ARG;
     }
-    CB_LAUNCH((conv2d_bf16x3_kernel<TW, MB, 8>), 512, smem, (const uint4*)wsplit, CinG);
-    CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");
-    return CCVS_OK;
+    CB_LAUNCH_RETURN((conv2d_bf16x3_kernel<TW, MB, 8>), smem, (const uint4*)wsplit, CinG);
+#undef CB_LAUNCH_RETURN
+#undef CB_LAUNCH_RETURN_ON
 }

@@ -1,5 +1,6 @@
 // The split-bf16 3 x 3 convolution as RESIDENT workgroups that walk their tiles ("persistent tiles", PT) -- the producer / consumer
-// kernel of conv2d_bf16_kernels.h (same LDS images, same MFMA order per output: bit-identical results) with the tile loop INSIDE the
+// kernel of conv2d_bf16_kernels.h (same LDS images, same MFMA order per output: bit-identical results -- the taps, the K tail, the
+// accumulator stage and the epilogues of both kernels are the ONE definition in conv2d_bf16_core.h) with the tile loop INSIDE the
 // workgroup, so that a tile's prologue runs under the step loop of the tile before it:
 //   * one workgroup per CU (gridDim = CUs), workgroup g takes the tiles g, g + gridDim, ... of the launch's XCD-aware tile order;
 //   * the two roles are separate LOOPS OVER TILES (`if (producer) { for tiles ... } else { for tiles ... }`): written as one tile
@@ -40,6 +41,7 @@ __device__ __forceinline__ void pt_tile_coords(const ConvK& p, int w_, int& bx, 
 
 // MB: 32-channel blocks per workgroup; PP: 32-pixel blocks per MFMA wave (2: 8 x 32 pixels, 4: 16 x 32); P8IN: packed split-bf16
 // input (LDS-DMA staging) instead of fp32 rows (aligned dwordx4 + conversion)
+#define CB_PT_OFF(tb) (tb)   // LDS offset of tap column tb of a tap row: always the dense 3 x 3
 template <int MB, int PP, bool P8IN>
 __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const uint4* __restrict__ wsplit, int CinG, int total) {
     constexpr int TW = 32, NPIX = 128 * PP, TH = NPIX / TW, NT = 32 * MB;
@@ -83,41 +85,7 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
         asm volatile("" : "+v"(tid_));
         const float* abase = a_ptr + (long)(add_kind == 1 ? n / p.pre_div : n) * a_sN;
         float* ybase = p.y + (long)n * p.out_sN;
-#define PT_EPI_OFFS(i)                                                                  \
-        const int idx4_ = tid_ + 512 * (i);                                             \
-        const int col_ = idx4_ / (NPIX / 4), px_ = (idx4_ % (NPIX / 4)) * 4;            \
-        const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                           \
-        const long opix_ = (long)(ty * TH + prow_) * p.Wout + tx * TW + pcol_;          \
-        const int co_ = n0 + m * 32 + col_;
-#define PT_EPI_FINISH(ADD1, ADD2, ADD3)                                                 \
-    _Pragma("unroll") for (int i = 0; i < NIT; ++i) {                                   \
-        PT_EPI_OFFS(i)                                                                  \
-        const float4 a4 = *reinterpret_cast<const float4*>(stage + col_ * NPIX + px_); \
-        float v[4] = {a4.x, a4.y, a4.z, a4.w};                                          \
-        const float bv = bias_all[co_];                                                 \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                 \
-            float t = (v[j] + (ADD1)) + bv;                                             \
-            if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                \
-            t = (t + (ADD2)) * p.out_scale;                                             \
-            v[j] = t + (ADD3);                                                          \
-        }                                                                               \
-        cb_store16(ybase + (long)co_ * p.out_sC + opix_, f32x4{v[0], v[1], v[2], v[3]}); \
-    }
-        if (add_kind == 0) {
-            PT_EPI_FINISH(0.f, 0.f, 0.f)
-        } else {
-            f32x4 ad[NIT];
-#pragma unroll
-            for (int i = 0; i < NIT; ++i) {
-                PT_EPI_OFFS(i)
-                ad[i] = *reinterpret_cast<const f32x4*>(abase + (long)co_ * a_sC + opix_);
-            }
-            if (add_kind == 1) { PT_EPI_FINISH(ad[i][j], 0.f, 0.f) }
-            else if (add_kind == 2) { PT_EPI_FINISH(0.f, ad[i][j], 0.f) }
-            else { PT_EPI_FINISH(0.f, 0.f, ad[i][j]) }
-        }
-#undef PT_EPI_OFFS
-#undef PT_EPI_FINISH
+        CB_EPI_FAST(tid_, 512, bias_all[co_])   // the fast fp32 epilogue (conv2d_bf16_core.h): these tiles are always whole and aligned
     };
     auto epi_store_p8 = [&](int m, int tx, int ty, int n, int n0) __attribute__((always_inline)) {
         uint4* y4 = reinterpret_cast<uint4*>(p.y);
@@ -126,48 +94,9 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
         constexpr int NI8 = PP;   // (pixel, 8 channels) items of a 32-channel pass per thread
         int tid_ = tid;   // (opaque, see epi_store_f32)
         asm volatile("" : "+v"(tid_));
-#define PT_P8_ITEM(i)                                                                   \
-        const int item_ = tid_ + 512 * (i);                                             \
-        const int gq_ = item_ / NPIX, px_ = item_ - gq_ * NPIX;                         \
-        const int co0_ = n0 + m * 32 + gq_ * 8;                                         \
-        const int prow_ = px_ / TW, pcol_ = px_ - prow_ * TW;                           \
-        const long opix_ = (long)(ty * TH + prow_) * p.Wout + tx * TW + pcol_;
-#define PT_P8_FINISH(PRE)                                                               \
-    _Pragma("unroll") for (int i = 0; i < NI8; ++i) {                                   \
-        PT_P8_ITEM(i)                                                                   \
-        float v[8];                                                                     \
-        const f32x4 s0 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8);   \
-        const f32x4 s1 = *reinterpret_cast<const f32x4*>(stage + px_ * 36 + gq_ * 8 + 4); \
-        _Pragma("unroll") for (int c = 0; c < 8; ++c) {                                 \
-            float t = c < 4 ? s0[c] : s1[c - 4];                                        \
-            t += (PRE);                                                                 \
-            t += bias_all[co0_ + c];                                                    \
-            if (p.act == CCVS_ACT_LRELU) t = lrelu01(t);                                \
-            v[c] = t * p.out_scale;                                                     \
-        }                                                                               \
-        uint4 hi, lo;                                                                   \
-        split8(v, hi, lo);                                                              \
-        uint4* dst = y4 + ((long)n * gout + (co0_ >> 3)) * 2 * hw_out + opix_;          \
-        cb_store16(dst, hi);                                                            \
-        cb_store16(dst + hw_out, lo);                                                   \
-    }
-        if (p.pre) {
-            float pv[NI8][8];
-            const float* pb = p.pre + (long)(n / p.pre_div) * p.pre_sN;
-#pragma unroll
-            for (int i = 0; i < NI8; ++i) {
-                PT_P8_ITEM(i)
-#pragma unroll
-                for (int c = 0; c < 8; ++c) pv[i][c] = pb[(long)(co0_ + c) * p.pre_sC + opix_];
-            }
-            PT_P8_FINISH(pv[i][c])
-        } else {
-            PT_P8_FINISH(0.f)
-        }
-#undef PT_P8_ITEM
-#undef PT_P8_FINISH
+        // the packed-output epilogue (conv2d_bf16_core.h); whole tiles: no guard, the plain pixel offset, no clamp
+        CB_EPI_P8(tid_, true, ((long)(ty * TH + prow_) * p.Wout + tx * TW + pcol_), CB_NO_CLAMP, bias_all[co0_ + c])
     };
-#define PT_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")   /* LDS only: global stores / loads stay in flight */
 
     int lin = (int)blockIdx.x;   // the tile this role computes
     if (producer) {
@@ -199,10 +128,10 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
             const int n0 = by * NT, n = bz;
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
-                PT_LDS_BARRIER();
+                CB_LDS_BARRIER();
                 if (p.out_p8) epi_store_p8(m, tx, ty, n, n0);
                 else epi_store_f32(m, tx, ty, n, n0);
-                if (m + 1 < MB) PT_LDS_BARRIER();
+                if (m + 1 < MB) CB_LDS_BARRIER();
             }
         };
         if constexpr (P8IN) {
@@ -261,7 +190,7 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
                 epilogue();
                 lin += stride_t;
                 if (lin >= total) break;
-                PT_LDS_BARRIER();   // B0: the stage (over halo buffers 0 / 1) is free again
+                CB_LDS_BARRIER();   // B0: the stage (over halo buffers 0 / 1) is free again
             }
         } else {
             // item j of this thread: half vh (8 channels), halo row vr, float4 column vq -- the same for every tile
@@ -356,13 +285,13 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
                 store_xv(SET);                                                                                \
                 load_xv(SET);                                                                                 \
                 const int nb_ = (ktail && cc == nchunks - 1) ? 1 : 3;                                         \
-                for (int a = 0; a < nb_; ++a) PT_LDS_BARRIER();                                               \
+                for (int a = 0; a < nb_; ++a) CB_LDS_BARRIER();                                               \
                 if (++cc == nchunks) {                                                                        \
                     cc = 0;                                                                                   \
                     epilogue();                                                                               \
                     lin += stride_t;                                                                          \
                     more = lin < total;                                                                       \
-                    if (more) PT_LDS_BARRIER();                                                               \
+                    if (more) CB_LDS_BARRIER();                                                               \
                 }                                                                                             \
             }
             while (more) {
@@ -442,90 +371,22 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
                     const uint4* it0 = smem4 + (ci == 0 ? 2 * in_sz + 2 * w_sz : (ci & 1) * in_sz) + (khalf * 2) * plane + a * IWS;
                     const uint4* wt0 = w_buf + wp * w_sz + (khalf * 2) * NT + (lane & 31);
                     if constexpr (PP == 4) {
-                        // four pixel blocks of a tap in registers, the weight fragments of the tap's MB channel blocks in one of two sets;
-                        // each pixel block is re-read for the next tap right after its last MFMA (conv2d_bf16_kernels.h, CB_TAP4)
-                        bf16x8 fq[4][2], fw[2][MB][2];
-#pragma unroll
-                        for (int pp = 0; pp < 4; ++pp) {
-                            fq[pp][0] = __builtin_bit_cast(bf16x8, it0[bofs[pp]]);
-                            fq[pp][1] = __builtin_bit_cast(bf16x8, it0[plane + bofs[pp]]);
-                        }
-#pragma unroll
-                        for (int m = 0; m < MB; ++m) {
-                            fw[0][m][0] = __builtin_bit_cast(bf16x8, wt0[m * 32]);
-                            fw[0][m][1] = __builtin_bit_cast(bf16x8, wt0[NT + m * 32]);
-                        }
-#define PT_TAP4(CUR, tb, more_)                                                                                        \
-    {                                                                                                                  \
-        const uint4* itn_ = it0 + ((tb) + 1);                                                                          \
-        if (more_) {                                                                                                   \
-            const uint4* wtn_ = wt0 + ((tb) + 1) * 4 * NT;                                                             \
-            _Pragma("unroll") for (int m = 0; m < MB; ++m) {                                                           \
-                fw[(CUR) ^ 1][m][0] = __builtin_bit_cast(bf16x8, wtn_[m * 32]);                                        \
-                fw[(CUR) ^ 1][m][1] = __builtin_bit_cast(bf16x8, wtn_[NT + m * 32]);                                   \
-            }                                                                                                          \
-        }                                                                                                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                             \
-        _Pragma("unroll") for (int m = 0; m < MB; ++m) {                                                               \
-            _Pragma("unroll") for (int pp = 0; pp < 4; ++pp) {                                                         \
-                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[CUR][m][1], fq[pp][0], acc[m][pp], 0, 0, 0);   \
-                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[CUR][m][0], fq[pp][1], acc[m][pp], 0, 0, 0);   \
-                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fw[CUR][m][0], fq[pp][0], acc[m][pp], 0, 0, 0);   \
-                if (m == MB - 1 && (more_)) {                                                                          \
-                    fq[pp][0] = __builtin_bit_cast(bf16x8, itn_[bofs[pp]]);                                            \
-                    fq[pp][1] = __builtin_bit_cast(bf16x8, itn_[plane + bofs[pp]]);                                    \
-                }                                                                                                      \
-            }                                                                                                          \
-        }                                                                                                              \
-    }
-                        PT_TAP4(0, 0, true)
+                        bf16x8 fq[4][2], fw[2][MB][2];   // the 512-pixel tap (CB_TAP4, conv2d_bf16_core.h)
+                        CB_TAP4_PRIME(CB_PT_OFF)
+                        CB_TAP4(0, 0, true, CB_PT_OFF)
                         PT_MID_DMA()
-                        PT_TAP4(1, 1, true)
-                        PT_TAP4(0, 2, false)
-#undef PT_TAP4
+                        CB_TAP4(1, 1, true, CB_PT_OFF)
+                        CB_TAP4(0, 2, false, CB_PT_OFF)
                     } else {
-                        // fragment reads software-pipelined by hand: the next block's ds_reads above the current block's 6 MFMAs
-                        // (conv2d_bf16_kernels.h, CB_TAP)
+                        // the 256-pixel tap, written out (CB_LD_B / CB_LD_A / CB_TAP, conv2d_bf16_core.h)
                         bf16x8 fa[2][2];     // [set][0 hi | 1 lo]       weights of one 32-cout block
                         bf16x8 fb[2][2][2];  // [set][pp][0 hi | 1 lo]   the two pixel blocks of one tap
-#define PT_LD_B(SET, tb)                                                                        \
-    {                                                                                           \
-        const uint4* it_ = it0 + (tb);                                                          \
-        _Pragma("unroll") for (int pp = 0; pp < 2; ++pp) {                                      \
-            fb[SET][pp][0] = __builtin_bit_cast(bf16x8, it_[bofs[pp]]);                         \
-            fb[SET][pp][1] = __builtin_bit_cast(bf16x8, it_[plane + bofs[pp]]);                 \
-        }                                                                                       \
-    }
-#define PT_LD_A(SET, tb, m_)                                                                    \
-    {                                                                                           \
-        const uint4* wt_ = wt0 + (tb) * 4 * NT + (m_) * 32;                                     \
-        fa[SET][0] = __builtin_bit_cast(bf16x8, wt_[0]);                                        \
-        fa[SET][1] = __builtin_bit_cast(bf16x8, wt_[NT]);                                       \
-    }
-#define PT_TAP(BSET, A0, tb, has_next_)                                                         \
-    _Pragma("unroll") for (int m = 0; m < MB; ++m) {                                            \
-        if (m + 1 < MB) {                                                                       \
-            PT_LD_A(((A0) + m + 1) & 1, tb, m + 1)                                              \
-        } else if (has_next_) {                                                                 \
-            PT_LD_A(((A0) + m + 1) & 1, (tb) + 1, 0)                                            \
-            PT_LD_B((BSET) ^ 1, (tb) + 1)                                                       \
-        }                                                                                       \
-        __builtin_amdgcn_sched_barrier(0);                                                      \
-        _Pragma("unroll") for (int pp = 0; pp < 2; ++pp) {                                      \
-            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[((A0) + m) & 1][1], fb[BSET][pp][0], acc[m][pp], 0, 0, 0); \
-            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[((A0) + m) & 1][0], fb[BSET][pp][1], acc[m][pp], 0, 0, 0); \
-            acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[((A0) + m) & 1][0], fb[BSET][pp][0], acc[m][pp], 0, 0, 0); \
-        }                                                                                       \
-    }
-                        PT_LD_B(0, 0)
-                        PT_LD_A(0, 0, 0)
-                        PT_TAP(0, 0, 0, true)
+                        CB_LD_B(0, 0, CB_PT_OFF)
+                        CB_LD_A(0, 0, 0)
+                        CB_TAP(0, 0, 0, true, CB_PT_OFF)
                         PT_MID_DMA()
-                        PT_TAP(1, (MB & 1), 1, true)
-                        PT_TAP(0, 0, 2, false)
-#undef PT_LD_B
-#undef PT_LD_A
-#undef PT_TAP
+                        CB_TAP(1, (MB & 1), 1, true, CB_PT_OFF)
+                        CB_TAP(0, 0, 2, false, CB_PT_OFF)
                     }
                 }
 #undef PT_MID_DMA
@@ -535,44 +396,9 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
             }
             if constexpr (!P8IN) {
                 if (ktail) {
-                    // packed K tail (ccvs_conv_desc.w_ktail; conv2d_bf16_kernels.h): the last chunk's nine taps x r channels contracted in
-                    // ceil(9 r / 16) steps whose K index runs over (tap, channel); the pixel operand is gathered from the staged tile
+                    // packed K tail (CB_KTAIL, conv2d_bf16_core.h), after the request for the next tile's first weights
                     if (has_next) dma_w(n0n, 0, 0, w_buf + (wp ^ 1) * w_sz);
-                    const int r_ = p.ktail, nq_ = 9 * r_, nj_ = (nq_ + 15) >> 4;
-                    const unsigned short* ih = reinterpret_cast<const unsigned short*>(in_buf + ((nchunks - 1) & 1) * in_sz);
-                    const uint4* wtl = w_buf + wp * w_sz + (khalf * 2) * NT + (lane & 31);
-                    for (int j = 0; j < nj_; ++j) {
-                        bf16x8 gb[PP][2];
-#pragma unroll
-                        for (int pp = 0; pp < PP; ++pp) {
-                            unsigned hw[4], lw[4];
-#pragma unroll
-                            for (int i = 0; i < 8; ++i) {
-                                const int q = 16 * j + 8 * khalf + i;
-                                const int qc = min(q, nq_ - 1);
-                                const int t = qc / r_, c = qc - t * r_;
-                                const int tyy = t / 3, txx = t - 3 * tyy;
-                                const int e = (bofs[pp] + tyy * IWS + txx) * 8 + c;   // bf16 index inside the [pixel][8] plane
-                                unsigned hv = ih[e], lv = ih[plane * 8 + e];
-                                if (q >= nq_) { hv = 0; lv = 0; }
-                                if (i & 1) { hw[i >> 1] |= hv << 16; lw[i >> 1] |= lv << 16; }
-                                else { hw[i >> 1] = hv; lw[i >> 1] = lv; }
-                            }
-                            gb[pp][0] = __builtin_bit_cast(bf16x8, make_uint4(hw[0], hw[1], hw[2], hw[3]));
-                            gb[pp][1] = __builtin_bit_cast(bf16x8, make_uint4(lw[0], lw[1], lw[2], lw[3]));
-                        }
-#pragma unroll
-                        for (int m = 0; m < MB; ++m) {
-                            const bf16x8 ah = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + m * 32]);
-                            const bf16x8 al = __builtin_bit_cast(bf16x8, wtl[j * 4 * NT + NT + m * 32]);
-#pragma unroll
-                            for (int pp = 0; pp < PP; ++pp) {
-                                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, gb[pp][0], acc[m][pp], 0, 0, 0);
-                                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][1], acc[m][pp], 0, 0, 0);
-                                acc[m][pp] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, gb[pp][0], acc[m][pp], 0, 0, 0);
-                            }
-                        }
-                    }
+                    CB_KTAIL(reinterpret_cast<const unsigned short*>(in_buf + ((nchunks - 1) & 1) * in_sz), w_buf + wp * w_sz + (khalf * 2) * NT + (lane & 31))
                     __syncthreads();
                     wp ^= 1;
                 }
@@ -583,40 +409,23 @@ __global__ __launch_bounds__(512, 2) void conv2d_bf16x3_pt_kernel(ConvK p, const
             const int khalf_ = lane_ >> 5;
 #pragma unroll
             for (int m = 0; m < MB; ++m) {
-                if (p.out_p8) {
-#pragma unroll
-                    for (int pp = 0; pp < PP; ++pp) {
-                        float* sp = stage + ((rw_ * PP + pp) * 32 + (lane_ & 31)) * 36 + 4 * khalf_;
-#pragma unroll
-                        for (int g = 0; g < 4; ++g) {
-                            const f32x4 q4 = {acc[m][pp][4 * g], acc[m][pp][4 * g + 1], acc[m][pp][4 * g + 2], acc[m][pp][4 * g + 3]};
-                            *reinterpret_cast<f32x4*>(sp + 8 * g) = q4;
-                        }
-                    }
-                } else {
-#pragma unroll
-                    for (int pp = 0; pp < PP; ++pp)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            stage[((r & 3) + 8 * (r >> 2) + 4 * khalf_) * NPIX + (rw_ * PP + pp) * 32 + (lane_ & 31)] = acc[m][pp][r];
-                }
-                PT_LDS_BARRIER();
+                CB_STAGE_PASS(acc[m], p.out_p8, rw_, lane_, khalf_)
+                CB_LDS_BARRIER();
                 if (p.out_p8) epi_store_p8(m, tx, ty, n, n0);
                 else epi_store_f32(m, tx, ty, n, n0);
-                if (m + 1 < MB) PT_LDS_BARRIER();
+                if (m + 1 < MB) CB_LDS_BARRIER();
             }
             lin = lnext;
             if (!has_next) break;
             tx = txn; ty = tyn; n = nn; n0 = n0n;
-            PT_LDS_BARRIER();   // B0 of the next tile
+            CB_LDS_BARRIER();   // B0 of the next tile
         }
     }
-#undef PT_LDS_BARRIER
 }
 
 // Can this launch run as persistent tiles?  (k: the launch as launch_conv_bf16 sees it, tiles_x / tiles_y of the 256-pixel tiling.)
 template <int MB>
-static bool conv_pt_ok(const ConvK& k, int pp, bool kt_possible) {
+static bool conv_pt_ok(const ConvK& k, int pp) {
     const int th = 4 * pp, nt = 32 * MB;
     if (!(k.kh == 3 && k.kw == 3 && k.stride == 1 && k.pad == 1 && !k.transposed)) return false;
     if (k.cu_limit > 0 || k.Wout % 32 != 0 || k.Hout % th != 0 || k.Hout != k.Hin || k.Wout != k.Win) return false;
@@ -635,7 +444,6 @@ static bool conv_pt_ok(const ConvK& k, int pp, bool kt_possible) {
     if (!k.in_p8) {
         if (k.Win % 4 != 0 || k.in_sC % 4 != 0 || k.in_sN % 4 != 0 || (reinterpret_cast<uintptr_t>(k.x) & 15) != 0) return false;
     }
-    (void)kt_possible;
     return true;
 }
 
@@ -658,11 +466,7 @@ static int launch_conv_pt(ConvK k, const void* w, int CinG, int gz, hipStream_t 
     constexpr int NT = 32 * MB, TH = 4 * PP, IH = TH + 2, IWS = P8IN ? 34 : 41, plane = IH * IWS;
     constexpr size_t smem = (size_t)(3 * 4 * plane + 2 * 3 * 4 * NT) * 16;
     static_assert(smem <= 156 * 1024, "persistent tiles: LDS");
-    static bool attr_set = false;
-    if (!attr_set) {
-        CB_SET_LDS((conv2d_bf16x3_pt_kernel<MB, PP, P8IN>), (int)smem);   // (+ 2 KB static: the layer's bias values)
-        attr_set = true;
-    }
+    CB_SET_LDS_ONCE((conv2d_bf16x3_pt_kernel<MB, PP, P8IN>), (int)smem);   // (+ 2 KB static: the layer's bias values)
     k.tiles_x = k.Wout / 32;
     k.tiles_y = k.Hout / TH;
     k.gx = k.tiles_x * k.tiles_y;
@@ -686,18 +490,18 @@ static int conv_pt_try(const ConvK& k_in, const void* wsplit, const void* wktail
     if (k.in_p8) {
         if (!(pt_on & 2)) return CONV_PT_NOT_TAKEN;
         if constexpr (MB == 2) {
-            if (k.out_p8 && conv_pt_ok<2>(k, 4, false) && (long)(k.Wout / 32) * (k.Hout / 16) * (k.CoutPad / 64) * gz >= 2L * cus)
+            if (k.out_p8 && conv_pt_ok<2>(k, 4) && (long)(k.Wout / 32) * (k.Hout / 16) * (k.CoutPad / 64) * gz >= 2L * cus)
                 return launch_conv_pt<2, 4, true>(k, wsplit, CinG, gz, st);
         }
         if constexpr (MB == 4) {
-            if (conv_pt_ok<4>(k, 2, false) && (long)(k.Wout / 32) * (k.Hout / 8) * (k.CoutPad / 128) * gz >= 2L * cus)
+            if (conv_pt_ok<4>(k, 2) && (long)(k.Wout / 32) * (k.Hout / 8) * (k.CoutPad / 128) * gz >= 2L * cus)
                 return launch_conv_pt<4, 2, true>(k, wsplit, CinG, gz, st);
         }
         return CONV_PT_NOT_TAKEN;
     }
     if constexpr (MB == 4) {
         if (!(pt_on & 1)) return CONV_PT_NOT_TAKEN;
-        if (conv_pt_ok<4>(k, 2, true) && (long)(k.Wout / 32) * (k.Hout / 8) * (k.CoutPad / 128) * gz >= 2L * cus) {
+        if (conv_pt_ok<4>(k, 2) && (long)(k.Wout / 32) * (k.Hout / 8) * (k.CoutPad / 128) * gz >= 2L * cus) {
             const int ktail_r = k.Cin % CB_CC;
             const bool kt = wktail && ktail_r >= 1 && ktail_r <= 3 && k.Cin > CB_CC;
             k.ktail = kt ? ktail_r : 0;

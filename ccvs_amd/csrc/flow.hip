@@ -16,7 +16,6 @@
 // apart: every read a two-way bank conflict).
 // ---------------------------------------------------------------------------------------
 #define CORR_CC 8
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 template <int S>
 __global__ __launch_bounds__(256) void correlation7x7_kernel(const float* __restrict__ first, const float* __restrict__ second,
@@ -442,24 +441,9 @@ static void launch_backwarp(const CtxList& l, long x_sC, const float* flow, long
 // LDS-DMA, no conversion.  A lane owns ONE pixel and 8 channels: its two 16-byte units are the store width the four-pixel form
 // was built for, and consecutive lanes write consecutive units.  Group C/8 holds (flow x, flow y, occlusion, 0 x 5) as stored
 // (the warp itself uses flow * mult).  Same samples as backwarp4_kernel (bilin_setup_pair / bilin_sample_pair), split like the
-// convolution's staging waves split them (round to nearest even twice): the convolution sees the same operands.
+// convolution's staging waves split them (round to nearest even twice; split8 of common.h, the one definition both call): the
+// convolution sees the same operands.
 // ---------------------------------------------------------------------------------------
-typedef __bf16 wp_bf16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned wp_pk_bf16(float a, float b) {
-    const f32x2 v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wp_bf16x2));
-}
-__device__ __forceinline__ void wp_split8(const float (&v)[8], uint4& hi, uint4& lo) {
-    unsigned h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        h[i] = wp_pk_bf16(v[2 * i], v[2 * i + 1]);
-        l[i] = wp_pk_bf16(v[2 * i] - __uint_as_float(h[i] << 16), v[2 * i + 1] - __uint_as_float(h[i] & 0xffff0000u));
-    }
-    hi = make_uint4(h[0], h[1], h[2], h[3]);
-    lo = make_uint4(l[0], l[1], l[2], l[3]);
-}
-
 __global__ __launch_bounds__(256) void backwarp_p8_kernel(CtxList ctx, long x_sC, const float* __restrict__ fo, long fo_sN, float mult,
                                                           uint4* __restrict__ y, int C, int H, int W, GridWalk gw) {
     // lane = 4 consecutive pixels x 8 channels, sampled exactly like backwarp4_kernel (same values bit for bit); the 32 results
@@ -507,7 +491,7 @@ __global__ __launch_bounds__(256) void backwarp_p8_kernel(CtxList ctx, long x_sC
     for (int i = 0; i < 4; ++i) {
         const float vi[8] = {v[0][i], v[1][i], v[2][i], v[3][i], v[4][i], v[5][i], v[6][i], v[7][i]};
         uint4 hi, lo;
-        wp_split8(vi, hi, lo);
+        split8(vi, hi, lo);
         wp_stage[i * 256 + threadIdx.x] = hi;          // pixel 4 t + i of the block
         wp_stage[1024 + i * 256 + threadIdx.x] = lo;
     }
