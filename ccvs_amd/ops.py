@@ -270,13 +270,16 @@ def conv_heads(feat, w_packed, bias3, out, accumulate, flops_cb=None):
 
 
 # ------------------------------------------------------------------ resampling
-def upfirdn2d(x, up=1, down=1, pad=(0, 0), gain=1.0, act=False, residual=None, out_scale=1.0):
-    _need_gpu(x, residual)
+def upfirdn2d(x, up=1, down=1, pad=(0, 0), gain=1.0, act=False, residual=None, out_scale=1.0, out=None):
+    """(act(upfirdn2d(x, outer([1,3,3,1]) / 64 * gain, up, down, pad)) [+ residual]) * out_scale (`ccvs_upfirdn2d`).
+    out: optional contiguous fp32 [N,C,Ho,Wo] tensor to write into (default: a new one)."""
+    _need_gpu(x, residual, out)
     x = x.contiguous()
     n, c, h, w = x.shape
     ho = (h * up + pad[0] + pad[1] - 4) // down + 1
     wo = (w * up + pad[0] + pad[1] - 4) // down + 1
-    y = torch.empty(n, c, ho, wo, dtype=torch.float32, device=x.device)
+    y = torch.empty(n, c, ho, wo, dtype=torch.float32, device=x.device) if out is None else out
+    assert y.shape == (n, c, ho, wo) and y.is_contiguous() and y.dtype == torch.float32, (tuple(y.shape), (n, c, ho, wo))
     if residual is not None:
         residual = residual.contiguous()
         assert residual.shape == y.shape
@@ -313,17 +316,20 @@ def gaussian_kernel1d(k, sigma):
     return pdf / pdf.sum()
 
 
-def gaussian_blur(x, k, sigma):
+def gaussian_blur(x, k, sigma, out=None):
     """transforms.GaussianBlur(kernel_size=k, sigma=sigma)(x) of [N,C,H,W] fp32 (helpers/generator.py:381-390 `blur`): reflect
-    padding, the separable k x k Gaussian (`ccvs_gaussian_blur`).  x may have any batch / channel strides; the result is contiguous."""
-    _need_gpu(x)
+    padding, the separable k x k Gaussian (`ccvs_gaussian_blur`).  x may have any batch / channel strides; the result is contiguous.
+    out: optional contiguous fp32 [N,C,H,W] tensor to write into (default: a new one)."""
+    _need_gpu(x, out)
     assert x.dtype == torch.float32 and x.dim() == 4
     if not _rows_dense(x):
         x = x.contiguous()
     n, c, h, w = x.shape
     wt = gaussian_kernel1d(int(k), float(sigma))
     wbuf = (C.c_float * int(k))(*wt.tolist())
-    out = torch.empty(n, c, h, w, dtype=torch.float32, device=x.device)
+    if out is None:
+        out = torch.empty(n, c, h, w, dtype=torch.float32, device=x.device)
+    assert out.shape == (n, c, h, w) and out.is_contiguous() and out.dtype == torch.float32
     _lib.check(_lib.load().ccvs_gaussian_blur(_p(x), x.stride(0), x.stride(1), _p(out), n, c, h, w, int(k), wbuf, _stream()),
                "ccvs_gaussian_blur")
     return out
@@ -370,12 +376,18 @@ def channel_head(x, weight, scale, bias=None, act=True, tanh=False, out=None):
 
 
 # ------------------------------------------------------------------ cost volume / warp
-def correlation7x7(first, second, stride, first_div=1, lrelu=False):
-    _need_gpu(first, second)
+def correlation7x7(first, second, stride, first_div=1, lrelu=False, out=None):
+    """The 7 x 7 cost volume [N,49,ceil(H/stride),ceil(W/stride)] of second [N,C,H,W] against first [N/first_div,C,H,W]
+    (`ccvs_correlation7x7`), LeakyReLU(0.1) with `lrelu`.  out: optional contiguous fp32 tensor of that shape to write into
+    (default: a new one)."""
+    _need_gpu(first, second, out)
     first, second = first.contiguous(), second.contiguous()
     n, c, h, w = second.shape
     assert first.shape[0] * first_div == n and first.shape[1:] == second.shape[1:]
-    out = torch.empty(n, 49, -(-h // stride), -(-w // stride), dtype=torch.float32, device=second.device)
+    ho, wo = -(-h // stride), -(-w // stride)
+    if out is None:
+        out = torch.empty(n, 49, ho, wo, dtype=torch.float32, device=second.device)
+    assert out.shape == (n, 49, ho, wo) and out.is_contiguous() and out.dtype == torch.float32
     L = _lib.load()
     _lib.check(L.ccvs_correlation7x7(_p(first), _p(second), _p(out), n, c, h, w, stride, first_div, 1 if lrelu else 0, _stream()),
                "ccvs_correlation7x7")
@@ -443,34 +455,40 @@ def pack_proj_weight(weight):
     return out.contiguous(), pads[0]
 
 
-def backwarp_p8(ctxs, flow_occ, flow_mult):
+def backwarp_p8(ctxs, flow_occ, flow_mult, out=None):
     """[backwarp(ctx, flow * flow_mult) | flow | occ | 0 x 5] for the list of k context tensors [N/k,C,H,W] (see `backwarp`) as a P8Act of
-    C + 8 channels (`ccvs_backwarp_p8_ctx`): the packed input of the first Subpixel convolution.  flow_occ: [N,3,H,W]."""
-    _need_gpu(flow_occ)
+    C + 8 channels (`ccvs_backwarp_p8_ctx`): the packed input of the first Subpixel convolution.  flow_occ: [N,3,H,W].
+    out: optional flat contiguous float32 buffer of N (C + 8) H W elements that becomes the P8Act's `data` (default: a new one)."""
+    _need_gpu(flow_occ, out)
     if not _planes_dense(flow_occ):
         flow_occ = flow_occ.contiguous()
     cl, keep = _ctx_list(ctxs)
     nf, c, h, w = keep[0].shape
     n = nf * cl.k
     assert flow_occ.shape == (n, 3, h, w) and c % 8 == 0 and w % 4 == 0
-    out = torch.empty(n * (c + 8) * h * w, dtype=torch.float32, device=flow_occ.device)
+    if out is None:
+        out = torch.empty(n * (c + 8) * h * w, dtype=torch.float32, device=flow_occ.device)
+    assert out.shape == (n * (c + 8) * h * w,) and out.is_contiguous() and out.dtype == torch.float32
     L = _lib.load()
     _lib.check(L.ccvs_backwarp_p8_ctx(C.byref(cl), h * w, _p(flow_occ), flow_occ.stride(0), flow_mult, _p(out), n, c, h, w, _stream()),
                "ccvs_backwarp_p8_ctx")
     return P8Act(out, n, c + 8, h, w)
 
 
-def backwarp_proj(ctxs, flow, flow_mult, w_t, cout_pad, bias, cout, act=True):
+def backwarp_proj(ctxs, flow, flow_mult, w_t, cout_pad, bias, cout, act=True, out=None):
     """act(bias + W . backwarp(ctx, flow * flow_mult)) for the list of k context tensors [N/k,C,H,W] (see `backwarp`):
-    [N,cout,H,W], the warped tensor is never materialised (`ccvs_backwarp_proj_ctx`)."""
-    _need_gpu(flow, w_t, bias)
+    [N,cout,H,W], the warped tensor is never materialised (`ccvs_backwarp_proj_ctx`).  out: optional contiguous fp32 [N,cout,H,W]
+    tensor to write into (default: a new one)."""
+    _need_gpu(flow, w_t, bias, out)
     if not _planes_dense(flow):
         flow = flow.contiguous()
     cl, keep = _ctx_list(ctxs)
     nf, c, h, w = keep[0].shape
     n = nf * cl.k
     assert flow.shape == (n, 2, h, w) and w_t.shape == (c, cout_pad)
-    out = torch.empty(n, cout, h, w, dtype=torch.float32, device=flow.device)
+    if out is None:
+        out = torch.empty(n, cout, h, w, dtype=torch.float32, device=flow.device)
+    assert out.shape == (n, cout, h, w) and out.is_contiguous() and out.dtype == torch.float32
     L = _lib.load()
     _lib.check(L.ccvs_backwarp_proj_ctx(C.byref(cl), h * w, _p(flow), flow.stride(0), flow_mult, _p(w_t), _p(bias), _p(out), n, c, cout, cout_pad,
                                         h, w, ACT_LRELU if act else ACT_NONE, _stream()), "ccvs_backwarp_proj_ctx")
@@ -842,15 +860,18 @@ def stream_cu_limit(stream, cu_limit):
     _lib.check(L.ccvs_stream_cu_limit(C.c_void_p(stream.cuda_stream), int(cu_limit)), "ccvs_stream_cu_limit")
 
 
-def pack_u8_norm(vid, std, mean):
+def pack_u8_norm(vid, std, mean, out=None):
     """[..., 3, H, W] fp32 -> [..., H, W, 3] uint8 with the imagenet de-normalisation of helpers/generator.py:303-305 in front:
-    v*std[c], + mean[c], clamp(0, 1), x255, truncate (each step rounded on its own: byte-exact with the reference's ops)."""
-    _need_gpu(vid)
+    v*std[c], + mean[c], clamp(0, 1), x255, truncate (each step rounded on its own: byte-exact with the reference's ops).
+    out: optional contiguous uint8 [..., H, W, 3] tensor to write into (default: a new one)."""
+    _need_gpu(vid, out)
     vid = vid.contiguous()
     lead = vid.shape[:-3]
     h, w = vid.shape[-2:]
     n = int(math.prod(lead)) if len(lead) else 1
-    out = torch.empty(*lead, h, w, 3, dtype=torch.uint8, device=vid.device)
+    if out is None:
+        out = torch.empty(*lead, h, w, 3, dtype=torch.uint8, device=vid.device)
+    assert out.shape == (*lead, h, w, 3) and out.is_contiguous() and out.dtype == torch.uint8
     s3, m3 = (C.c_float * 3)(*[float(v) for v in std]), (C.c_float * 3)(*[float(v) for v in mean])
     L = _lib.load()
     _lib.check(L.ccvs_pack_u8_norm(_p(vid), _p(out), n, h, w, s3, m3, _stream()), "ccvs_pack_u8_norm")
@@ -909,14 +930,17 @@ def resize_bilinear(x, size):
     return out
 
 
-def pack_u8(vid, lo=-1.0, hi=1.0):
-    """[..., 3, H, W] fp32 -> [..., H, W, 3] uint8 (helpers/generator.py:306-309)."""
-    _need_gpu(vid)
+def pack_u8(vid, lo=-1.0, hi=1.0, out=None):
+    """[..., 3, H, W] fp32 -> [..., H, W, 3] uint8 (helpers/generator.py:306-309).  out: optional contiguous uint8 [..., H, W, 3]
+    tensor to write into (default: a new one)."""
+    _need_gpu(vid, out)
     vid = vid.contiguous()
     lead = vid.shape[:-3]
     h, w = vid.shape[-2:]
     n = int(math.prod(lead)) if len(lead) else 1
-    out = torch.empty(*lead, h, w, 3, dtype=torch.uint8, device=vid.device)
+    if out is None:
+        out = torch.empty(*lead, h, w, 3, dtype=torch.uint8, device=vid.device)
+    assert out.shape == (*lead, h, w, 3) and out.is_contiguous() and out.dtype == torch.uint8
     L = _lib.load()
     _lib.check(L.ccvs_pack_u8(_p(vid), _p(out), n, h, w, lo, hi, _stream()), "ccvs_pack_u8")
     return out

@@ -1,7 +1,11 @@
 """Worker of tests/test_ops_gpu.py::test_conv_persistent_tiles_are_bit_identical: the 3 x 3 layers the persistent-tile kernel takes
 (conv2d_bf16_pt.h) under whatever CCVS_CONV_PT the parent set (the library reads the switch once per process), results to the .npz
 named on the command line.  Every launch has >= 2 x 256 tiles (fewer keep the producer / consumer kernel) and an odd tile count per
-workgroup somewhere (the two register sets of the staging stream change roles from tile to tile)."""
+workgroup somewhere (the two register sets of the staging stream change roles from tile to tile).
+
+With `budget` as a second argument it is the worker of tests/test_cu_budget_gpu.py::test_packed_convolutions_under_a_budget instead: the
+packed (P8) layers of the InterBlock chain with `ccvs_conv_desc.cu_limit` = 3, 61 and 0 (in that order, every result kept alive, so
+that no launch gets memory an earlier one has filled), with their inputs and weights for the parent's float64 reference."""
 import os
 import sys
 
@@ -24,6 +28,40 @@ def layer(cin, cout):
     w = rnd(cout, cin, 3, 3, scale=(9 * cin) ** -0.5)
     return ops.pack_conv_weight(w), rnd(cout)
 
+
+def budget_cases():
+    n, h, w = 6, 40, 64
+    x, pre = rnd(n, 99, h, w), rnd(n // 3, 128, h, w)
+    raw = {name: (rnd(cout, cin, 3, 3), rnd(cout)) for name, cin, cout in (("l1", 99, 128), ("l2", 128, 64), ("l3", 64, 32))}
+    packs = {name: ops.pack_conv_weight(wt) for name, (wt, _) in raw.items()}
+    out.update(x=x, pre=pre)
+    for name, (wt, b) in raw.items():
+        out[f"w_{name}"], out[f"b_{name}"] = wt, b
+
+    def sweep(name, run):
+        for lim in (3, 61, 0):
+            ops.CONV_CU_LIMIT = lim
+            try:
+                out[f"{name}_{lim}"] = run()
+            finally:
+                ops.CONV_CU_LIMIT = 0
+    # fp32 input -> packed output, the shared pre-activation image of the first Subpixel convolution
+    sweep("l1", lambda: ops.conv2d(x, packs["l1"], raw["l1"][1], 128, 3, pad=1, act=True, pre=pre, pre_div=3, out_p8=True).data)
+    out["in_l2"] = out["l1_0"]
+    a8 = ops.P8Act(out["in_l2"], n, 128, h, w)
+    # packed input -> fp32 output
+    sweep("l2", lambda: ops.conv2d(a8, packs["l2"], raw["l2"][1], 64, 3, pad=1, act=True))
+    out["in_l3"] = ops.conv2d(a8, packs["l2"], raw["l2"][1], 64, 3, pad=1, act=True, out_p8=True).data
+    b8 = ops.P8Act(out["in_l3"], n, 64, h, w)
+    # packed input -> packed output
+    sweep("l3", lambda: ops.conv2d(b8, packs["l3"], raw["l3"][1], 32, 3, pad=1, act=True, out_p8=True).data)
+
+
+if sys.argv[2:] == ["budget"]:
+    budget_cases()
+    torch.cuda.synchronize()
+    np.savez(sys.argv[1], **{k: v.cpu().numpy() for k, v in out.items()})
+    sys.exit(0)
 
 # fp32 input, 128 output channels: 99 (K tail r = 3), 49 (r = 1), 195, 96 (no tail), 128; 64 x 64 images (16 tiles of 8 x 32, 8 of 16 x 32 each), 72 images = 1152 / 576 tiles: 4.5 / 2.25 per workgroup
 for cin in (99, 49, 195, 96, 128):
