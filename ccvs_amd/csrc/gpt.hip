@@ -167,7 +167,7 @@ struct Gemm16 {
 
 #define GEMM_U 4  // one-block form: K steps (of 16) whose loads are issued together (4 float4 of W + 4 of x per lane: the 48-VGPR budget)
 #define GEMM_U_RB 8  // the same for the prefill form (512 threads, its own CU)
-#define GEMM_WS_TILES 1024  // 16 x 16 output tiles a workspace covers (64 column tiles x 16 row blocks: every split-K launch fits)
+#define GEMM_WS_TILES 1024  // 16 x 16 output tiles a workspace covers (64 column tiles x 16 row blocks: gemm_kz splits K only where every decode launch fits)
 #define GEMM_KZ_MAX 4       // cap of the split-K depth of the decode GEMMs (the workspace holds GEMM_KZ_MAX slabs per tile)
 #define GEMM_KZ_MIN_K 2048  // the shallowest K that is split over workgroups
 #define GEMM_DECODE_MAX_M 256  // up to this many rows the weight-stream kernel below runs; beyond, the prefill form
@@ -682,11 +682,13 @@ __global__ __launch_bounds__(256, 4) void gemm_seq_kernel(Gemm16 p, int row_tile
 // K slices across workgroups (split-K): spreads GEMMs with few output columns over the chip.  Pays only for deep K:
 // the release/acquire hand-off costs ~3-4 us (measured).
 // A function of N and K only -- never of M -- so that a row's K partition, hence its rounding,
-// does not depend on how many rows share the launch.
+// does not depend on how many rows share the launch.  Hence only where the workspace covers the blocks of EVERY decode launch
+// of these N columns, GEMM_DECODE_MAX_M rows included (at most 64 column tiles): whether this launch's rows happen to fit is
+// not asked.
 static int gemm_kz(const Gemm16& g) {
     const int tiles = cdiv(g.N, 16);
     int kz = 1;
-    if (g.ws_slabs && !g.ln_s)
+    if (g.ws_slabs && !g.ln_s && tiles * cdiv(GEMM_DECODE_MAX_M, 16) <= GEMM_WS_TILES)
         while (g.K >= GEMM_KZ_MIN_K && kz < GEMM_KZ_MAX && tiles * kz * 2 <= 256 && g.K % (16 * GEMM_WAVES * kz * 2) == 0) kz *= 2;
     return kz;
 }
@@ -710,7 +712,6 @@ enum GemmForm { GEMM_FORM_TILE1, GEMM_FORM_TILE2, GEMM_FORM_RB, GEMM_FORM_SEQ };
 static GemmForm gemm16_plan(Gemm16& g) {
     const bool decode_form = !g.seq && g.M <= GEMM_DECODE_MAX_M;
     g.kz = decode_form ? gemm_kz(g) : 1;
-    if (g.kz > 1 && cdiv(g.N, 16) * cdiv(g.M, 16) > GEMM_WS_TILES) g.kz = 1;   // cannot happen for M <= 256 (kz > 1 needs <= 64 column tiles)
     g.ks = decode_form ? GEMM_WAVES : 8;
     while (g.ks > 1 && g.K % (16 * g.ks * g.kz) != 0) g.ks >>= 1;
     // 2 x 2 blocks from three row blocks on (stacked batches): with two, N / 32 workgroups are too few alone (2.03 against 1.53 ms per step)
@@ -720,6 +721,11 @@ static GemmForm gemm16_plan(Gemm16& g) {
     return g.seq && seq_dense && fits ? GEMM_FORM_SEQ : GEMM_FORM_RB;
 }
 
+// gemm_kz grants split-K only where the workspace holds every block of a decode launch (M <= GEMM_DECODE_MAX_M): a planned launch that
+// outgrows it is a bug in this file -- refused by both forms of the step, never run on another K partition (a row's bits would then
+// depend on M) or past the workspace's end
+static bool gemm_ws_holds(const Gemm16& g) { return g.kz == 1 || cdiv(g.N, 16) * cdiv(g.M, 16) <= GEMM_WS_TILES; }
+
 static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
     if (!(g.x && g.w && g.y)) { ccvs_set_error("%s: null pointer", name); return CCVS_ERR_ARG; }
     if (!(g.M > 0 && g.N > 0 && g.K > 0)) { ccvs_set_error("%s: empty tensor", name); return CCVS_ERR_ARG; }
@@ -727,6 +733,7 @@ static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
     if (g.epi < 0 || g.epi > 2 || (g.epi == 2 && !g.res)) { ccvs_set_error("%s: bad epilogue", name); return CCVS_ERR_ARG; }
     const GemmForm form = gemm16_plan(g);
     const bool decode_form = form == GEMM_FORM_TILE1 || form == GEMM_FORM_TILE2;
+    if (!gemm_ws_holds(g)) { ccvs_set_error("%s: split-K over %d x %d blocks outgrows the workspace", name, cdiv(g.M, 16), cdiv(g.N, 16)); return CCVS_ERR_ARG; }
     if (decode_form && ((long)g.N * g.K * 4 >= (1L << 31) || (long)g.M * g.ldx * 4 >= (1L << 31))) {
         ccvs_set_error("%s: operand beyond 2^31 bytes (32-bit buffer offsets)", name);
         return CCVS_ERR_ARG;
@@ -1810,7 +1817,7 @@ extern "C" int ccvs_gpt_decode_prepare(const ccvs_gpt_decode* d, void* stream) {
     const GemmForm tile = step_tile2(d) ? GEMM_FORM_TILE2 : GEMM_FORM_TILE1;
     int n = 0;
     rc = step_phases(d, "ccvs_gpt_decode_prepare", [&](int kind, Gemm16& g, const char* name) -> int {
-        if (n == n_ph || (kind == STEP_GEMM && gemm16_plan(g) != tile)) { ccvs_set_error("ccvs_gpt_decode_prepare: %s does not fit the persistent step's table", name); return CCVS_ERR_ARG; }
+        if (n == n_ph || (kind == STEP_GEMM && (gemm16_plan(g) != tile || !gemm_ws_holds(g)))) { ccvs_set_error("ccvs_gpt_decode_prepare: %s does not fit the persistent step's table", name); return CCVS_ERR_ARG; }
         prog[n].kind = kind;
         prog[n++].g = g;
         return CCVS_OK;

@@ -711,13 +711,14 @@ def gemm_ln(x, wg, bb, s, eps=1e-5, epilogue=EPI_NONE, out=None):
     return out
 
 
-def gemm_ln_qkv(x, wg, bb, s, kcache, vcache, b, tq, pos0, pos_dev=None, eps=1e-5):
-    """ln1 + fused QKV projection: returns q [b*tq, C]; K / V go straight into the caches."""
-    _need_gpu(x, wg, bb, s, kcache, vcache, pos_dev)
+def gemm_ln_qkv(x, wg, bb, s, kcache, vcache, b, tq, pos0, pos_dev=None, eps=1e-5, out=None):
+    """ln1 + fused QKV projection: returns q [b*tq, C] (`out`, dense, when given); K / V go straight into the caches."""
+    _need_gpu(x, wg, bb, s, kcache, vcache, pos_dev, out)
     c = x.shape[1]
     _, h, tmax, d = kcache.shape
     assert x.shape[0] == b * tq and x.stride(1) == 1 and wg.shape == (3 * c, c) and h * d == c
-    q = torch.empty(b * tq, c, dtype=torch.float32, device=x.device)
+    q = out if out is not None else torch.empty(b * tq, c, dtype=torch.float32, device=x.device)
+    assert q.shape == (b * tq, c) and q.dtype == torch.float32 and q.is_contiguous()   # the C ABI takes q with row stride C
     L = _lib.load()
     _lib.check(L.ccvs_gemm_ln_qkv(_p(x), x.stride(0), _p(wg), _p(bb), _p(s), eps, _p(q), _p(kcache), _p(vcache), b, tq, c, h, pos0,
                                   _p(pos_dev), tmax, _stream()), "ccvs_gemm_ln_qkv")
