@@ -68,6 +68,8 @@ static inline unsigned limited_grid(long blocks, void* stream, int per_cu) {
 // ran at 0.6 of what a plain copy reaches on this chip (tools/mem_bench.py).
 struct __attribute__((packed, aligned(4))) F32Pair { float x, y; };
 struct __attribute__((packed, aligned(4))) F32Quad { float v[4]; };
+// a lane's PX consecutive pixels of a row in the kernels written once for several pixels per lane: a float, ..., an F32Quad
+template <int PX> struct __attribute__((packed, aligned(4))) F32Row { float v[PX]; };
 
 // The library's run-time switches (CCVS_CORR_PAIR, CCVS_WARP_TILED, CCVS_CONV_PT, CCVS_GEMM_SEQ_DENSE, CCVS_GEMM_TILE2: DESIGN.md
 // "Switches") are read here and nowhere else, each once into a function-local static of its launcher.
@@ -78,6 +80,11 @@ static inline int getenv_int(const char* name, int dflt) {
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// workgroups of a grid-stride kernel (256 threads) over `work` items: one per 256 items, at most 2^20, under the stream's CU budget
+static inline unsigned strided_grid(long work, void* stream, int per_cu) {
+    const long blocks = cdiv64(work, 256);
+    return limited_grid(blocks < 65536 * 16 ? blocks : 65536 * 16, stream, per_cu);
+}
 
 __device__ __forceinline__ float lrelu01(float v) { return v > 0.f ? v : 0.1f * v; }
 

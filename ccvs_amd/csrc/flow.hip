@@ -242,23 +242,37 @@ extern "C" int ccvs_correlation7x7(const float* first, const float* second, floa
 // (skip_autoencoder.py:120-128).  Sample position in input pixels, following the
 // reference's arithmetic: g = (2x+1)/W - 1 + f / ((W-1)/2);  ix = ((g+1)*W - 1)/2.
 // ---------------------------------------------------------------------------------------
-struct Bilin {
-    int o00, o01, o10, o11;  // plane offsets (clamped to 0 when outside, weight then 0)
+// the four weights and the integer corner (x0, y0) of a sample: the ONE copy of the coordinate arithmetic
+struct BilinPos {
     float w00, w01, w10, w11;
+    int x0, y0;
 };
 
-__device__ __forceinline__ Bilin bilin_setup(int x, int y, float fx, float fy, int H, int W) {
+__device__ __forceinline__ BilinPos bilin_pos(int x, int y, float fx, float fy, int H, int W) {
     const float gx = ((2.f * x + 1.f) / W - 1.f) + fx / ((W - 1.0f) / 2.0f);
     const float gy = ((2.f * y + 1.f) / H - 1.f) + fy / ((H - 1.0f) / 2.0f);
     const float ix = ((gx + 1.f) * W - 1.f) * 0.5f;
     const float iy = ((gy + 1.f) * H - 1.f) * 0.5f;
     const float x0f = floorf(ix), y0f = floorf(iy);
     const float tx = ix - x0f, ty = iy - y0f;
-    Bilin b;
-    b.w00 = (1.f - tx) * (1.f - ty); b.w01 = tx * (1.f - ty); b.w10 = (1.f - tx) * ty; b.w11 = tx * ty;
+    BilinPos p;
+    p.w00 = (1.f - tx) * (1.f - ty); p.w01 = tx * (1.f - ty); p.w10 = (1.f - tx) * ty; p.w11 = tx * ty;
     // clamp before the int conversion so that huge flows cannot overflow
     const float xc = fminf(fmaxf(x0f, -2.f), (float)W + 1.f), yc = fminf(fmaxf(y0f, -2.f), (float)H + 1.f);
-    const int x0 = (int)xc, y0 = (int)yc, x1 = x0 + 1, y1 = y0 + 1;
+    p.x0 = (int)xc; p.y0 = (int)yc;
+    return p;
+}
+
+struct Bilin {
+    int o00, o01, o10, o11;  // plane offsets (clamped to 0 when outside, weight then 0)
+    float w00, w01, w10, w11;
+};
+
+__device__ __forceinline__ Bilin bilin_setup(int x, int y, float fx, float fy, int H, int W) {
+    const BilinPos p = bilin_pos(x, y, fx, fy, H, W);
+    Bilin b;
+    b.w00 = p.w00; b.w01 = p.w01; b.w10 = p.w10; b.w11 = p.w11;
+    const int x0 = p.x0, y0 = p.y0, x1 = x0 + 1, y1 = y0 + 1;
     const bool vx0 = (x0 >= 0 && x0 < W), vx1 = (x1 >= 0 && x1 < W), vy0 = (y0 >= 0 && y0 < H), vy1 = (y1 >= 0 && y1 < H);
     // corners outside the image: weight 0 and a clamped (valid) offset, so that the four loads of a
     // sample are unconditional (predicated loads in the channel loop would serialise)
@@ -292,15 +306,9 @@ struct BilinWin {
 };
 
 __device__ __forceinline__ BilinWin bilin_setup_win(int x, int y, float fx, float fy, int H, int W) {
-    const float gx = ((2.f * x + 1.f) / W - 1.f) + fx / ((W - 1.0f) / 2.0f);
-    const float gy = ((2.f * y + 1.f) / H - 1.f) + fy / ((H - 1.0f) / 2.0f);
-    const float ix = ((gx + 1.f) * W - 1.f) * 0.5f;
-    const float iy = ((gy + 1.f) * H - 1.f) * 0.5f;
-    const float x0f = floorf(ix), y0f = floorf(iy);
-    const float tx = ix - x0f, ty = iy - y0f;
-    const float w00 = (1.f - tx) * (1.f - ty), w01 = tx * (1.f - ty), w10 = (1.f - tx) * ty, w11 = tx * ty;
-    const float xc = fminf(fmaxf(x0f, -2.f), (float)W + 1.f), yc = fminf(fmaxf(y0f, -2.f), (float)H + 1.f);
-    const int x0 = (int)xc, y0 = (int)yc, y1 = y0 + 1;
+    const BilinPos p = bilin_pos(x, y, fx, fy, H, W);
+    const float w00 = p.w00, w01 = p.w01, w10 = p.w10, w11 = p.w11;
+    const int x0 = p.x0, y0 = p.y0, y1 = y0 + 1;
     const bool vy0 = (y0 >= 0 && y0 < H), vy1 = (y1 >= 0 && y1 < H);
     BilinWin b;
     BilinPair& q = b.q;
@@ -338,8 +346,18 @@ __device__ __forceinline__ float bilin_sample_pair(const float* __restrict__ pla
     return bilin_mix(r0, r1, q);
 }
 
-#define WARP_CCH 16  // channels per thread
-#define WARP4_CCH 8  // ... of the four-pixel kernels
+// The warp kernels below exist in a one-pixel form (PX = 1: Bilin, four independent corner loads; any W) and the four-pixel form
+// (PX = 4: BilinPair, 8-byte pair loads; W % 4 == 0) described above: one body each, the sample type and the row type chosen by PX.
+template <int PX> struct BilinOf { typedef BilinPair type; };
+template <> struct BilinOf<1> { typedef Bilin type; };
+template <int PX>
+__device__ __forceinline__ typename BilinOf<PX>::type bilin_setup_px(int x, int y, float fx, float fy, int H, int W) {
+    if constexpr (PX == 1) return bilin_setup(x, y, fx, fy, H, W);
+    else return bilin_setup_pair(x, y, fx, fy, H, W);
+}
+__device__ __forceinline__ float bilin_sample(const float* __restrict__ plane, const BilinPair& q) { return bilin_sample_pair(plane, q); }
+
+constexpr int warp_cch(int px) { return px == 1 ? 16 : 8; }  // channels per thread of the one-pixel / four-pixel kernels
 
 // The k context features of a decode step live in slots of the per-level context ring (and, point-to-point, in a
 // separate tensor): item n of the batch of N*k pairs reads source ctx.p[n % k] + (n / k) * ctx.sN[n % k], so the
@@ -350,25 +368,6 @@ struct CtxList {
     const float* p[CCVS_MAX_CTX];
     long sN[CCVS_MAX_CTX];
 };
-
-__global__ __launch_bounds__(256) void backwarp_kernel(CtxList ctx, long x_sC,
-                                                       const float* __restrict__ flow, long flow_sN, float mult,
-                                                       float* __restrict__ y, long y_sN, long y_sC, int C, int H, int W, GridWalk gw) {
-    const int HW = H * W;
-    GRID_WALK_BEGIN(gw, bx, by, bz)
-    const int pix = bx * 256 + threadIdx.x;
-    if (pix >= HW) continue;
-    const int n = bz, c0 = by * WARP_CCH;
-    const int jn = n % ctx.k;
-    const float* x = ctx.p[jn] + (long)(n / ctx.k) * ctx.sN[jn];
-    const int py = pix / W, px = pix - py * W;
-    const float fx = flow[(long)n * flow_sN + pix] * mult, fy = flow[(long)n * flow_sN + HW + pix] * mult;
-    const Bilin b = bilin_setup(px, py, fx, fy, H, W);
-    const int cend = min(c0 + WARP_CCH, C);
-    for (int c = c0; c < cend; ++c)
-        y[(long)n * y_sN + (long)c * y_sC + pix] = bilin_sample(x + (long)c * x_sC, b);
-    GRID_WALK_END
-}
 
 // First pixel of a thread's quad in the four-pixel warp kernels.  Plain: block bx = 1024 consecutive pixels (4 rows of a 256-wide
 // image).  Tiled: block bx = a tile of 4 t x 256 / t pixels, t threads along a row (t = GridWalk.tiled = 16: 64 x 16; needs W % 4t == 0,
@@ -395,44 +394,58 @@ __device__ __forceinline__ int quad_pixel(const GridWalk& gw, int bx, int W) {
     return (bx * 256 + (int)threadIdx.x) * 4;
 }
 
-__global__ __launch_bounds__(256) void backwarp4_kernel(CtxList ctx, long x_sC, const float* __restrict__ flow, long flow_sN, float mult,
-                                                        float* __restrict__ y, long y_sN, long y_sC, int C, int H, int W, GridWalk gw) {
+template <int PX>
+__device__ __forceinline__ int lane_pixel(const GridWalk& gw, int bx, int W) {
+    if constexpr (PX == 1) return bx * 256 + threadIdx.x;
+    else return quad_pixel(gw, bx, W);
+}
+
+template <int PX>
+__global__ __launch_bounds__(256) void backwarp_kernel(CtxList ctx, long x_sC, const float* __restrict__ flow, long flow_sN, float mult,
+                                                       float* __restrict__ y, long y_sN, long y_sC, int C, int H, int W, GridWalk gw) {
+    typedef F32Row<PX> Row;
     const int HW = H * W;
     GRID_WALK_BEGIN(gw, bx, by, bz)
-    const int pix = quad_pixel(gw, bx, W);
+    const int pix = lane_pixel<PX>(gw, bx, W);
     if (pix >= HW) continue;
-    const int n = bz, c0 = by * WARP4_CCH;
+    const int n = bz, c0 = by * warp_cch(PX);
     const int jn = n % ctx.k;
     const float* x = ctx.p[jn] + (long)(n / ctx.k) * ctx.sN[jn];
     const int py = pix / W, px = pix - py * W;
-    const F32Quad fx = *reinterpret_cast<const F32Quad*>(flow + (long)n * flow_sN + pix);
-    const F32Quad fy = *reinterpret_cast<const F32Quad*>(flow + (long)n * flow_sN + HW + pix);
-    BilinPair q[4];
+    const Row fx = *reinterpret_cast<const Row*>(flow + (long)n * flow_sN + pix);
+    const Row fy = *reinterpret_cast<const Row*>(flow + (long)n * flow_sN + HW + pix);
+    typename BilinOf<PX>::type q[PX];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) q[i] = bilin_setup_pair(px + i, py, fx.v[i] * mult, fy.v[i] * mult, H, W);
-    const int cend = min(c0 + WARP4_CCH, C);
+    for (int i = 0; i < PX; ++i) q[i] = bilin_setup_px<PX>(px + i, py, fx.v[i] * mult, fy.v[i] * mult, H, W);
+    const int cend = min(c0 + warp_cch(PX), C);
     for (int c = c0; c < cend; ++c) {
         const float* pl = x + (long)c * x_sC;
-        F32Quad o;
+        Row o;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) o.v[i] = bilin_sample_pair(pl, q[i]);
-        *reinterpret_cast<F32Quad*>(y + (long)n * y_sN + (long)c * y_sC + pix) = o;
+        for (int i = 0; i < PX; ++i) o.v[i] = bilin_sample(pl, q[i]);
+        *reinterpret_cast<Row*>(y + (long)n * y_sN + (long)c * y_sC + pix) = o;
     }
     GRID_WALK_END
 }
 
+static int fill_ctx(CtxList& l, const ccvs_ctx_list* c, const char* name) {
+    if (!c || c->k < 1 || c->k > CCVS_MAX_CTX) { ccvs_set_error("%s: context list of 1..%d entries expected", name, CCVS_MAX_CTX); return CCVS_ERR_ARG; }
+    l.k = c->k;
+    for (int j = 0; j < c->k; ++j) {
+        if (!c->p[j]) { ccvs_set_error("%s: null context %d", name, j); return CCVS_ERR_ARG; }
+        l.p[j] = c->p[j];
+        l.sN[j] = (long)c->sN[j];
+    }
+    return CCVS_OK;
+}
+
 static void launch_backwarp(const CtxList& l, long x_sC, const float* flow, long flow_sN, float mult, float* y, long y_sN, long y_sC, int N, int C,
                             int H, int W, void* stream) {
-    if (W % 4 == 0) {
-        GridWalk gw = grid_walk(cdiv(H * W / 4, 256), cdiv(C, WARP4_CCH), N);
-        gw.tiled = warp_tiled(H, W);
-        hipLaunchKernelGGL(backwarp4_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, l, x_sC, flow, flow_sN, mult,
-                           y, y_sN, y_sC, C, H, W, gw);
-    } else {
-        const GridWalk gw = grid_walk(cdiv(H * W, 256), cdiv(C, WARP_CCH), N);
-        hipLaunchKernelGGL(backwarp_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, l, x_sC, flow, flow_sN, mult,
-                           y, y_sN, y_sC, C, H, W, gw);
-    }
+    const int px = W % 4 == 0 ? 4 : 1;
+    GridWalk gw = grid_walk(cdiv(H * W / px, 256), cdiv(C, warp_cch(px)), N);
+    if (px == 4) gw.tiled = warp_tiled(H, W);
+    hipLaunchKernelGGL(px == 4 ? backwarp_kernel<4> : backwarp_kernel<1>, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream,
+                       l, x_sC, flow, flow_sN, mult, y, y_sN, y_sC, C, H, W, gw);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -440,13 +453,13 @@ static void launch_backwarp(const CtxList& l, long x_sC, const float* flow, long
 // (skip_autoencoder.py:222-224) as [N][C/8 + 1][hi|lo][H][W] units of 8 bf16 -- the form the convolution kernel stages by
 // LDS-DMA, no conversion.  A lane owns ONE pixel and 8 channels: its two 16-byte units are the store width the four-pixel form
 // was built for, and consecutive lanes write consecutive units.  Group C/8 holds (flow x, flow y, occlusion, 0 x 5) as stored
-// (the warp itself uses flow * mult).  Same samples as backwarp4_kernel (bilin_setup_pair / bilin_sample_pair), split like the
+// (the warp itself uses flow * mult).  Same samples as backwarp_kernel<4> (bilin_setup_pair / bilin_sample_pair), split like the
 // convolution's staging waves split them (round to nearest even twice; split8 of common.h, the one definition both call): the
 // convolution sees the same operands.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void backwarp_p8_kernel(CtxList ctx, long x_sC, const float* __restrict__ fo, long fo_sN, float mult,
                                                           uint4* __restrict__ y, int C, int H, int W, GridWalk gw) {
-    // lane = 4 consecutive pixels x 8 channels, sampled exactly like backwarp4_kernel (same values bit for bit); the 32 results
+    // lane = 4 consecutive pixels x 8 channels, sampled exactly like backwarp_kernel<4> (same values bit for bit); the 32 results
     // leave as 4 x (hi, lo) 16-byte units, one pixel each.  (One pixel per lane -- consecutive lanes writing consecutive units --
     // was built first and lost 40-70 % on the LOAD side: 4.1-5.0 ms against 2.9 on 120 x 96 x 256^2.)
     __shared__ uint4 wp_stage[2048];
@@ -509,8 +522,6 @@ __global__ __launch_bounds__(256) void backwarp_p8_kernel(CtxList ctx, long x_sC
     GRID_WALK_END
 }
 
-static int fill_ctx(CtxList& l, const ccvs_ctx_list* c, const char* name);
-
 extern "C" int ccvs_backwarp_p8_ctx(const ccvs_ctx_list* ctx, int64_t x_sC, const float* flow_occ, int64_t fo_sN, float flow_mult, void* y_p8,
                                     int32_t N, int32_t C, int32_t H, int32_t W, void* stream) {
     CCVS_REQUIRE(flow_occ && y_p8, "ccvs_backwarp_p8_ctx: null pointer");
@@ -522,17 +533,6 @@ extern "C" int ccvs_backwarp_p8_ctx(const ccvs_ctx_list* ctx, int64_t x_sC, cons
     hipLaunchKernelGGL(backwarp_p8_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, l, (long)x_sC, flow_occ,
                        (long)fo_sN, flow_mult, (uint4*)y_p8, C, H, W, gw);
     CCVS_CHECK_LAUNCH("ccvs_backwarp_p8_ctx");
-    return CCVS_OK;
-}
-
-static int fill_ctx(CtxList& l, const ccvs_ctx_list* c, const char* name) {
-    if (!c || c->k < 1 || c->k > CCVS_MAX_CTX) { ccvs_set_error("%s: context list of 1..%d entries expected", name, CCVS_MAX_CTX); return CCVS_ERR_ARG; }
-    l.k = c->k;
-    for (int j = 0; j < c->k; ++j) {
-        if (!c->p[j]) { ccvs_set_error("%s: null context %d", name, j); return CCVS_ERR_ARG; }
-        l.p[j] = c->p[j];
-        l.sN[j] = (long)c->sN[j];
-    }
     return CCVS_OK;
 }
 
@@ -733,7 +733,7 @@ extern "C" int ccvs_backwarp_proj_ctx(const ccvs_ctx_list* ctx, int64_t x_sC, co
 // ---------------------------------------------------------------------------------------
 // InterBlock tail (skip_autoencoder.py:254-264): warp each of the k context features with
 // its final flow, fuse with confidences 1 - sigmoid(occ_k) + eps, blend into the decoder
-// feature with sigmoid of the fused occlusion.  One lane per pixel, WARP_CCH channels per
+// feature with sigmoid of the fused occlusion.  One lane per pixel, warp_cch(1) channels per
 // thread; the per-k sample set-up is recomputed per channel chunk (3 floats per k).
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ float sigmoidf_(float v) { return 1.f / (1.f + expf(-v)); }
@@ -746,12 +746,12 @@ __global__ __launch_bounds__(256) void warp_fuse_blend_kernel(float* __restrict_
     GRID_WALK_BEGIN(gw, bx, by, bz)
     const int pix = bx * 256 + threadIdx.x;
     if (pix >= HW) continue;
-    const int n = bz, c0 = by * WARP_CCH;
+    const int n = bz, c0 = by * warp_cch(1);
     const int py = pix / W, px = pix - py * W;
-    const int cn = min(WARP_CCH, C - c0);
-    float acc[WARP_CCH];
+    const int cn = min(warp_cch(1), C - c0);
+    float acc[warp_cch(1)];
 #pragma unroll
-    for (int j = 0; j < WARP_CCH; ++j) acc[j] = 0.f;
+    for (int j = 0; j < warp_cch(1); ++j) acc[j] = 0.f;
     float sum_conf = 0.f, sum_occ = 0.f;
     for (int kk = 0; kk < k; ++kk) {
         const long nk = (long)n * k + kk;
@@ -763,13 +763,13 @@ __global__ __launch_bounds__(256) void warp_fuse_blend_kernel(float* __restrict_
         const Bilin b = bilin_setup(px, py, fx, fy, H, W);
         const float* base = ctx.p[kk] + (long)n * ctx.sN[kk] + (long)c0 * HW;
 #pragma unroll
-        for (int j = 0; j < WARP_CCH; ++j)
+        for (int j = 0; j < warp_cch(1); ++j)
             if (j < cn) acc[j] += conf * bilin_sample(base + (long)j * HW, b);
     }
     const float occ = (k > 1) ? sum_occ / sum_conf : sum_occ;
     const float m = sigmoidf_(occ);
 #pragma unroll
-    for (int j = 0; j < WARP_CCH; ++j) {
+    for (int j = 0; j < warp_cch(1); ++j) {
         if (j < cn) {
             float* d = dec + (long)n * dec_sN + (long)(c0 + j) * dec_sC + pix;
             const float wv = (k > 1) ? acc[j] / sum_conf : acc[j];
@@ -779,7 +779,6 @@ __global__ __launch_bounds__(256) void warp_fuse_blend_kernel(float* __restrict_
     GRID_WALK_END
 }
 
-#define FUSE_CCH 8   // channels per thread of the four-pixel form
 __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict__ dec, long dec_sN, long dec_sC, CtxList ctx,
                                                                const float* __restrict__ flows, long flows_sN, const float* __restrict__ occs,
                                                                long occs_sN, float mult, int k, int C, int H, int W, GridWalk gw) {
@@ -787,12 +786,12 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
     GRID_WALK_BEGIN(gw, bx, by, bz)
     const int pix = quad_pixel(gw, bx, W);
     if (pix >= HW) continue;
-    const int n = bz, c0 = by * FUSE_CCH;
+    const int n = bz, c0 = by * warp_cch(4);
     const int py = pix / W, px = pix - py * W;
-    const int cn = min(FUSE_CCH, C - c0);
-    float acc[FUSE_CCH][4];
+    const int cn = min(warp_cch(4), C - c0);
+    float acc[warp_cch(4)][4];
 #pragma unroll
-    for (int j = 0; j < FUSE_CCH; ++j)
+    for (int j = 0; j < warp_cch(4); ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
     float sum_conf[4] = {0.f, 0.f, 0.f, 0.f}, sum_occ[4] = {0.f, 0.f, 0.f, 0.f};
@@ -820,7 +819,7 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
         }
         const float* base = ctx.p[kk] + (long)n * ctx.sN[kk] + (long)c0 * HW;
 #pragma unroll
-        for (int j = 0; j < FUSE_CCH; ++j)
+        for (int j = 0; j < warp_cch(4); ++j)
             if (j < cn) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) acc[j][i] += conf[i] * bilin_sample_pair(base + (long)j * HW, q[i]);
@@ -830,7 +829,7 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
 #pragma unroll
     for (int i = 0; i < 4; ++i) m[i] = sigmoidf_((k > 1) ? sum_occ[i] / sum_conf[i] : sum_occ[i]);
 #pragma unroll
-    for (int j = 0; j < FUSE_CCH; ++j) {
+    for (int j = 0; j < warp_cch(4); ++j) {
         if (j < cn) {
             F32Quad* d = reinterpret_cast<F32Quad*>(dec + (long)n * dec_sN + (long)(c0 + j) * dec_sC + pix);
             F32Quad dv = *d;
@@ -847,16 +846,11 @@ __global__ __launch_bounds__(256) void warp_fuse_blend4_kernel(float* __restrict
 
 static void launch_warp_fuse_blend(float* dec, long dec_sN, long dec_sC, const CtxList& l, const float* flows, long flows_sN, const float* occs,
                                    long occs_sN, float mult, int N, int k, int C, int H, int W, void* stream) {
-    if (W % 4 == 0) {
-        GridWalk gw = grid_walk(cdiv(H * W / 4, 256), cdiv(C, FUSE_CCH), N);
-        gw.tiled = warp_tiled(H, W);
-        hipLaunchKernelGGL(warp_fuse_blend4_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, dec, dec_sN, dec_sC, l,
-                           flows, flows_sN, occs, occs_sN, mult, k, C, H, W, gw);
-    } else {
-        const GridWalk gw = grid_walk(cdiv(H * W, 256), cdiv(C, WARP_CCH), N);
-        hipLaunchKernelGGL(warp_fuse_blend_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, (hipStream_t)stream, dec, dec_sN, dec_sC, l,
-                           flows, flows_sN, occs, occs_sN, mult, k, C, H, W, gw);
-    }
+    const int px = W % 4 == 0 ? 4 : 1;
+    GridWalk gw = grid_walk(cdiv(H * W / px, 256), cdiv(C, warp_cch(px)), N);
+    if (px == 4) gw.tiled = warp_tiled(H, W);
+    hipLaunchKernelGGL(px == 4 ? warp_fuse_blend4_kernel : warp_fuse_blend_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0,
+                       (hipStream_t)stream, dec, dec_sN, dec_sC, l, flows, flows_sN, occs, occs_sN, mult, k, C, H, W, gw);
 }
 
 extern "C" int ccvs_warp_fuse_blend(float* dec, int64_t dec_sN, int64_t dec_sC, const float* ctx, const float* flows, int64_t flows_sN,
@@ -895,37 +889,19 @@ extern "C" int ccvs_warp_fuse_blend_ctx(float* dec, int64_t dec_sN, int64_t dec_
 // 9x9 heads), and this kernel applies the horizontal taps:
 //   y[n][co][yy][x] (+)= bias[co] + sum_kx T[n][kx*3+co][yy][x + kx]          (T width = W + k - 1)
 // ---------------------------------------------------------------------------------------
+// PX = 4 (W % 4 == 0): a lane owns four consecutive pixels of a row -- every tap is one 16-byte load (dword-aligned in the horizontal
+// form), the result one 16-byte store; per pixel the same sum in the same order as the one-pixel form.
+template <int PX>
 __global__ __launch_bounds__(256) void tap_shift_add_kernel(const float* __restrict__ t, const float* __restrict__ bias,
                                                             float* __restrict__ y, long y_sN, long total, int k, int H, int W,
                                                             int accumulate, int vertical) {
+    typedef F32Row<PX> Row;
     // horizontal: T is [N,3k,H,W+k-1] and tap kx reads column x+kx; vertical: T is [N,3k,H+k-1,W], tap ky reads row yy+ky
     const int Wt = vertical ? W : W + k - 1, Ht = vertical ? H + k - 1 : H;
     const long tap = (long)3 * Ht * Wt + (vertical ? Wt : 1);  // next tap: 3 maps further, one row / column further
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int x = (int)(i % W);
-        long r = i / W;
-        const int yy = (int)(r % H);
-        r /= H;
-        const int co = (int)(r % 3);
-        const long n = r / 3;
-        const float* tp = t + ((n * 3 * k + co) * Ht + yy) * (long)Wt + x;
-        float acc = bias ? bias[co] : 0.f;
-        for (int kk = 0; kk < k; ++kk) acc += tp[kk * tap];
-        float* dst = y + n * y_sN + ((long)co * H + yy) * W + x;
-        *dst = accumulate ? *dst + acc : acc;
-    }
-}
-
-// W % 4 == 0: a lane owns four consecutive pixels of a row -- every tap is one 16-byte load (dword-aligned in the horizontal
-// form), the result one 16-byte store; per pixel the same sum in the same order as the one-pixel form.
-__global__ __launch_bounds__(256) void tap_shift_add4_kernel(const float* __restrict__ t, const float* __restrict__ bias,
-                                                             float* __restrict__ y, long y_sN, long total4, int k, int H, int W,
-                                                             int accumulate, int vertical) {
-    const int Wt = vertical ? W : W + k - 1, Ht = vertical ? H + k - 1 : H;
-    const long tap = (long)3 * Ht * Wt + (vertical ? Wt : 1);
-    const int Wq = W >> 2;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total4; i += (long)gridDim.x * 256) {
-        const int x = (int)(i % Wq) * 4;
+    const int Wq = W >> (PX == 4 ? 2 : 0);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {   // total: lanes' rows of PX pixels
+        const int x = (int)(i % Wq) * PX;
         long r = i / Wq;
         const int yy = (int)(r % H);
         r /= H;
@@ -933,21 +909,27 @@ __global__ __launch_bounds__(256) void tap_shift_add4_kernel(const float* __rest
         const long n = r / 3;
         const float* tp = t + ((n * 3 * k + co) * Ht + yy) * (long)Wt + x;
         const float b = bias ? bias[co] : 0.f;
-        float acc[4] = {b, b, b, b};
+        float acc[PX];
+#pragma unroll
+        for (int j = 0; j < PX; ++j) acc[j] = b;
         for (int kk = 0; kk < k; ++kk) {
-            const F32Quad q = *reinterpret_cast<const F32Quad*>(tp + kk * tap);
+            if constexpr (PX == 1) {
+                acc[0] += tp[kk * tap];
+            } else {
+                const Row q = *reinterpret_cast<const Row*>(tp + kk * tap);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] += q.v[j];
+                for (int j = 0; j < PX; ++j) acc[j] += q.v[j];
+            }
         }
-        F32Quad* dst = reinterpret_cast<F32Quad*>(y + n * y_sN + ((long)co * H + yy) * W + x);
-        F32Quad o;
+        Row* dst = reinterpret_cast<Row*>(y + n * y_sN + ((long)co * H + yy) * W + x);
+        Row o;
         if (accumulate) {
-            const F32Quad d = *dst;
+            const Row d = *dst;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o.v[j] = d.v[j] + acc[j];
+            for (int j = 0; j < PX; ++j) o.v[j] = d.v[j] + acc[j];
         } else {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o.v[j] = acc[j];
+            for (int j = 0; j < PX; ++j) o.v[j] = acc[j];
         }
         *dst = o;
     }
@@ -957,18 +939,10 @@ extern "C" int ccvs_tap_shift_add(const float* t, const float* bias, float* y, i
                                   int32_t accumulate, int32_t vertical, void* stream) {
     CCVS_REQUIRE(t && y, "ccvs_tap_shift_add: null pointer");
     CCVS_REQUIRE(N > 0 && k >= 1 && k <= 9 && H > 0 && W > 0, "ccvs_tap_shift_add: bad shape");
-    const long total = (long)N * 3 * H * W;
-    if (W % 4 == 0 && y_sN % 4 == 0) {
-        const long total4 = total / 4;
-        const unsigned blocks4 = limited_grid(cdiv64(total4, 256) < 65536 * 16 ? cdiv64(total4, 256) : 65536 * 16, stream, 8);
-        hipLaunchKernelGGL(tap_shift_add4_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, t, bias, y, (long)y_sN, total4, k, H, W, accumulate,
-                           vertical ? 1 : 0);
-        CCVS_CHECK_LAUNCH("ccvs_tap_shift_add");
-        return CCVS_OK;
-    }
-    const unsigned blocks = limited_grid(cdiv64(total, 256) < 65536 * 16 ? cdiv64(total, 256) : 65536 * 16, stream, 8);
-    hipLaunchKernelGGL(tap_shift_add_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, t, bias, y, (long)y_sN, total, k, H, W, accumulate,
-                       vertical ? 1 : 0);
+    const int px = (W % 4 == 0 && y_sN % 4 == 0) ? 4 : 1;
+    const long total = (long)N * 3 * H * W / px;
+    hipLaunchKernelGGL(px == 4 ? tap_shift_add_kernel<4> : tap_shift_add_kernel<1>, dim3(strided_grid(total, stream, 8)), dim3(256), 0,
+                       (hipStream_t)stream, t, bias, y, (long)y_sN, total, k, H, W, accumulate, vertical ? 1 : 0);
     CCVS_CHECK_LAUNCH("ccvs_tap_shift_add");
     return CCVS_OK;
 }

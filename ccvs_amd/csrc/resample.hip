@@ -396,27 +396,18 @@ extern "C" int ccvs_upfirdn2d(const float* x, float* y, const float* residual, i
         const GridWalk gw = grid_walk((long)tiles_x * tiles_y, NC, 1);
         hipLaunchKernelGGL(blur4x4_tile_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, st, k, tiles_x, gw);
     } else if (up == 2 && down == 1 && pad0 == 2 && pad1 == 1) {
-        const long work = NC * (long)H * W;
-        const unsigned blocks = limited_grid(cdiv64(work, 256) < 65536 * 16 ? cdiv64(work, 256) : 65536 * 16, stream, 8);
-        if (W % 2 == 0) {
-            const long work2 = NC * (long)H * (W / 2);
-            const unsigned blocks2 = limited_grid(cdiv64(work2, 256) < 65536 * 16 ? cdiv64(work2, 256) : 65536 * 16, stream, 8);
-            hipLaunchKernelGGL(upsample2x2_kernel, dim3(blocks2), dim3(256), 0, st, k);
-        } else {
-            hipLaunchKernelGGL(upsample2_kernel, dim3(blocks), dim3(256), 0, st, k);
-        }
+        if (W % 2 == 0)
+            hipLaunchKernelGGL(upsample2x2_kernel, dim3(strided_grid(NC * (long)H * (W / 2), stream, 8)), dim3(256), 0, st, k);
+        else
+            hipLaunchKernelGGL(upsample2_kernel, dim3(strided_grid(NC * (long)H * W, stream, 8)), dim3(256), 0, st, k);
     } else if (up == 1 && down == 2 && k.Wo >= 32 && k.Ho >= 8) {   // (small planes: the direct form below)
         const int tiles_x = cdiv(k.Wo, DOWN_TW), tiles_y = cdiv(k.Ho, DOWN_TH);
         const GridWalk gw = grid_walk((long)tiles_x * tiles_y, NC, 1);
         hipLaunchKernelGGL(down2_tile_kernel, dim3(limited_grid(gw.total, stream, 8)), dim3(256), 0, st, k, tiles_x, gw);
     } else if (up == 1 && down == 2) {
-        const long work = NC * k.Ho * ((k.Wo + 3) / 4);
-        const unsigned blocks = limited_grid(cdiv64(work, 256) < 65536 * 16 ? cdiv64(work, 256) : 65536 * 16, stream, 8);
-        hipLaunchKernelGGL(down2_kernel, dim3(blocks), dim3(256), 0, st, k);
+        hipLaunchKernelGGL(down2_kernel, dim3(strided_grid(NC * k.Ho * ((k.Wo + 3) / 4), stream, 8)), dim3(256), 0, st, k);
     } else {
-        const long work = NC * k.Ho * k.Wo;
-        const unsigned blocks = limited_grid(cdiv64(work, 256) < 65536 * 16 ? cdiv64(work, 256) : 65536 * 16, stream, 8);
-        hipLaunchKernelGGL(upfirdn2d_generic_kernel, dim3(blocks), dim3(256), 0, st, k);
+        hipLaunchKernelGGL(upfirdn2d_generic_kernel, dim3(strided_grid(NC * k.Ho * k.Wo, stream, 8)), dim3(256), 0, st, k);
     }
     CCVS_CHECK_LAUNCH("ccvs_upfirdn2d");
     return CCVS_OK;
@@ -425,141 +416,70 @@ extern "C" int ccvs_upfirdn2d(const float* x, float* y, const float* residual, i
 // Transposed 4x4 stride-2 pad-1 depthwise filter, gather form: y + 1 = 2*iy + ky.  One thread per INPUT
 // pixel (i, j) produces the output quad (2i..2i+1, 2j..2j+1) from the 3 x 3 input neighbourhood:
 // row 2i takes (ky=1, iy=i), (ky=3, iy=i-1); row 2i+1 takes (ky=0, iy=i+1), (ky=2, iy=i); same along x.
+// PX = 2: the same for TWO input pixels (jx, jx + 1) per thread (W even): 3 x 4 neighbourhood in, a 2 x 4 output block out as two
+// 16-byte stores; per output the sum is that of the one-pixel form.
+// PX = 4: FOUR input pixels (jx .. jx + 3) per thread (W % 4 == 0): a 3 x 6 neighbourhood in -- per row one aligned 16-byte load plus the two
+// edge columns -- and a 2 x 8 output block out as four 16-byte stores.  The two-pixel form spends its time on index arithmetic and
+// 28 load instructions per 32 bytes stored (2.5 TB/s); this one issues 25 per 128 bytes.  Per output the sum of the one-pixel form.
+template <int PX>
 __global__ __launch_bounds__(256) void dwconvT4x4s2_kernel(const float* __restrict__ x, long x_sN, const float* __restrict__ w,
                                                            float* __restrict__ y, long y_sN, long N, int C, int H, int W) {
-    const int Ho = 2 * H, Wo = 2 * W;
-    const long total = N * C * (long)H * W;
+    constexpr int SW = PX == 1 ? 2 : 4;   // floats per store
+    const int Ho = 2 * H, Wo = 2 * W, Wp = W >> (PX == 4 ? 2 : PX == 2 ? 1 : 0);
+    const long total = N * C * (long)H * Wp;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int jx = (int)(i % W);
-        const long t = i / W;
+        const int jx = (int)(i % Wp) * PX;
+        const long t = i / Wp;
         const int iy = (int)(t % H);
         const long nc = t / H;
         const int c = (int)(nc % C);
         const long n = nc / C;
         const float* xp = x + n * x_sN + (long)c * H * W;
         const float* wp = w + c * 16;
-        float v[3][3];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) {
-                const int yy = iy + a - 1, xx = jx + b - 1;
-                const float tv = xp[(long)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)];
-                v[a][b] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? tv : 0.f;
-            }
-        // (output parity, tap) -> neighbourhood index: parity 0: ky {1,3} -> rows {1,0}; parity 1: ky {0,2} -> rows {2,1}
-        const int kyt[2][2] = {{1, 3}, {0, 2}}, nyt[2][2] = {{1, 0}, {2, 1}};
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            float o2[2];
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                float acc = 0.f;
-#pragma unroll
-                for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-                    for (int tb = 0; tb < 2; ++tb) acc += v[nyt[a][ta]][nyt[b][tb]] * wp[kyt[a][ta] * 4 + kyt[b][tb]];
-                o2[b] = acc;
-            }
-            *reinterpret_cast<float2*>(y + n * y_sN + ((long)c * Ho + 2 * iy + a) * Wo + 2 * jx) = make_float2(o2[0], o2[1]);
-        }
-    }
-}
-
-// The same for TWO input pixels (jx, jx + 1) per thread (W even): 3 x 4 neighbourhood in, a 2 x 4 output block out as two
-// 16-byte stores; per output the sum is that of dwconvT4x4s2_kernel.
-__global__ __launch_bounds__(256) void dwconvT4x4s2x2_kernel(const float* __restrict__ x, long x_sN, const float* __restrict__ w,
-                                                             float* __restrict__ y, long y_sN, long N, int C, int H, int W) {
-    const int Ho = 2 * H, Wo = 2 * W, W2 = W >> 1;
-    const long total = N * C * (long)H * W2;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int jx = (int)(i % W2) * 2;
-        const long t = i / W2;
-        const int iy = (int)(t % H);
-        const long nc = t / H;
-        const int c = (int)(nc % C);
-        const long n = nc / C;
-        const float* xp = x + n * x_sN + (long)c * H * W;
-        const float* wp = w + c * 16;
-        float v[3][4];
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int yy = iy + a - 1, xx = jx + b - 1;
-                const float tv = xp[(long)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)];
-                v[a][b] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? tv : 0.f;
-            }
-        const int kyt[2][2] = {{1, 3}, {0, 2}}, nyt[2][2] = {{1, 0}, {2, 1}};
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-            F32Quad o4;
-#pragma unroll
-            for (int bi = 0; bi < 2; ++bi)       // input column jx + bi
-#pragma unroll
-                for (int b = 0; b < 2; ++b) {    // output parity along x
-                    float acc = 0.f;
-#pragma unroll
-                    for (int ta = 0; ta < 2; ++ta)
-#pragma unroll
-                        for (int tb = 0; tb < 2; ++tb) acc += v[nyt[a][ta]][bi + nyt[b][tb]] * wp[kyt[a][ta] * 4 + kyt[b][tb]];
-                    o4.v[2 * bi + b] = acc;
-                }
-            *reinterpret_cast<F32Quad*>(y + n * y_sN + ((long)c * Ho + 2 * iy + a) * Wo + 2 * jx) = o4;
-        }
-    }
-}
-
-// FOUR input pixels (jx .. jx + 3) per thread (W % 4 == 0): a 3 x 6 neighbourhood in -- per row one aligned 16-byte load plus the two
-// edge columns -- and a 2 x 8 output block out as four 16-byte stores.  The two-pixel form spends its time on index arithmetic and
-// 28 load instructions per 32 bytes stored (2.5 TB/s); this one issues 25 per 128 bytes.  Per output the sum of dwconvT4x4s2_kernel.
-__global__ __launch_bounds__(256) void dwconvT4x4s2x4_kernel(const float* __restrict__ x, long x_sN, const float* __restrict__ w,
-                                                             float* __restrict__ y, long y_sN, long N, int C, int H, int W) {
-    const int Ho = 2 * H, Wo = 2 * W, W4 = W >> 2;
-    const long total = N * C * (long)H * W4;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int jx = (int)(i % W4) * 4;
-        const long t = i / W4;
-        const int iy = (int)(t % H);
-        const long nc = t / H;
-        const int c = (int)(nc % C);
-        const long n = nc / C;
-        const float* xp = x + n * x_sN + (long)c * H * W;
-        const float* wp = w + c * 16;
-        float v[3][6];
+        float v[3][PX + 2];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
             const int yy = iy + a - 1;
-            const bool rin = yy >= 0 && yy < H;
-            const float* rp = xp + (long)min(max(yy, 0), H - 1) * W;
-            const F32Quad m = *reinterpret_cast<const F32Quad*>(rp + jx);
-            const float l = rp[max(jx - 1, 0)], r = rp[min(jx + 4, W - 1)];
-            v[a][0] = (rin && jx > 0) ? l : 0.f;
+            if constexpr (PX == 4) {
+                const bool rin = yy >= 0 && yy < H;
+                const float* rp = xp + (long)min(max(yy, 0), H - 1) * W;
+                const F32Quad m = *reinterpret_cast<const F32Quad*>(rp + jx);
+                const float l = rp[max(jx - 1, 0)], r = rp[min(jx + 4, W - 1)];
+                v[a][0] = (rin && jx > 0) ? l : 0.f;
 #pragma unroll
-            for (int b = 0; b < 4; ++b) v[a][1 + b] = rin ? m.v[b] : 0.f;
-            v[a][5] = (rin && jx + 4 < W) ? r : 0.f;
+                for (int b = 0; b < 4; ++b) v[a][1 + b] = rin ? m.v[b] : 0.f;
+                v[a][5] = (rin && jx + 4 < W) ? r : 0.f;
+            } else {
+#pragma unroll
+                for (int b = 0; b < PX + 2; ++b) {
+                    const int xx = jx + b - 1;
+                    const float tv = xp[(long)min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1)];
+                    v[a][b] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? tv : 0.f;
+                }
+            }
         }
+        // (output parity, tap) -> neighbourhood index: parity 0: ky {1,3} -> rows {1,0}; parity 1: ky {0,2} -> rows {2,1}
         const int kyt[2][2] = {{1, 3}, {0, 2}}, nyt[2][2] = {{1, 0}, {2, 1}};
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             float* yp = y + n * y_sN + ((long)c * Ho + 2 * iy + a) * Wo + 2 * jx;
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {        // two 16-byte stores per output row
-                F32Quad o4;
+            for (int h = 0; h < 2 * PX / SW; ++h) {        // 8-byte (PX = 1) or 16-byte stores of an output row
+                F32Row<SW> o;
 #pragma unroll
-                for (int bj = 0; bj < 2; ++bj) {
-                    const int bi = 2 * h + bj;   // input column jx + bi
+                for (int bj = 0; bj < SW / 2; ++bj) {
+                    const int bi = (SW / 2) * h + bj;   // input column jx + bi
 #pragma unroll
-                    for (int b = 0; b < 2; ++b) {
+                    for (int b = 0; b < 2; ++b) {    // output parity along x
                         float acc = 0.f;
 #pragma unroll
                         for (int ta = 0; ta < 2; ++ta)
 #pragma unroll
                             for (int tb = 0; tb < 2; ++tb) acc += v[nyt[a][ta]][bi + nyt[b][tb]] * wp[kyt[a][ta] * 4 + kyt[b][tb]];
-                        o4.v[2 * bj + b] = acc;
+                        o.v[2 * bj + b] = acc;
                     }
                 }
-                *reinterpret_cast<F32Quad*>(yp + 4 * h) = o4;
+                *reinterpret_cast<F32Row<SW>*>(yp + SW * h) = o;
             }
         }
     }
@@ -569,19 +489,10 @@ extern "C" int ccvs_dwconvT4x4s2(const float* x, int64_t x_sN, const float* w, f
                                  int32_t W, void* stream) {
     CCVS_REQUIRE(x && w && y, "ccvs_dwconvT4x4s2: null pointer");
     CCVS_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0, "ccvs_dwconvT4x4s2: empty tensor");
-    const long work = (long)N * C * H * W;
-    const unsigned blocks = limited_grid(cdiv64(work, 256) < 65536 * 16 ? cdiv64(work, 256) : 65536 * 16, stream, 8);
-    if (W % 4 == 0 && x_sN % 4 == 0) {
-        const long work4 = (long)N * C * H * (W / 4);
-        const unsigned blocks4 = limited_grid(cdiv64(work4, 256) < 65536 * 16 ? cdiv64(work4, 256) : 65536 * 16, stream, 8);
-        hipLaunchKernelGGL(dwconvT4x4s2x4_kernel, dim3(blocks4), dim3(256), 0, (hipStream_t)stream, x, (long)x_sN, w, y, (long)y_sN, (long)N, C, H, W);
-    } else if (W % 2 == 0) {
-        const long work2 = (long)N * C * H * (W / 2);
-        const unsigned blocks2 = limited_grid(cdiv64(work2, 256) < 65536 * 16 ? cdiv64(work2, 256) : 65536 * 16, stream, 8);
-        hipLaunchKernelGGL(dwconvT4x4s2x2_kernel, dim3(blocks2), dim3(256), 0, (hipStream_t)stream, x, (long)x_sN, w, y, (long)y_sN, (long)N, C, H, W);
-    } else {
-        hipLaunchKernelGGL(dwconvT4x4s2_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (long)x_sN, w, y, (long)y_sN, (long)N, C, H, W);
-    }
+    const int px = (W % 4 == 0 && x_sN % 4 == 0) ? 4 : (W % 2 == 0 ? 2 : 1);
+    const auto kern = px == 4 ? dwconvT4x4s2_kernel<4> : px == 2 ? dwconvT4x4s2_kernel<2> : dwconvT4x4s2_kernel<1>;
+    hipLaunchKernelGGL(kern, dim3(strided_grid((long)N * C * H * (W / px), stream, 8)), dim3(256), 0, (hipStream_t)stream, x, (long)x_sN, w, y,
+                       (long)y_sN, (long)N, C, H, W);
     CCVS_CHECK_LAUNCH("ccvs_dwconvT4x4s2");
     return CCVS_OK;
 }

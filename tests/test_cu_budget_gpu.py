@@ -24,18 +24,18 @@ the two budgets, so a later change of a tile size fails here instead of silently
                 down2_tile_kernel .......... test_upfirdn2d[down2_tile-pad22], [down2_tile-pad11]
                 down2_kernel ............... test_upfirdn2d[down2]
                 upfirdn2d_generic_kernel ... test_upfirdn2d[generic]
-                dwconvT4x4s2x4 / x2 / (one pixel) ... test_dwconvT[w16], [w18], [w17]
+                dwconvT4x4s2_kernel<4 / 2 / 1> .... test_dwconvT[w16], [w18], [w17]
                 to_rgb_kernel<64 / 16 / 4> . test_to_rgb[G64*], [G16*], [G4*]
   stft.hip      channel_head_kernel<64 / 16 / 4, 4> ... test_channel_head[G64], [G16], [G4];  <64, 1> ... [G64-px1]
   misc.hip      pack_u8_kernel, pack_u8_norm_kernel ... test_pack_u8
   blur.hip      gaussian_blur_kernel ....... test_gaussian_blur
   flow.hip      correlation7x7_kernel<1 / 2> ... test_correlation[one-s1], [one-s1-div2-lrelu], [one-s2]
                 correlation7x7x2_kernel<1 / 2> . test_correlation[pair-s1], [pair-s2]
-                backwarp_kernel / backwarp4_kernel (plain, tiled) ... test_backwarp[*-one], [*-quad], [*-tiled]
+                backwarp_kernel<1> / <4> (plain, tiled) ......... test_backwarp[*-one], [*-quad], [*-tiled]
                 warp_fuse_blend_kernel / warp_fuse_blend4_kernel .... test_warp_fuse_blend[*-one], [*-quad], [*-tiled]
                 warp_proj_kernel / warp_proj4_kernel ................ test_backwarp_proj[one], [quad], [tiled]
                 backwarp_p8_kernel ......... test_backwarp_p8
-                tap_shift_add4_kernel / tap_shift_add_kernel ... test_conv_heads[*-w4], [*-odd]
+                tap_shift_add_kernel<4> / <1> .................. test_conv_heads[*-w4], [*-odd]
 The packed-input / packed-output convolutions (chunked 1-D launches under `ccvs_conv_desc.cu_limit`) are the last test."""
 import math
 import os

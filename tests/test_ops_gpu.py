@@ -849,7 +849,7 @@ def test_backwarp_p8_feeds_the_first_subpixel_convolution(ops, n, k, c, h, w):
     pk = ops.pack_conv_weight(wt)
     a = ops.conv2d(want, pk, b, 128, 3, pad=1, act=True, pre=pre, pre_div=k)
     bb = ops.conv2d(packed, pk, b, 128, 3, pad=1, act=True, pre=pre, pre_div=k)
-    assert torch.equal(a, bb)     # same samples as backwarp4_kernel, same split as the staging waves: the same operands
+    assert torch.equal(a, bb)     # same samples as backwarp_kernel<4>, same split as the staging waves: the same operands
     # ... and against torch on the unpadded 99-channel form of the layer
     ref = torch.nn.functional.conv2d(want[:, :c + 3].cpu(), (wt[:, :c + 3] * (1 / math.sqrt((c + 8) * 9))).cpu(), bias=b.cpu(), padding=1)
     ref = torch.nn.functional.leaky_relu(ref + pre.cpu().repeat_interleave(k, dim=0), 0.1)

@@ -67,6 +67,8 @@ def test_unknown_kernels_raise(widths):
         widths.read_bytes_per_lane("conv2d_next_round_kernel<32>")
     with pytest.raises(KeyError):
         widths.fetch_scale("some_new_stencil_kernel<4>")
+    with pytest.raises(KeyError):
+        widths.read_bytes_per_lane("backwarp_kernel<2>")                            # a pixels-per-lane form that does not exist
 
 
 def test_decoder_stencils_of_the_profiles_are_in_the_table(widths):
@@ -78,6 +80,14 @@ def test_decoder_stencils_of_the_profiles_are_in_the_table(widths):
     lo, hi = widths.fetch_scale("backwarp4_kernel")                      # 8-byte gathers: calibrated on a known byte count in round 6
     assert lo == hi and 1.15 < lo < 1.25
     assert widths.fetch_scale("void blur4x4_tile_kernel(FirK, int, GridWalk)") == (2.0, 2.0)
+    # the kernels templated on pixels per lane: <1> and <4> are told apart, with the widths of the names they replace
+    assert widths.fetch_scale("void backwarp_kernel<4>(CtxList, long, float const*, long, float, float*, long, long, int, int, int, GridWalk)") == (lo, hi)
+    assert widths.fetch_scale("backwarp_kernel<1>") == widths.fetch_scale("backwarp_kernel") == (1.0, 1.0)
+    assert widths.fetch_scale("tap_shift_add_kernel<4>") == widths.fetch_scale("tap_shift_add4_kernel") == (2.0, 2.0)
+    assert widths.fetch_scale("tap_shift_add_kernel<1>") == widths.fetch_scale("tap_shift_add_kernel") == (1.0, 1.0)
+    assert widths.fetch_scale("dwconvT4x4s2_kernel<4>") == widths.fetch_scale("dwconvT4x4s2x4_kernel") == (2.0, 2.0)
+    assert widths.fetch_scale("dwconvT4x4s2_kernel<2>") == widths.fetch_scale("dwconvT4x4s2x2_kernel") == (1.0, 1.0)
+    assert widths.fetch_scale("dwconvT4x4s2_kernel<1>") == (1.0, 1.0)
 
 
 def test_committed_traffic_is_the_corrected_reduction(widths, tmp_path):

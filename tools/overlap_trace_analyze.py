@@ -63,7 +63,7 @@ for flag in (False, True):
         print(f"token kernels while the decoder stream is {'BUSY' if flag else 'idle'}: {len(g)} gaps, mean {1e-3 * sum(g) / len(g):.2f} us, "
               f"median {1e-3 * g[len(g) // 2]:.2f}, p90 {1e-3 * g[int(0.9 * len(g))]:.2f} us; kernel duration mean {1e-3 * sum(d) / max(len(d), 1):.2f} us")
 # decoder kernels: duration of the big convolution chunks when token kernels run beside them
-for name in ("pc_kernel<32, 4, 3>", "backwarp_kernel"):
+for name in ("pc_kernel<32, 4, 3>", "backwarp_kernel<4>"):
     d = [e - s for s, e, n, q in dec if name in n]
     if d:
         print(f"{name}: {len(d)} launches, mean {1e-3 * sum(d) / len(d):.1f} us")

@@ -16,7 +16,7 @@ python3 - <<'PY'
 import csv, glob, collections, re, os, sys
 sys.path.insert(0, os.path.join(os.environ.get("GRAFT_REPO_ROOT", "/root/repo"), "tools"))
 import pmc_widths
-names = ("correlation7x7", "backwarp4", "warp_fuse_blend4", "warp_proj4", "blur4x4_tile", "down2", "dwconvT4x4s2", "tap_shift_add", "upsample2x2")
+names = ("correlation7x7", "backwarp_kernel<4>", "warp_fuse_blend4", "warp_proj4", "blur4x4_tile", "down2", "dwconvT4x4s2", "tap_shift_add", "upsample2x2")
 def short(n):
     for k in names:
         if k in n: return k

@@ -32,6 +32,11 @@ STENCIL_READ_BYTES = {
     "correlation7x7x2_kernel": 4, "correlation7x7_kernel": 4,   # halo elements and `first` values dword by dword
     "backwarp4_kernel": None,         # flow rows 16 B, the bilinear taps as 8-byte pairs from gathered addresses
     "backwarp_p8_kernel": None, "warp_proj4_kernel": None, "warp_fuse_blend4_kernel": None,
+    # the kernels written once for several pixels per lane (template <int PX>): the full base name is looked up before the stem;
+    # the names above stay for the committed profiles
+    "dwconvT4x4s2_kernel<4>": 16, "dwconvT4x4s2_kernel<2>": 4, "dwconvT4x4s2_kernel<1>": 4,
+    "tap_shift_add_kernel<4>": 16, "tap_shift_add_kernel<1>": 4,
+    "backwarp_kernel<4>": None, "backwarp_kernel<1>": 4,
 }
 
 
@@ -73,7 +78,11 @@ def read_bytes_per_lane(kernel_name):
         if b not in (4, 16):
             raise KeyError(f"convolution kernel `{name}` is not classified by ccvs_conv_fetch_bytes_per_lane (conv_common.h: conv_nty_*)")
         return b
+    if name in STENCIL_READ_BYTES:
+        return STENCIL_READ_BYTES[name]
     stem = re.sub(r"<.*$", "", name)
+    if stem != name and any(k.startswith(stem + "<") for k in STENCIL_READ_BYTES):   # a PX form nobody classified
+        raise KeyError(f"kernel `{name}` has no entry in tools/pmc_widths.py:STENCIL_READ_BYTES")
     if stem not in STENCIL_READ_BYTES:
         raise KeyError(f"kernel `{name}` has no entry in tools/pmc_widths.py:STENCIL_READ_BYTES")
     return STENCIL_READ_BYTES[stem]
