@@ -9,8 +9,21 @@
 #include "common.h"
 
 // ---- PSNR / MSE ------------------------------------------------------------------------------
-// sum ((x - y) * inv_range)^2 over `count` elements by one 1024-thread workgroup, in float64: per lane, per wave, then the 16 waves
-// in index order (the same bits on every run).  The total is valid in thread 0.
+// the lanes' float64 partial sums of one 1024-thread workgroup: per wave, then the 16 waves in index order (the same bits on every
+// run).  The total is valid in thread 0.
+__device__ __forceinline__ double block_sum_f64(double acc) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    __shared__ double part[16];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    double s = 0.0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < 16; ++w) s += part[w];   // fixed order: the same bits on every run
+    return s;
+}
+
+// sum ((x - y) * inv_range)^2 over `count` elements by one 1024-thread workgroup, in float64 (`block_sum_f64`).
 __device__ __forceinline__ double block_sum_sq_diff(const float* __restrict__ x, const float* __restrict__ y, long count, double inv_range) {
     double acc = 0.0;
     const long n4 = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0 ? count / 4 : 0;
@@ -26,15 +39,7 @@ __device__ __forceinline__ double block_sum_sq_diff(const float* __restrict__ x,
         const double d = ((double)x[i] - (double)y[i]) * inv_range;
         acc += d * d;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    __shared__ double part[16];
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    double s = 0.0;
-    if (threadIdx.x == 0)
-        for (int w = 0; w < 16; ++w) s += part[w];   // fixed order: the same bits on every run
-    return s;
+    return block_sum_f64(acc);
 }
 
 // one workgroup per image: score = -10 log10(mse / R^2 + 1e-8)
@@ -65,6 +70,121 @@ extern "C" int ccvs_mse(const float* a, const float* b, float* out, int64_t n, v
     CCVS_REQUIRE(n > 0, "ccvs_mse: no elements");
     hipLaunchKernelGGL(mse_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, a, b, out, (long)n);
     CCVS_CHECK_LAUNCH("ccvs_mse");
+    return CCVS_OK;
+}
+
+// ---- teacher-forced NLL (transformer_model.py:229,239: F.cross_entropy over selected rows of the logits) -----------------------
+// nll[m] = logsumexp(row[0 : ncols]) - row[target[m]] for row = logits + rows[m] * ld.  HBM-bound: a row's logits are loaded ONCE into
+// registers (columns past ncols stand as -inf and are never read), the maximum and the sum of exp(x - max) are taken from the
+// registers, so a row of 16384 fp32 is 64 registers per lane of a 256-thread workgroup.  A team of lanes owns a row:
+//   ONE_WAVE  a wave per row, four rows per workgroup, 4 * NQ = 16 logits per lane (ncols <= 1024): no LDS, no barrier -- the
+//             BAIR vocabulary and the state heads, where a workgroup per row would leave 4 KB in flight per workgroup;
+//   otherwise a 256-thread workgroup per row, 4 * NQ = 16 or 64 logits per lane (ncols <= 4096 / 16384), the four waves' partial
+//             results through LDS, combined as (w0 . w1) . (w2 . w3).
+// VEC: 16-byte loads, lane t taking quads t, t + team, ...; a quad that crosses ncols is read column by column.  Not VEC (ld % 4 != 0
+// or an unaligned base): 4-byte loads, lane t taking columns t, t + team, ... -- coalesced all the same.
+// The butterfly and the fixed LDS order make the result the same bits on every run; there are no atomics.
+// exp is v_exp_f32 (__expf): a term e^d, d <= 0, is off by |d| * 6e-8 of itself, so the sum by at most max(|d| e^d) * 6e-8 = 2e-8 of
+// itself -- below the rounding of the fp32 sum.
+template <int NQ, bool VEC, int TEAM>
+__device__ __forceinline__ void nll_load_row(const float* __restrict__ row, int ncols, int t, float (&v)[4 * NQ]) {
+    if (VEC) {
+#pragma unroll
+        for (int j = 0; j < NQ; ++j) {
+            const int c = 4 * (t + TEAM * j);
+            if (c + 3 < ncols) {
+                const float4 a = *reinterpret_cast<const float4*>(row + c);
+                v[4 * j] = a.x; v[4 * j + 1] = a.y; v[4 * j + 2] = a.z; v[4 * j + 3] = a.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[4 * j + e] = c + e < ncols ? row[c + e] : -INFINITY;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4 * NQ; ++k) {
+            const int c = t + TEAM * k;
+            v[k] = c < ncols ? row[c] : -INFINITY;
+        }
+    }
+}
+
+template <int NQ, bool VEC, bool ONE_WAVE>
+__global__ __launch_bounds__(256) void token_nll_kernel(const float* __restrict__ logits, long ld, const int* __restrict__ rows,
+                                                         const int64_t* __restrict__ target, long n_rows, int ncols, float* __restrict__ nll) {
+    constexpr int TEAM = ONE_WAVE ? 64 : 256;
+    __shared__ float wmax[4], wsum[4];
+    const int t = threadIdx.x & (TEAM - 1), wave = threadIdx.x >> 6;
+    const long m = ONE_WAVE ? (long)blockIdx.x * 4 + wave : (long)blockIdx.x;
+    if (ONE_WAVE && m >= n_rows) return;   // a whole wave leaves; this form has no barrier
+    const float* row = logits + (long)(rows ? rows[m] : m) * ld;
+    const int64_t tgt = target[m];
+    const bool ok = tgt >= 0 && tgt < ncols;   // outside: NaN, and nothing is read for it
+    const float xt = ok && t == 0 ? row[tgt] : 0.f;
+    float v[4 * NQ];
+    nll_load_row<NQ, VEC, TEAM>(row, ncols, t, v);
+    float mx = v[0];
+#pragma unroll
+    for (int k = 1; k < 4 * NQ; ++k) mx = fmaxf(mx, v[k]);
+    mx = wave_max(mx);
+    if (!ONE_WAVE) {
+        if ((threadIdx.x & 63) == 0) wmax[wave] = mx;
+        __syncthreads();
+        mx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4 * NQ; ++k) s += __expf(v[k] - mx);   // -inf (a masked logit, a column past ncols) adds 0
+    s = wave_sum(s);
+    if (!ONE_WAVE) {
+        if ((threadIdx.x & 63) == 0) wsum[wave] = s;
+        __syncthreads();
+        s = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    }
+    if (t == 0) nll[m] = ok ? logf(s) + (mx - xt) : __builtin_nanf("");
+}
+
+template <int NQ, bool ONE_WAVE>
+static void launch_token_nll(bool vec, const float* logits, long ld, const int* rows, const int64_t* target, long n_rows, int ncols, float* nll,
+                             hipStream_t stream) {
+    const dim3 grid((unsigned)(ONE_WAVE ? cdiv64(n_rows, 4) : n_rows));
+    if (vec)
+        hipLaunchKernelGGL((token_nll_kernel<NQ, true, ONE_WAVE>), grid, dim3(256), 0, stream, logits, ld, rows, target, n_rows, ncols, nll);
+    else
+        hipLaunchKernelGGL((token_nll_kernel<NQ, false, ONE_WAVE>), grid, dim3(256), 0, stream, logits, ld, rows, target, n_rows, ncols, nll);
+}
+
+extern "C" int ccvs_token_nll(const float* logits, int64_t ld, const int32_t* rows, const int64_t* target, int64_t n_rows, int32_t ncols, float* nll,
+                              void* stream) {
+    CCVS_REQUIRE(logits && target && nll, "ccvs_token_nll: null pointer");
+    CCVS_REQUIRE(n_rows > 0 && n_rows < 2147483647L, "ccvs_token_nll: 1 .. 2^31 - 2 rows per call");
+    CCVS_REQUIRE(ncols > 0 && ncols <= 16384 && ld >= ncols, "ccvs_token_nll: 1 <= ncols <= 16384 (a row is held in registers), ncols <= ld; got ncols %d, ld %ld",
+                 ncols, (long)ld);
+    const bool vec = (reinterpret_cast<uintptr_t>(logits) & 15) == 0 && ld % 4 == 0;   // every row starts on 16 bytes
+    if (ncols <= 1024)
+        launch_token_nll<4, true>(vec, logits, (long)ld, rows, target, (long)n_rows, ncols, nll, (hipStream_t)stream);
+    else if (ncols <= 4096)
+        launch_token_nll<4, false>(vec, logits, (long)ld, rows, target, (long)n_rows, ncols, nll, (hipStream_t)stream);
+    else
+        launch_token_nll<16, false>(vec, logits, (long)ld, rows, target, (long)n_rows, ncols, nll, (hipStream_t)stream);
+    CCVS_CHECK_LAUNCH("ccvs_token_nll");
+    return CCVS_OK;
+}
+
+// mean of n fp32 into one fp32: float64 sums in index order by one workgroup, rounded once (the shape of mse_kernel).  A NaN element
+// gives a NaN mean.
+__global__ __launch_bounds__(1024) void mean_kernel(const float* __restrict__ x, float* __restrict__ out, long n) {
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < n; i += 1024) acc += (double)x[i];
+    const double s = block_sum_f64(acc);
+    if (threadIdx.x == 0) out[0] = (float)(s / (double)n);
+}
+
+extern "C" int ccvs_mean_f32(const float* x, int64_t n, float* out, void* stream) {
+    CCVS_REQUIRE(x && out, "ccvs_mean_f32: null pointer");
+    CCVS_REQUIRE(n > 0, "ccvs_mean_f32: no elements");
+    hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, x, out, (long)n);
+    CCVS_CHECK_LAUNCH("ccvs_mean_f32");
     return CCVS_OK;
 }
 

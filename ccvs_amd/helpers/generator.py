@@ -203,6 +203,36 @@ class Generator:
         return {"data": data, "encoded": encoded_data, "cropped": cropped, "total_len": total_len, "cond_len": cond_len,
                 "crop_prop": crop_prop, "blur": blurred}
 
+    @torch.no_grad()
+    def transformer_loss(self, data, global_iter=None, log=False):
+        """The forward half of the reference trainer's `step_model` for a clip batch (helpers/transformer_trainer.py:57-84,
+        data_type "vid"): encode the clip, tokenise the ancillary streams, split off the point-to-point prefix, then the
+        transformer's teacher-forced loss (`Transformer.forward(mode='transformer')`) as a 0-dim fp32 tensor on the device.
+        No optimiser, no all-reduce, no backward: the validation figure of a `transformer_t` checkpoint.  Under `--x_cat` a batch
+        without `vid_lbl` gets a label per clip drawn with `torch.randint` from the CPU default generator, and -- as in the reference --
+        the draw is written back into the caller's `data["vid_lbl"]`."""
+        opt = self.opt
+        if getattr(opt, "layout", False):
+            raise NotImplementedError("layout conditioning is not on the MI355X path (SURVEY 8f)")
+        encoded_data = self.vid_model(data, mode='vid_encoder')                                     # :57
+        if opt.state:                                                                               # :59-62
+            data_for_state = data if getattr(self.state_opt, "quantize_only", False) else encoded_data
+            encoded_data.update(self.state_model(data_for_state, mode='vid_encoder'))
+        if opt.stft:                                                                                # :64-66
+            encoded_data.update(self.stft_model(data, mode='vid_encoder'))
+        if opt.p2p:                                                                                 # :68-71
+            encoded_data["cond_code"] = encoded_data["code"][:, -opt.z_chunk:]
+            encoded_data["code"] = encoded_data["code"][:, :-opt.z_chunk]
+            encoded_data["delta_length_cond"] = data["delta_length"]
+        if opt.cat:                                                                                 # :73-76
+            if "vid_lbl" not in data:
+                data["vid_lbl"] = torch.randint(low=0, high=len(opt.categories), size=[data["vid"].size(0)])
+            encoded_data["vid_lbl"] = data["vid_lbl"]
+        if getattr(opt, "deblurring", False):                                                       # :78-81
+            blurred_encoded = self.vid_model(blur(data, blur_sigma=opt.blur_sigma), mode='vid_encoder')
+            encoded_data["state_code"] = blurred_encoded["code"]
+        return self.transformer_model(encoded_data, mode='transformer', prefix="vid_", log=log, global_iter=global_iter)   # :84
+
     def _frames_to_encode(self, n_frames, size):
         """Frames of the input clip the encoder has to see.  The reference encodes all of them (generator.py:69); with
         `--encode_all false` only those the conditioning crop keeps (generator.py:93-99: the first crop_prop of the codes and of

@@ -18,6 +18,7 @@ EXPORTS = [
     "ccvs_gpt_embed", "ccvs_layernorm", "ccvs_gemm_workspace_bytes", "ccvs_gemm_nt", "ccvs_gemm_ln", "ccvs_gemm_ln_qkv", "ccvs_attention", "ccvs_kv_append", "ccvs_sample_topk", "ccvs_sample_topk_philox", "ccvs_sample_topn",
     "ccvs_gpt_decode_step", "ccvs_gpt_decode_status", "ccvs_gpt_program_bytes", "ccvs_gpt_decode_prepare", "ccvs_pack_u8", "ccvs_pack_u8_norm", "ccvs_stream_cu_limit", "ccvs_psnr", "ccvs_ssim_workspace_bytes", "ccvs_ssim", "ccvs_resize_bilinear",
     "ccvs_deform_conv3x3_ctx", "ccvs_gconvT4x4s2", "ccvs_flow_mask_toff", "ccvs_gaussian_blur", "ccvs_to_rgb", "ccvs_channel_head", "ccvs_mse",
+    "ccvs_token_nll", "ccvs_mean_f32",
 ]
 
 
@@ -141,6 +142,8 @@ def load():
         "ccvs_to_rgb": [vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
         "ccvs_channel_head": [vp, i64, vp, f32, vp, vp, i32, i32, i32, i32, i32, i32, vp],
         "ccvs_mse": [vp, vp, vp, i64, vp],
+        "ccvs_token_nll": [vp, i64, vp, vp, i64, i32, vp, vp],
+        "ccvs_mean_f32": [vp, i64, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

@@ -1,9 +1,11 @@
 """Transformer wrapper: the autoregressive sampling loop over latent tokens.
 
 Host-side mirror of the reference's `models/skip_vid_generator/models/transformer_model.py`
-(inference only): `Transformer(opt, is_train, is_main, logger)`, `forward(data, mode='inference',
+(forward passes only): `Transformer(opt, is_train, is_main, logger)`, `forward(data, mode='inference',
 total_len=...) -> {"code", "state_code"}`, `generate_fake`, `fill_code`, `get_icode`,
-`top_k_logits` keep their names, argument meaning and error behaviour.
+`top_k_logits` keep their names, argument meaning and error behaviour; so does the teacher-forced
+validation loss, `forward(data, mode='transformer' | 'eval_transformer')` -> `compute_transformer_loss`
+(the forward value only: no backward, no optimiser).
 
 The loop itself is re-designed: one prefill of the known tokens, then one KV-cached decode step
 per new token (the reference re-runs the full prefix each time, transformer_model.py:343-350);
@@ -19,6 +21,23 @@ from .mingpt import GPT
 from ccvs_amd.tools.utils import to_cuda
 from ccvs_amd.models import load_network, print_network
 from ccvs_amd import ops
+
+
+def loss_rows(n_logits, state_size, tot_size, num_blocks, state_front):
+    """Which of the `n_logits` teacher-forced positions predict an ancillary token and which a frame token
+    (transformer_model.py:215-220): row i predicts position i + 1 of the merged sequence, which lies in a frame's state slot when
+    (i + 1) % tot_size < state_size -- with `state_front`, when i + 1 < state_size * num_blocks.  Returns (state_i, frame_i)."""
+    if state_front:
+        is_state = [i + 1 < state_size * num_blocks for i in range(n_logits)]
+    else:
+        is_state = [(i + 1) % tot_size < state_size for i in range(n_logits)]
+    return [i for i, s in enumerate(is_state) if s], [i for i, s in enumerate(is_state) if not s]
+
+
+def _same_count(n_rows, n_targets, what):
+    if n_rows != n_targets:   # F.cross_entropy's own failure in the reference
+        raise ValueError(f"Expected input batch_size ({n_rows}) to match target batch_size ({n_targets}) per clip: the {what} rows of the "
+                         "teacher-forced logits and their targets differ in number")
 
 
 class Transformer(torch.nn.Module):
@@ -37,13 +56,18 @@ class Transformer(torch.nn.Module):
         self.sample_noise = getattr(opt, "sample_noise", "host")  # 'host' (reference-reproducible) | 'device'
         self.generator = None                                      # optional torch.Generator for the noise
         self.trace = None                                          # optional list collecting per-step logits (tests)
+        self._loss_rows_cache = {}                                 # per (batch, logits length): the loss's row lists on the device (`_loss_plan`)
 
     def forward(self, data, prefix='', mode='', total_len=None, log=False, global_iter=None, show_progress=False):
         code, state_code, cond_code, delta_length_cond, vid_lbl = self.preprocess_input(data)
         if mode == 'inference':
             return self.generate_fake(code, state_code, cond_code, delta_length_cond, vid_lbl, total_len, show_progress)
-        if mode in ('transformer', 'eval_transformer'):
-            raise NotImplementedError(f"mode '{mode}' (training loss) is outside the MI355X hot path")
+        if mode == 'transformer':
+            return self.compute_transformer_loss(code, state_code, cond_code, delta_length_cond, vid_lbl, prefix, log, global_iter)
+        if mode == 'eval_transformer':
+            # (deviation) the reference passes (code, log, global_iter) to the eight-parameter function here and fails with a
+            # TypeError for every input (transformer_model.py:36-39); this runs what the line plainly means: the same loss, not logged
+            return self.compute_transformer_loss(code, state_code, cond_code, delta_length_cond, vid_lbl, prefix, log, global_iter, is_eval=True)
         raise ValueError(f"mode '{mode}' is invalid")
 
     def preprocess_input(self, data):
@@ -68,6 +92,71 @@ class Transformer(torch.nn.Module):
         if self.is_main:
             net_t = load_network(net_t, "transformer_t", opt, head_to_n=getattr(opt, "head_to_n", 0))
         return net_t
+
+    # ------------------------------------------------------------------ teacher-forced loss
+    def _loss_plan(self, code, state_code):
+        """The host half of `compute_transformer_loss`, before anything is launched: the cropped code, the targets and the rows of the
+        flattened [B * T, V] logits they are scored against -- (code, [(rows or None, target, ncols), ...]) with the frame tokens
+        first and the ancillary tokens, if any, second.  Raises where the reference's shapes do not agree (`F.cross_entropy`'s
+        ValueError), and `GPT.forward`'s NotImplementedError for the combinations it refuses."""
+        opt, net = self.opt, self.net_t
+        code = code[:, :opt.z_len]                                         # transformer_model.py:143
+        b, n_code = code.shape
+        n_pre = net.n_prefix()
+        if 0 in state_code.size():
+            n_logits = n_pre + n_code - 1
+            target = code if (opt.use_start_token or opt.cat) else code[:, 1:]   # :225-228
+            _same_count(n_logits, target.shape[1], "frame")
+            return code, [(None, target, opt.z_num)]
+        if n_pre:
+            raise NotImplementedError("label / start tokens together with an ancillary token stream")
+        n_logits = len(net.stream_kinds(n_code - 1, state_code.shape[1]))
+        state_i, frame_i = loss_rows(n_logits, self.state_size, self.tot_size, opt.num_blocks, bool(opt.state_front))
+        state_target = state_code[:, 1:]                                   # :239
+        _same_count(len(frame_i), n_code, "frame")                         # target = code, all of it (:223)
+        _same_count(len(state_i), state_target.shape[1], "state")
+        key = (b, n_logits, code.device)
+        if key not in self._loss_rows_cache:                                # row b * T + i of the flattened logits: no logits[:, frame_i] copy
+            flat = lambda idx: (torch.arange(b, dtype=torch.int32).view(b, 1) * n_logits
+                                + torch.tensor(idx, dtype=torch.int32).view(1, -1)).reshape(-1).to(code.device)
+            self._loss_rows_cache[key] = {"state": flat(state_i), "frame": flat(frame_i)}
+        rows = self._loss_rows_cache[key]
+        return code, [(rows["frame"], code, opt.z_num), (rows["state"], state_target, opt.state_num)]
+
+    @torch.no_grad()
+    def token_nll(self, data):
+        """(ccvs_amd) The per-token values behind `forward(data, mode='transformer')`, before the mean: {"nll": [B, frame rows],
+        "state_nll": [B, ancillary rows], or an empty tensor without an ancillary stream} as fp32 on the device -- perplexity by
+        position or by frame is a mean over a slice of them.  Same inputs, same checks."""
+        code, state_code, cond_code, delta_length_cond, vid_lbl = self.preprocess_input(data)
+        per_token = self._token_nll(code, state_code, cond_code, delta_length_cond, vid_lbl)
+        b = code.shape[0]
+        return {"nll": per_token[0].view(b, -1),
+                "state_nll": per_token[1].view(b, -1) if len(per_token) > 1 else torch.empty(0, dtype=torch.float32, device=code.device)}
+
+    def _token_nll(self, code, state_code, cond_code, delta_length_cond, vid_lbl):
+        code, plan = self._loss_plan(code, state_code)
+        logits = self.net_t(code[:, :-1].contiguous(), cond_idx=cond_code, state_idx=state_code, delta_length_cond=delta_length_cond,
+                            lbl_idx=vid_lbl)                               # :212
+        flat = logits.view(-1, logits.shape[-1])
+        return [ops.token_nll(flat, target.reshape(-1), rows=rows, ncols=ncols) for rows, target, ncols in plan]
+
+    @torch.no_grad()
+    def compute_transformer_loss(self, code, state_code, cond_code, delta_length_cond, vid_lbl, prefix, log, global_iter, is_eval=False):
+        """transformer_model.py:142-253, the discrete branch: the mean NLL of the teacher-forced logits over the frame tokens, plus
+        -- with an ancillary stream -- the mean NLL of the first `state_num` logits over the ancillary tokens, as a 0-dim fp32 tensor
+        on the device (`ccvs_token_nll` over row lists of the flattened logits, `ccvs_mean_f32`; nothing is synchronised).  A token
+        outside its vocabulary makes the value NaN where the reference raises.  With a logger and not `is_eval` the two means are
+        logged under the reference's names (its six other scalars are always None and are not).  The forward value only."""
+        per_token = self._token_nll(code, state_code, cond_code, delta_length_cond, vid_lbl)
+        nll_loss = ops.mean_f32(per_token[0])
+        state_nll_loss = ops.mean_f32(per_token[1]) if len(per_token) > 1 else None
+        t_loss = nll_loss if state_nll_loss is None else nll_loss + state_nll_loss
+        if self.logger and not is_eval:
+            self.logger.log_scalar(f"transformer/{prefix}nll", nll_loss, global_iter)
+            if state_nll_loss is not None:
+                self.logger.log_scalar(f"transformer/{prefix}state_nll", state_nll_loss, global_iter)
+        return t_loss
 
     def top_k_logits(self, logits, k):
         """transformer_model.py:256-260 (torch ops; the fused kernel applies the same rule)."""

@@ -900,6 +900,37 @@ def mse(a, b):
     return out
 
 
+def token_nll(logits2d, target, rows=None, ncols=None):
+    """Per-token NLL over selected rows of teacher-forced logits (`ccvs_token_nll`): out[m] = logsumexp(logits2d[r, :ncols]) -
+    logits2d[r, target[m]] with r = rows[m] (int32 device tensor; None: r = m), as fp32 [n_rows].  logits2d: [M, V] fp32 with dense
+    columns (any row stride); ncols defaults to V.  A target outside [0, ncols) gives NaN for its row -- nothing is synchronised to
+    raise, as the reference's F.cross_entropy would."""
+    _need_gpu(logits2d, target, rows)
+    assert logits2d.dim() == 2 and logits2d.dtype == torch.float32 and logits2d.stride(1) == 1, (logits2d.shape, logits2d.stride())
+    ncols = logits2d.shape[1] if ncols is None else int(ncols)
+    assert 0 < ncols <= logits2d.shape[1], (ncols, logits2d.shape)
+    target = target.reshape(-1).to(torch.int64).contiguous()
+    n_rows = target.numel()
+    if rows is not None:
+        assert rows.dtype == torch.int32 and rows.dim() == 1 and rows.is_contiguous() and rows.numel() == n_rows, (rows.shape, n_rows)
+    else:
+        assert n_rows == logits2d.shape[0], (n_rows, logits2d.shape)
+    out = torch.empty(n_rows, dtype=torch.float32, device=logits2d.device)
+    _lib.check(_lib.load().ccvs_token_nll(_p(logits2d), logits2d.stride(0), _p(rows), _p(target), n_rows, ncols, _p(out), _stream()),
+               "ccvs_token_nll")
+    return out
+
+
+def mean_f32(x):
+    """Mean of an fp32 tensor as a 0-dim fp32 tensor on the device, float64 inside (`ccvs_mean_f32`; nothing is synchronised)."""
+    _need_gpu(x)
+    assert x.dtype == torch.float32 and x.numel() > 0, (x.dtype, x.shape)
+    x = x.contiguous()
+    out = torch.empty((), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().ccvs_mean_f32(_p(x), x.numel(), _p(out), _stream()), "ccvs_mean_f32")
+    return out
+
+
 def ssim_planes(x, y, data_range=2.0):
     """skimage 0.17.2 `structural_similarity` (defaults) of every 2-D plane of [..., H, W] fp32 tensors: [...] fp64
     (tools/pytorch_metrics/metrics.py:15-22; data_range 2 = what skimage takes for float planes when none is given)."""

@@ -437,6 +437,19 @@ int ccvs_psnr(const float* x, const float* y, float* out, int64_t N, int64_t per
 /* F.mse_loss(a, b) of stft_model.py:117 (eval_stft_reconstruction) and state_model.py:106 (eval_state_estimator): mean((a - b)^2)
  * over n fp32 elements, differences and sums in float64, into out[1] fp32 on the device (no host synchronisation). */
 int ccvs_mse(const float* a, const float* b, float* out, int64_t n, void* stream);
+/* The per-token half of F.cross_entropy in transformer_model.py:229,239 (compute_transformer_loss), over selected rows of the
+ * teacher-forced logits:  nll[m] = logsumexp(row[0 : ncols]) - row[target[m]]  with  row = logits + r * ld,  r = rows[m], or m when
+ * rows is NULL (rows: int32 on the device, any order, repeats allowed).  Only the first ncols columns of a row are read (the state
+ * head reads :state_num of a z_num-wide row); max-subtracted, so logits of +-80 do not overflow, and a -inf logit adds 0.
+ * A row that is -inf in all of its first ncols columns gives NaN (max = -inf, exp(-inf - -inf)), as aten's cross_entropy does.
+ * 1 <= ncols <= 16384, ncols <= ld.  A target outside [0, ncols) gives nll[m] = NaN and no read outside the row: the reference's
+ * F.cross_entropy raises on the host there; this call does not synchronise to find out, so the caller sees the NaN (and a NaN
+ * mean).  16-byte loads where logits is 16-byte aligned and ld % 4 == 0, 4-byte loads otherwise; same bits on every run. */
+int ccvs_token_nll(const float* logits, int64_t ld, const int32_t* rows, const int64_t* target, int64_t n_rows, int32_t ncols, float* nll,
+                   void* stream);
+/* mean of n fp32 elements into out[1] fp32 on the device (no host synchronisation): float64 sums in index order, rounded once --
+ * F.cross_entropy's reduction='mean' over ccvs_token_nll's output.  A NaN element gives a NaN mean. */
+int ccvs_mean_f32(const float* x, int64_t n, float* out, void* stream);
 /* tools/pytorch_metrics/metrics.py:15-22 get_ssim = skimage.metrics.structural_similarity on every 2-D plane x[i, c], y[i, c]
  * with scikit-image 0.17.2's defaults: 7 x 7 uniform window, sample covariance, K1 = 0.01, K2 = 0.03, float64 arithmetic,
  * mean over the windows inside the plane; data_range is the caller's (the reference passes float planes and no data_range,
