@@ -12,7 +12,9 @@
 // transposed codebook [C][n_e] (128-B coalesced per half-wave, L2-resident) into the A
 // operand of v_mfma_f32_32x32x2_f32.  D[code][row]: a lane owns one row and 16 codes, so
 // the running (min, index) lives in registers; ties keep the lowest index like
-// torch.argmin.  d = (|z|^2 + |e|^2) - 2 z.e in the reference's association order.
+// torch.argmin.  d = (|z|^2 + |e|^2) - 2 z.e in the reference's association order.  A row whose distances are all
+// non-finite (NaN or +inf: a NaN or inf in z, or |z|^2 overflowing) returns code 0, as torch.argmin does on an all-NaN
+// row and as the scalar kernel below does: the index is always inside [0, n_e).
 __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict__ z, const float* __restrict__ cbt,
                                                         const float* __restrict__ e_sq, int64_t* __restrict__ idx, long rows, int C,
                                                         int HW, int n_e) {
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(256) void vq_argmin_kernel(const float* __restrict_
             const int oi = red_i[w * 32 + tid];
             if (od < bd || (od == bd && oi < bi)) { bd = od; bi = oi; }
         }
-        idx[r0 + tid] = (int64_t)bi;
+        idx[r0 + tid] = (int64_t)(bi == 0x7fffffff ? 0 : bi);   // no distance was < +inf (all NaN / +inf): 0, like torch.argmin
     }
 }
 
