@@ -171,6 +171,7 @@ static int launch_conv(const ConvK& k, int halo_h, int halo_w, int ntx_max, int 
     dim3 grid(k.tiles_x * k.tiles_y, k.CoutPad / NT, gz);
     hipLaunchKernelGGL((conv2d_mfma_kernel<TW, MB>), grid, dim3(256), smem, st, k);
     CCVS_CHECK_LAUNCH("ccvs_conv2d");
+    ccvs_conv_record_launch("f32 TW=%d MB=%d", TW, MB);
     return CCVS_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdio.h>
+#include <stdarg.h>
 
 #define CB_DECL(TWv, MBv) int ccvs_conv_bf16_launch_##TWv##_##MBv(const ConvK& k, const void* wsplit, const void* wktail, int CinG, int halo_h, int halo_w, int ntx_max, int gz, hipStream_t st, int wpc2);
 CB_DECL(32, 4) CB_DECL(32, 2) CB_DECL(32, 1) CB_DECL(16, 4) CB_DECL(16, 2) CB_DECL(16, 1) CB_DECL(8, 4) CB_DECL(8, 2) CB_DECL(8, 1)
@@ -29,6 +30,15 @@ extern "C" int ccvs_conv_fetch_bytes_per_lane(const char* kernel_name) {
     if (strstr(kernel_name, "conv2d_bf16x3_kernel<") || strstr(kernel_name, "conv2d_mfma_kernel")) return 4;
     return -1;
 }
+
+static thread_local char g_conv_launch[160] = "";
+void ccvs_conv_record_launch(const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_conv_launch, sizeof(g_conv_launch), fmt, ap);
+    va_end(ap);
+}
+extern "C" const char* ccvs_conv_last_launch(void) { return g_conv_launch; }
 
 // Persistent tiles (conv2d_bf16_pt.h) by CONTEXT: alone on the chip the resident form is 6 % faster over a decode's convolutions (a single
 // generate call: +1...1.5 %), beside the token loops of other batches the chip is power-managed and the denser kernel costs everyone clock

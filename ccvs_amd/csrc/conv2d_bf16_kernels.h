@@ -1042,18 +1042,31 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
     };
     // The tail of every form: the kernel's LDS limit (159 KB + the static bias block; set before its first launch), plan / chunk /
     // launch over GRID with 512 threads, check, RETURN from the launcher.  CB_LAUNCH_RETURN: over the 256-pixel tiling.
-#define CB_LAUNCH_RETURN_ON(GRID, KERNEL, SMEM, ...)                                                      \
+#define CB_LAUNCH_RETURN_ON(GRID, KERNEL, SMEM, REC, ...)                                                 \
     do {                                                                                          \
         CB_SET_LDS_ONCE(KERNEL, 159 * 1024);                                                      \
         plan(GRID, (const void*)KERNEL, SMEM);                                                    \
+        int xcd0_ = 0;                                                                            \
         for (long c_ = 0; c_ < n_chunk; ++c_) {                                                   \
             const dim3 g_ = chunk_grid(GRID, c_);                                                 \
+            if (c_ == 0) xcd0_ = k.xcd_chunk != 0;                                                \
             hipLaunchKernelGGL((KERNEL), g_, dim3(512), SMEM, st, k, __VA_ARGS__);                \
         }                                                                                         \
         CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3");                                                  \
+        ccvs_conv_record_launch("%s chunks=%ld xcd=%d zi=%d", REC, n_chunk, xcd0_, k.zi);         \
         return CCVS_OK;                                                                           \
     } while (0)
-#define CB_LAUNCH_RETURN(KERNEL, SMEM, ...) CB_LAUNCH_RETURN_ON(grid3, KERNEL, SMEM, __VA_ARGS__)
+#define CB_LAUNCH_RETURN(KERNEL, SMEM, REC, ...) CB_LAUNCH_RETURN_ON(grid3, KERNEL, SMEM, REC, __VA_ARGS__)
+    // the launch record (ccvs_conv_last_launch) of a producer / consumer instantiation: every template argument by value, p.ktail
+    char rec[64];
+    auto pc_rec = [&](int nty, int pp, int wpc) -> const char* {
+        snprintf(rec, sizeof(rec), "pc TW=%d MB=%d NTY=%d PP=%d WPC=%d ktail=%d", TW, MB, nty, pp, wpc, k.ktail);
+        return rec;
+    };
+    auto sync_rec = [&]() -> const char* {
+        snprintf(rec, sizeof(rec), "sync TW=%d MB=%d", TW, MB);
+        return rec;
+    };
     if (k.in_p8) {  // packed input: LDS-DMA staging (validated by the caller: stride 1, not transposed, Cin % 8 == 0)
         const size_t smem_p = (size_t)(2 * 4 * plane + 2 * ntx_max * 4 * NT) * 16;
         if (4 * plane > 8 * 256 || ntx_max > (MB == 1 ? 9 : 3) || smem_p > 156 * 1024) {
@@ -1068,16 +1081,16 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
                 k.tiles_y = cdiv(k.Hout, th4);
                 const dim3 grid4(k.tiles_x * k.tiles_y, k.CoutPad / NT, gz);
                 // (cu_limit <= 0: one launch over the whole chip)
-                CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), (smem_4 > p8s4 ? smem_4 : p8s4), (const uint4*)wsplit, CinG, ntx_max);
+                CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, -83, 4>), (smem_4 > p8s4 ? smem_4 : p8s4), pc_rec(-83, 4, 1), (const uint4*)wsplit, CinG, ntx_max);
             }
         }
         const size_t smem_p2 = smem_p > p8s2 ? smem_p : p8s2;
         if constexpr (MB != 4) {   // (128 output channels per workgroup: the written-out form spills; no layer of the models needs it)
             if (k.kh == 3 && k.kw == 3 && k.pad == 1) {
-                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -83>), smem_p2, (const uint4*)wsplit, CinG, ntx_max);
+                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -83>), smem_p2, pc_rec(-83, 2, 1), (const uint4*)wsplit, CinG, ntx_max);
             }
         }
-        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -8>), smem_p2, (const uint4*)wsplit, CinG, ntx_max);
+        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -8>), smem_p2, pc_rec(-8, 2, 1), (const uint4*)wsplit, CinG, ntx_max);
     }
     // aligned float4 staging: dense stride-1 rows on 16-byte boundaries, one item per staging thread
     const int xsh = ((-k.pad % 4) + 4) % 4, nq = (xsh + halo_w + 3) / 4;
@@ -1100,8 +1113,8 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
             // (one launch over the whole chip; with a CU budget the 256-pixel form below runs in chunks)
             if (k.cu_limit <= 0) {
                 k.ktail = kt ? ktail_r : 0;
-                if (k.kh == 3) CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, 3, 4>), smem_4, (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
-                else CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), smem_4, (const uint4*)wsplit, CinG, ntx_max);
+                if (k.kh == 3) CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, 3, 4>), smem_4, pc_rec(3, 4, 1), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
+                else CB_LAUNCH_RETURN_ON(grid4, (conv2d_bf16x3_pc_kernel<TW, MB, 1, 4>), smem_4, pc_rec(1, 4, 1), (const uint4*)wsplit, CinG, ntx_max);
             }
             k.tiles_y = k_in.tiles_y;
         }
@@ -1111,14 +1124,14 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         if constexpr (TW == 32 && MB == 2) {
             if (wpc2 && k.kh == 3 && k.kw == 3 && smem_v <= 80 * 1024 && k.cu_limit <= 0) {   // two workgroups per CU (see the kernel)
                 k.ktail = kt ? ktail_r : 0;
-                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 3, 2, 2>), (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
+                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 3, 2, 2>), (smem_v > p8s2 ? smem_v : p8s2), pc_rec(3, 2, 2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
             }
         }
         if (smem_v <= 156 * 1024) {
             if (k.kh == 3) {
                 k.ktail = kt ? ktail_r : 0;
-                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 3>), (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
-            } else CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 1>), (smem_v > p8s2 ? smem_v : p8s2), (const uint4*)wsplit, CinG, ntx_max);
+                CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 3>), (smem_v > p8s2 ? smem_v : p8s2), pc_rec(3, 2, 1), (const uint4*)(kt ? wktail : wsplit), CinG, ntx_max);
+            } else CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 1>), (smem_v > p8s2 ? smem_v : p8s2), pc_rec(1, 2, 1), (const uint4*)wsplit, CinG, ntx_max);
         }
     }
     // Scalar staging: the producer / consumer form with the halo tile in one (NTY 0) or two (NTY -2) pixel passes per tap row.
@@ -1129,10 +1142,10 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
     const bool pc_ok = !k.transposed && smem_pc <= 156 * 1024 && ntx_max <= (MB == 1 ? 9 : 3);
     // (8 staging waves for <= 64 output channels were measured slower: the steps are latency- not staging-bound)
     if (pc_ok && passes <= k.kh) {  // double-buffered producer / consumer form, scalar staging
-        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 0>), (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
+        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, 0>), (smem_pc > p8s2 ? smem_pc : p8s2), pc_rec(0, 2, 1), (const uint4*)wsplit, CinG, ntx_max);
     }
     if (pc_ok && passes <= 2 * k.kh) {
-        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -2>), (smem_pc > p8s2 ? smem_pc : p8s2), (const uint4*)wsplit, CinG, ntx_max);
+        CB_LAUNCH_RETURN((conv2d_bf16x3_pc_kernel<TW, MB, -2>), (smem_pc > p8s2 ? smem_pc : p8s2), pc_rec(-2, 2, 1), (const uint4*)wsplit, CinG, ntx_max);
     }
     if (k.out_p8) {
         ccvs_set_error("ccvs_conv2d_bf16x3: packed output is not available for this shape (synchronous kernel)");
@@ -1143,7 +1156,7 @@ static int launch_conv_bf16(const ConvK& k_in, const void* wsplit, const void* w
         ccvs_set_error("ccvs_conv2d_bf16x3: %zu bytes of LDS needed", smem);
         return CCVS_ERR_ARG;
     }
-    CB_LAUNCH_RETURN((conv2d_bf16x3_kernel<TW, MB, 8>), smem, (const uint4*)wsplit, CinG);
+    CB_LAUNCH_RETURN((conv2d_bf16x3_kernel<TW, MB, 8>), smem, sync_rec(), (const uint4*)wsplit, CinG);
 #undef CB_LAUNCH_RETURN
 #undef CB_LAUNCH_RETURN_ON
 }

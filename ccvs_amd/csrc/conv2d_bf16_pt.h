@@ -478,6 +478,7 @@ static int launch_conv_pt(ConvK k, const void* w, int CinG, int gz, hipStream_t 
     const unsigned grid = (unsigned)(total < cus ? total : cus);
     hipLaunchKernelGGL((conv2d_bf16x3_pt_kernel<MB, PP, P8IN>), dim3(grid), dim3(512), smem, st, k, (const uint4*)w, CinG, (int)total);
     CCVS_CHECK_LAUNCH("ccvs_conv2d_bf16x3 (persistent tiles)");
+    ccvs_conv_record_launch("pt MB=%d PP=%d p8in=%d ktail=%d xcd=%d zi=%d", MB, PP, P8IN ? 1 : 0, k.ktail, k.xcd_chunk != 0, k.zi);
     return CCVS_OK;
 }
 

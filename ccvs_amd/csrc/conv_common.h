@@ -31,6 +31,11 @@ struct ConvK {
     int pt;        // host side only: persistent tiles for this launch (conv2d_bf16_pt.h): bit 0 fp32-input 128-channel layers, bit 1 packed-input layers
 };
 
+// The launch record (ccvs_conv_last_launch, conv2d_bf16.hip): every convolution launcher writes, after its launch was accepted, the
+// kernel it took, every template argument by value and its launch-time choices.  Host code, thread-local; tests read it to assert WHICH
+// instantiation a shape reached, so that a change of a dispatch heuristic fails a test instead of silently un-testing a form.
+void ccvs_conv_record_launch(const char* fmt, ...);
+
 // Staging mode of a producer / consumer instantiation (template parameter NTY of conv2d_bf16x3_pc_kernel, described at the kernel):
 // which modes fetch their activations 16 bytes per lane (aligned global_load_dwordx4 or LDS-DMA) and which dword by dword.  One
 // definition for the kernel and for ccvs_conv_fetch_bytes_per_lane (the HBM-counter scripts under tools/ ask the LIBRARY how an

@@ -18,7 +18,7 @@ EXPORTS = [
     "ccvs_gpt_embed", "ccvs_layernorm", "ccvs_gemm_workspace_bytes", "ccvs_gemm_nt", "ccvs_gemm_ln", "ccvs_gemm_ln_qkv", "ccvs_attention", "ccvs_kv_append", "ccvs_sample_topk", "ccvs_sample_topk_philox", "ccvs_sample_topn",
     "ccvs_gpt_decode_step", "ccvs_gpt_decode_status", "ccvs_gpt_program_bytes", "ccvs_gpt_decode_prepare", "ccvs_pack_u8", "ccvs_pack_u8_norm", "ccvs_stream_cu_limit", "ccvs_psnr", "ccvs_ssim_workspace_bytes", "ccvs_ssim", "ccvs_resize_bilinear",
     "ccvs_deform_conv3x3_ctx", "ccvs_gconvT4x4s2", "ccvs_flow_mask_toff", "ccvs_gaussian_blur", "ccvs_to_rgb", "ccvs_channel_head", "ccvs_mse",
-    "ccvs_token_nll", "ccvs_mean_f32",
+    "ccvs_token_nll", "ccvs_mean_f32", "ccvs_conv_last_launch",
 ]
 
 
@@ -99,6 +99,8 @@ def load():
     lib.ccvs_conv_fetch_bytes_per_lane.argtypes = [C.c_char_p]
     lib.ccvs_conv_persistent_tiles.restype = C.c_int          # (returns the previous mode, not a status)
     lib.ccvs_conv_persistent_tiles.argtypes = [C.c_int32]
+    lib.ccvs_conv_last_launch.restype = C.c_char_p            # (the record of the calling thread's last convolution launch, not a status)
+    lib.ccvs_conv_last_launch.argtypes = []
     sigs = {
         "ccvs_conv2d": [vp, vp, vp, vp, vp, C.POINTER(ConvDesc), vp],
         "ccvs_conv2d_bf16x3": [vp, vp, vp, vp, vp, C.POINTER(ConvDesc), vp],

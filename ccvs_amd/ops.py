@@ -70,6 +70,13 @@ def conv_persistent_tiles(mode=-1):
     return int(_lib.load().ccvs_conv_persistent_tiles(int(mode)))
 
 
+def conv_last_launch():
+    """Which kernel the calling thread's last successful convolution call launched (`ccvs_conv_last_launch`, host code only): e.g.
+    `pc TW=32 MB=2 NTY=3 PP=4 WPC=1 ktail=2 chunks=1 xcd=1 zi=0`, `sync TW=16 MB=1 chunks=1 xcd=0 zi=0`,
+    `pt MB=4 PP=2 p8in=0 ktail=3 xcd=1 zi=0`, `f32 TW=8 MB=2`; "" before the first one.  Tests assert it per case."""
+    return _lib.load().ccvs_conv_last_launch().decode()
+
+
 def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
@@ -193,8 +200,11 @@ def conv2d(x, w_packed, bias, cout, k, stride=1, pad=0, transposed=False, act=Fa
         ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - kw) // stride + 1
     dev = x.data.device if in_p8 else x.device
     if out_p8:
-        assert w_packed.kind == "bf16x3" and cout % 8 == 0 and out is None and residual is None and not accumulate
-        out = torch.empty(n * cout * ho * wo, dtype=torch.float32, device=dev)
+        assert w_packed.kind == "bf16x3" and cout % 8 == 0 and residual is None and not accumulate
+        if out is None:
+            out = torch.empty(n * cout * ho * wo, dtype=torch.float32, device=dev)
+        else:   # the packed buffer itself (tests hand in a poisoned one): opaque float32, n*cout*ho*wo elements
+            assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * cout * ho * wo, (out.shape, (n, cout, ho, wo))
     elif out is None:
         out = torch.empty(n, cout, ho, wo, dtype=torch.float32, device=dev)
     if not out_p8:

@@ -115,6 +115,17 @@ int ccvs_conv_fetch_bytes_per_lane(const char* kernel_name);
  * counterpart: the reference's convolutions are cuDNN calls (models/skip_vid_generator/models/skip_autoencoder.py:53-59). */
 int ccvs_conv_persistent_tiles(int32_t mode);
 
+/* Test support (host code only, no GPU call; additive, ABI version 6; no reference counterpart): which kernel the last successful
+ * ccvs_conv2d / ccvs_conv2d_bf16x3 call OF THE CALLING THREAD launched -- the kernel, every template argument by value and the
+ * launch-time choices (p.ktail; number of 1-D chunks, 1 without a CU budget; XCD tile order on / off, of the first chunk; zi):
+ *   "pc TW=32 MB=2 NTY=3 PP=4 WPC=1 ktail=2 chunks=1 xcd=1 zi=0"   conv2d_bf16x3_pc_kernel<TW, MB, NTY, PP, WPC>
+ *   "sync TW=16 MB=1 chunks=1 xcd=0 zi=0"                          conv2d_bf16x3_kernel<TW, MB, 8>
+ *   "pt MB=4 PP=2 p8in=0 ktail=3 xcd=1 zi=0"                       conv2d_bf16x3_pt_kernel<MB, PP, P8IN>
+ *   "f32 TW=8 MB=2"                                                conv2d_mfma_kernel<TW, MB>
+ * "" before the thread's first convolution.  The string is thread-local storage of the library, valid until the thread's next
+ * convolution call.  tests/test_conv_forms_gpu.py asserts it per case, so a dispatcher change fails a test instead of un-testing a form. */
+const char* ccvs_conv_last_launch(void);
+
 /* ---- FIR resampling ------------------------------------------------------------------
  * Replaces upfirdn2d(input, kernel, up, down, pad) (modules/upfirdn2d.py:145-159, CUDA
  * upfirdn2d_kernel.cu:107-207, pybind upfirdn2d.cpp:21-23) for the 4-tap separable

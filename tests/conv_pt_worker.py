@@ -5,7 +5,11 @@ workgroup somewhere (the two register sets of the staging stream change roles fr
 
 With `budget` as a second argument it is the worker of tests/test_cu_budget_gpu.py::test_packed_convolutions_under_a_budget instead: the
 packed (P8) layers of the InterBlock chain with `ccvs_conv_desc.cu_limit` = 3, 61 and 0 (in that order, every result kept alive, so
-that no launch gets memory an earlier one has filled), with their inputs and weights for the parent's float64 reference."""
+that no launch gets memory an earlier one has filled), with their inputs and weights for the parent's float64 reference.
+
+Either way the launch record of every result (`ops.conv_last_launch()` right after the call that produced it) goes into the file as
+`records`, a JSON object by result name: the parents assert which kernel each launch took."""
+import json
 import os
 import sys
 
@@ -17,7 +21,22 @@ from ccvs_amd import ops  # noqa: E402
 
 ops.CONV_PRECISION = "bf16x3"
 g = torch.Generator().manual_seed(23)
-out = {}
+
+
+class Results(dict):
+    """name -> result; storing one notes the record of the convolution launched last (inputs stored before any launch: "")."""
+    records = {}
+
+    def __setitem__(self, key, value):
+        super().__setitem__(key, value)
+        self.records[key] = ops.conv_last_launch()
+
+    def save(self, path):
+        torch.cuda.synchronize()
+        np.savez(path, records=np.array(json.dumps(self.records)), **{k: v.cpu().numpy() for k, v in self.items()})
+
+
+out = Results()
 
 
 def rnd(*shape, scale=1.0):
@@ -59,8 +78,7 @@ def budget_cases():
 
 if sys.argv[2:] == ["budget"]:
     budget_cases()
-    torch.cuda.synchronize()
-    np.savez(sys.argv[1], **{k: v.cpu().numpy() for k, v in out.items()})
+    out.save(sys.argv[1])
     sys.exit(0)
 
 # fp32 input, 128 output channels: 99 (K tail r = 3), 49 (r = 1), 195, 96 (no tail), 128; 64 x 64 images (16 tiles of 8 x 32, 8 of 16 x 32 each), 72 images = 1152 / 576 tiles: 4.5 / 2.25 per workgroup
@@ -94,5 +112,4 @@ wp, b = layer(99, 128)
 out["ragged"] = ops.conv2d(x, wp, b, 128, 3, pad=1, act=True)
 x = rnd(4, 99, 64, 64)
 out["few"] = ops.conv2d(x, wp, b, 128, 3, pad=1, act=True)
-torch.cuda.synchronize()
-np.savez(sys.argv[1], **{k: v.cpu().numpy() for k, v in out.items()})
+out.save(sys.argv[1])

@@ -40,6 +40,29 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert handle.ccvs_abi_version() == 6
 
 
+def test_conv_last_launch_is_declared_exported_and_empty_without_a_launch(built_lib):
+    """`ccvs_conv_last_launch` (include/ccvs_hip.h): additive to ABI 6, host code -- callable with no GPU, "" on a thread that has launched
+    no convolution; a refused call (CPU tensors never reach the library, a bad descriptor does) leaves it alone."""
+    import threading
+    from ccvs_amd import ops
+    assert "ccvs_conv_last_launch" in header_symbols() and "ccvs_conv_last_launch" in built_lib.EXPORTS and len(built_lib.EXPORTS) == 51
+    L = built_lib.load()
+    seen = []
+    t = threading.Thread(target=lambda: seen.append(ops.conv_last_launch()))   # a fresh thread: its own (empty) record
+    t.start()
+    t.join()
+    assert seen == [""]
+    before = ops.conv_last_launch()
+    d = built_lib.ConvDesc()
+    d.N = d.Cin = d.Cout = d.Hin = d.Win = 1
+    d.kh, d.kw, d.CoutPad = 2, 3, 32   # unsupported kernel shape: refused before any GPU call
+    one = ctypes.c_void_p(16)
+    for fn in (L.ccvs_conv2d, L.ccvs_conv2d_bf16x3):
+        assert fn(one, one, None, None, one, ctypes.byref(d), None) != 0
+    assert ops.conv_last_launch() == before
+    assert L.ccvs_abi_version() == 6
+
+
 def test_conv_desc_layout_matches_c(built_lib, tmp_path):
     fields = [f[0] for f in built_lib.ConvDesc._fields_]
     prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ccvs_hip.h"\nint main(){printf("%zu", sizeof(ccvs_conv_desc));\n'

@@ -37,6 +37,7 @@ the two budgets, so a later change of a tile size fails here instead of silently
                 backwarp_p8_kernel ......... test_backwarp_p8
                 tap_shift_add_kernel<4> / <1> .................. test_conv_heads[*-w4], [*-odd]
 The packed-input / packed-output convolutions (chunked 1-D launches under `ccvs_conv_desc.cu_limit`) are the last test."""
+import json
 import math
 import os
 import subprocess
@@ -482,6 +483,16 @@ def test_packed_convolutions_under_a_budget(tmp_path, mode):
                    check=True, timeout=600)
     z = np.load(path)
     T = lambda key: torch.from_numpy(z[key]).double()
+    # which kernels ran (ops.conv_last_launch() per result): 6 images of 40 x 64 are 60 tiles, so the dispatcher halves every layer's channel
+    # block to 32 (MB = 1) -- never persistent tiles, a budget of 3 in chunks, no budget in one launch
+    records = json.loads(str(z["records"]))
+    forms = {"l1": "pc TW=32 MB=1 NTY=3 PP=2 WPC=1 ktail=3 ", "l2": "pc TW=32 MB=1 NTY=-83 PP=2 WPC=1 ktail=0 ", "l3": "pc TW=32 MB=1 NTY=-83 PP=2 WPC=1 ktail=0 "}
+    for name, form in forms.items():
+        for lim in (3, 61, 0):
+            rec = records[f"{name}_{lim}"]
+            assert rec.startswith(form) and rec.endswith(" zi=3" if name == "l1" else " zi=0"), (name, lim, rec)
+            chunks = int(rec.split(" chunks=")[1].split()[0])
+            assert (chunks == 1) if lim == 0 else (chunks > 1 or lim == 61), (name, lim, rec)
 
     def decode(data, c):   # P8Act.float()
         n, h, w = 6, 40, 64

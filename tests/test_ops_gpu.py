@@ -127,12 +127,26 @@ def test_conv_oracle_shapes(ops, cin, cout, k, stride, hw):
     close(got, want)
 
 
+TALL_TILE_RECORDS = {   # ops.conv_last_launch() of the first call of each case of test_conv_tall_tile_shapes, by (cin, cout)
+    (128, 64, 48): "pc TW=32 MB=1 NTY=3 PP=2 WPC=1 ktail=0 chunks=1 xcd=1 zi=0",
+    (64, 32, 40): "pc TW=32 MB=1 NTY=3 PP=2 WPC=1 ktail=0 chunks=1 xcd=0 zi=0",
+    (32, 27, 33): "pc TW=32 MB=1 NTY=1 PP=2 WPC=1 ktail=0 chunks=1 xcd=0 zi=0",
+    (99, 64, 37): "pc TW=32 MB=1 NTY=3 PP=2 WPC=1 ktail=3 chunks=1 xcd=1 zi=0",
+    (128, 64, 256): "pc TW=32 MB=2 NTY=3 PP=4 WPC=1 ktail=0 chunks=1 xcd=1 zi=0",
+    (17, 5, 32): "pc TW=32 MB=1 NTY=3 PP=2 WPC=1 ktail=1 chunks=1 xcd=0 zi=0",
+}
+
+
 @pytest.mark.parametrize("cin,cout,k,kw,hw", [(128, 64, 3, 3, (48, 64)), (64, 32, 3, 3, (40, 36)), (32, 27, 1, 9, (33, 64)), (99, 64, 3, 3, (37, 100)),
                                               (128, 64, 3, 3, (256, 256)), (17, 5, 3, 3, (32, 40))])
 def test_conv_tall_tile_shapes(ops, cin, cout, k, kw, hw):
-    """33 .. 64 output channels on dense stride-1 rows of >= 32 lines run the 512-pixel tile (PP = 4: four pixel blocks per MFMA wave,
-    two activation items per staging thread): ragged heights / widths, a channel tail, the 1 x 9 head shape, pre-activation
-    addend + residual + accumulate through its epilogue; and the same bits with a CU budget (which takes the 256-pixel form)."""
+    """Dense stride-1 rows of >= 32 lines, at most 64 output channels: ragged heights / widths, a channel tail, the 1 x 9 head shape,
+    residual and accumulate through the epilogue; and the same bits with a CU budget (chunked 1-D launches of the 256-pixel form).
+    Written for the 512-pixel tile (PP = 4); since the dispatcher halves the channel block of launches under 256 workgroups, three
+    images of these sizes run the 32-channel 256-pixel form (`TALL_TILE_RECORDS`, asserted per case: `<32, 1, 3>` with and without the packed K
+    tail, `<32, 1, 1>` for the 1 x 9 head) and only the single 256 x 256 image still reaches `<32, 2, 3, 4>` and, under the budget,
+    `<32, 2, 3>`.  The ragged 512-pixel cases are in tests/test_conv_forms_gpu.py."""
+    record = TALL_TILE_RECORDS[cin, cout, hw[0]]
     torch.manual_seed(cin + 3 * cout)
     n = 1 if hw[0] > 100 else 3
     x = torch.randn(n, cin, *hw)
@@ -144,8 +158,10 @@ def test_conv_tall_tile_shapes(ops, cin, cout, k, kw, hw):
     pk = ops.pack_conv_weight(w.cuda())
     got = ops.conv2d(x.cuda(), pk, b.cuda(), cout, k, pad=kw // 2 if k == 1 else k // 2, act=True, residual=res.cuda(), out_scale=1 / math.sqrt(2)) \
         if k == kw else None
+    assert got is None or ops.conv_last_launch() == record
     if got is None:   # the 1 x k head form: padding on x only
         got = ops.conv2d(x.cuda(), pk, b.cuda(), cout, k, pad=kw // 2, act=True)
+        assert ops.conv_last_launch() == record
         hp = got.shape[2]
         got = (got[:, :, (hp - hw[0]) // 2:(hp - hw[0]) // 2 + hw[0]] + res.cuda()) / math.sqrt(2)
     close(got, want, 2e-4)
@@ -153,8 +169,11 @@ def test_conv_tall_tile_shapes(ops, cin, cout, k, kw, hw):
         ops.CONV_CU_LIMIT = 7
         try:
             budget = ops.conv2d(x.cuda(), pk, b.cuda(), cout, k, pad=k // 2, act=True, residual=res.cuda(), out_scale=1 / math.sqrt(2))
+            rec_b = ops.conv_last_launch()
         finally:
             ops.CONV_CU_LIMIT = 0
+        form, chunks = rec_b.split(" chunks=")   # (how many chunks: the budget x the instantiation's occupancy)
+        assert form == record.split(" chunks=")[0].replace("PP=4", "PP=2") and int(chunks.split()[0]) > 1, rec_b
         assert torch.equal(budget, got), "the 256- and the 512-pixel tile must round identically"
         base = torch.randn(n, cout, *hw).cuda()
         acc = base.clone()
@@ -935,7 +954,12 @@ def test_conv_persistent_tiles_are_bit_identical(tmp_path):
     reads it once): fp32 input with and without the packed K tail, packed input (256- and 512-pixel tiles), fp32 and packed output,
     every epilogue addend (pre-activation image with the shared-image tile order, residual + scale, accumulate), two channel blocks
     per position, workgroups with odd and even tile counts -- and shapes the persistent form must refuse.  Same arithmetic per
-    output in the same order: the same bits.  (Reference of the layer: skip_autoencoder.py:53-59.)"""
+    output in the same order: the same bits.  (Reference of the layer: skip_autoencoder.py:53-59.)
+    The worker saves `ops.conv_last_launch()` per result: with the switch on (3: both bits) every launch meant for the persistent form
+    must record `pt ...` -- except the 49-channel layer with fp32 output, which the dispatcher gives to the two-workgroups-per-CU form
+    (`WPC=2`, 64-channel blocks: no persistent form exists for it; its packed-output launches stay 128-channel and are persistent) --
+    the `ragged` and `few` launches must not, and nothing does with the switch off."""
+    import json
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
@@ -945,10 +969,20 @@ def test_conv_persistent_tiles_are_bit_identical(tmp_path):
         env = dict(os.environ, CCVS_CONV_PT=flag)
         subprocess.run([sys.executable, os.path.join(here, "conv_pt_worker.py"), path], env=env, check=True, timeout=900)
         outs.append(np.load(path))
-    assert sorted(outs[0].files) == sorted(outs[1].files) and len(outs[0].files) == 5 * 8 + 3
+    assert sorted(outs[0].files) == sorted(outs[1].files) and len(outs[0].files) == 5 * 8 + 3 + 1
+    off, on = (json.loads(str(o["records"])) for o in outs)
     for key in outs[0].files:
+        if key == "records":
+            continue
         a, b = outs[0][key], outs[1][key]
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), key
+        assert off[key].startswith("pc "), (key, off[key])
+        wpc2 = key in ("f32_49", "pre_49", "res_49", "acc_49")
+        assert on[key].startswith("pt ") == (key not in ("ragged", "few") and not wpc2), (key, on[key])
+        if wpc2:
+            assert "WPC=2 ktail=1" in on[key] and on[key] == off[key], (key, on[key], off[key])
+    assert on["f32_99"].startswith("pt MB=4 PP=2 p8in=0 ktail=3") and on["chain64_99"].startswith("pt MB=2 PP=4 p8in=1 ktail=0") \
+        and on["chain128_99"].startswith("pt MB=4 PP=2 p8in=1 ktail=0"), on
     assert np.isfinite(outs[0]["f32_99"]).all() and np.abs(outs[0]["f32_99"]).max() > 0.1
 
 
