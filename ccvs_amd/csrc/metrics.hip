@@ -188,6 +188,172 @@ extern "C" int ccvs_mean_f32(const float* x, int64_t n, float* out, void* stream
     return CCVS_OK;
 }
 
+// ---- frame autoencoder validation (quantized_video_model.py:460-480, quantize.py:59-68) ------------------------------------------
+// Three HBM-bound reductions behind `eval_img_to_img_generator`: the L1 between a frame batch and its reconstruction, the quantiser's
+// loss term with the code histogram, and the perplexity of that histogram.  float64 inside, no float atomics, every partial sum
+// written by one workgroup and added in a fixed order: the same bits on every run.
+
+// torch.mean(torch.abs(a - b)), stage 1: workgroup g of G adds |a[i] - b[i]| over the quads g * 1024 + t, (g + G) * 1024 + t, ...
+// (16-byte loads where both bases are 16-byte aligned) and over the elements behind the last whole quad -- all of them when a base is
+// not aligned -- with the same stride, and writes one float64 partial.  G is a function of n alone (`l1_groups`).
+#define L1_PER_GROUP 16384   // elements a workgroup is given before another one is launched: 4 quads per lane
+#define L1_MAX_GROUPS 1024
+static inline long l1_groups(long n) {
+    const long g = cdiv64(n, L1_PER_GROUP);
+    return g < 1 ? 1 : (g > L1_MAX_GROUPS ? L1_MAX_GROUPS : g);
+}
+
+__global__ __launch_bounds__(1024) void l1_partial_kernel(const float* __restrict__ a, const float* __restrict__ b, double* __restrict__ part, long n) {
+    double acc = 0.0;
+    const long n4 = ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0 ? n / 4 : 0;
+    const float4* a4 = reinterpret_cast<const float4*>(a);
+    const float4* b4 = reinterpret_cast<const float4*>(b);
+    const long first = (long)blockIdx.x * 1024 + threadIdx.x, step = (long)gridDim.x * 1024;
+    for (long i = first; i < n4; i += step) {
+        const float4 u = a4[i], v = b4[i];
+        acc += (fabs((double)u.x - (double)v.x) + fabs((double)u.y - (double)v.y)) + (fabs((double)u.z - (double)v.z) + fabs((double)u.w - (double)v.w));
+    }
+    for (long i = 4 * n4 + first; i < n; i += step) acc += fabs((double)a[i] - (double)b[i]);
+    const double s = block_sum_f64(acc);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// stage 2 of a two-stage mean: `count` (<= 1024) float64 partials through LDS, added by thread 0 in index order, divided by n and
+// rounded once to fp32.  A NaN partial gives NaN.
+__global__ __launch_bounds__(1024) void partials_mean_kernel(const double* __restrict__ part, int count, double n, float* __restrict__ out) {
+    __shared__ double p[1024];
+    if ((int)threadIdx.x < count) p[threadIdx.x] = part[threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int g = 0; g < count; ++g) s += p[g];
+    out[0] = (float)(s / n);
+}
+
+extern "C" int64_t ccvs_l1_workspace_bytes(int64_t n) { return n > 0 ? l1_groups((long)n) * (int64_t)sizeof(double) : 0; }
+
+extern "C" int ccvs_l1_mean(const float* a, const float* b, float* out, void* workspace, int64_t n, void* stream) {
+    CCVS_REQUIRE(a && b && out && workspace, "ccvs_l1_mean: null pointer");
+    CCVS_REQUIRE(n > 0, "ccvs_l1_mean: no elements");
+    const long groups = l1_groups((long)n);
+    hipLaunchKernelGGL(l1_partial_kernel, dim3((unsigned)groups), dim3(1024), 0, (hipStream_t)stream, a, b, (double*)workspace, (long)n);
+    CCVS_CHECK_LAUNCH("ccvs_l1_mean");
+    hipLaunchKernelGGL(partials_mean_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double*)workspace, (int)groups, (double)n, out);
+    CCVS_CHECK_LAUNCH("ccvs_l1_mean");
+    return CCVS_OK;
+}
+
+// The quantiser's statistics.  z [N, C, HW] is read once: a 256-thread workgroup owns 64 consecutive positions p = n * HW + hw (the
+// lanes of a wave: every channel row of z is read as coalesced runs) and VQ_CB consecutive channels, which its four waves share in
+// blocks of four -- wave w takes the channels c0 + 4 (w + 4 j) .. + 3.  A lane gathers its code's four entries of those channels with
+// one 16-byte load where the codebook allows it (C % 4 == 0, 16-byte aligned base), entry by entry otherwise; the rows come from L2.
+// (s * e - z)^2 is formed and added in float64; the workgroup's sum (butterfly, then its waves in index order) is one float64 partial,
+// part[channel block][position tile].  A lane whose index is outside [0, n_e) reads no codebook row, counts nothing and adds NaN.
+// The histogram is integer: the workgroups of channel block 0 add 1 to counts[idx[p]] with a vector atomic (order-independent).
+#define VQ_CB 64
+__global__ __launch_bounds__(256) void vq_stats_kernel(const float* __restrict__ z, const int64_t* __restrict__ idx, const float* __restrict__ cb,
+                                                        const float* __restrict__ row_scale, double* __restrict__ part, int* __restrict__ counts,
+                                                        long P, int C, int HW, int n_e, int vec) {
+    __shared__ double wpart[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long p = (long)blockIdx.x * 64 + lane;
+    const int c0 = blockIdx.y * VQ_CB, c1 = min(C, c0 + VQ_CB);
+    double acc = 0.0;
+    if (p < P) {
+        const int64_t code = idx[p];
+        const bool ok = code >= 0 && code < n_e;
+        if (!ok) {
+            acc = __builtin_nan("");
+        } else {
+            if (blockIdx.y == 0 && wave == 0) atomicAdd(counts + code, 1);
+            const long n = p / HW;
+            const float* zp = z + n * (long)C * HW + (p - n * HW);   // + c * HW
+            const float* e = cb + code * (long)C;
+            const double s = row_scale ? (double)row_scale[code] : 1.0;
+            for (int c = c0 + 4 * wave; c < c1; c += 16) {
+                float ev[4];
+                if (vec) {   // C % 4 == 0: the four channels are inside the row
+                    const float4 q = *reinterpret_cast<const float4*>(e + c);
+                    ev[0] = q.x; ev[1] = q.y; ev[2] = q.z; ev[3] = q.w;
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) ev[k] = c + k < c1 ? e[c + k] : 0.f;
+                }
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (c + k < c1) {
+                        const double d = s * (double)ev[k] - (double)zp[(long)(c + k) * HW];
+                        acc += d * d;
+                    }
+            }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    if (lane == 0) wpart[wave] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = ((wpart[0] + wpart[1]) + wpart[2]) + wpart[3];
+}
+
+// `count` float64 partials -> their sum / n as fp32: thread t adds the partials t, t + 1024, ... in that order, then `block_sum_f64`.
+__global__ __launch_bounds__(1024) void partials_mean_strided_kernel(const double* __restrict__ part, long count, double n, float* __restrict__ out) {
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < count; i += 1024) acc += part[i];
+    const double s = block_sum_f64(acc);
+    if (threadIdx.x == 0) out[0] = (float)(s / n);
+}
+
+extern "C" int64_t ccvs_vq_stats_workspace_bytes(int64_t N, int32_t C, int32_t HW) {
+    if (N <= 0 || C <= 0 || HW <= 0) return 0;
+    return cdiv64(N * HW, 64) * cdiv64(C, VQ_CB) * (int64_t)sizeof(double);
+}
+
+extern "C" int ccvs_vq_stats(const float* z, const int64_t* idx, const float* codebook, const float* row_scale, float* sq_sum_out, int32_t* counts,
+                             void* workspace, int64_t N, int32_t C, int32_t HW, int32_t n_e, void* stream) {
+    CCVS_REQUIRE(z && idx && codebook && sq_sum_out && counts && workspace, "ccvs_vq_stats: null pointer");
+    CCVS_REQUIRE(N > 0 && C > 0 && HW > 0 && n_e > 0, "ccvs_vq_stats: bad arguments");
+    const long P = (long)N * HW, tiles = cdiv64(P, 64), blocks = cdiv64(C, VQ_CB);
+    CCVS_REQUIRE(tiles < 2147483647L && blocks <= 65535, "ccvs_vq_stats: N * HW < 2^37, C <= 4194240; got N %ld, HW %d, C %d", (long)N, HW, C);
+    if (hipMemsetAsync(counts, 0, (size_t)n_e * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) {
+        ccvs_set_error("ccvs_vq_stats: clearing counts failed");
+        return CCVS_ERR_LAUNCH;
+    }
+    const int vec = C % 4 == 0 && (reinterpret_cast<uintptr_t>(codebook) & 15) == 0;
+    hipLaunchKernelGGL(vq_stats_kernel, dim3((unsigned)tiles, (unsigned)blocks), dim3(256), 0, (hipStream_t)stream, z, idx, codebook, row_scale,
+                       (double*)workspace, counts, P, C, HW, n_e, vec);
+    CCVS_CHECK_LAUNCH("ccvs_vq_stats");
+    hipLaunchKernelGGL(partials_mean_strided_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, (const double*)workspace, tiles * blocks,
+                       (double)P * (double)C, sq_sum_out);
+    CCVS_CHECK_LAUNCH("ccvs_vq_stats");
+    return CCVS_OK;
+}
+
+// quantize.py:67-68: exp(-sum_j p_j log(p_j + 1e-10)), p_j = counts[j] / total, by one workgroup in float64: thread t adds the terms
+// of the run j = t * run .. (t + 1) * run - 1 in index order, thread 0 adds the 1024 runs in index order; rounded once to fp32.
+__global__ __launch_bounds__(1024) void code_perplexity_kernel(const int* __restrict__ counts, int n_e, double total, float* __restrict__ out) {
+    __shared__ double runs[1024];
+    const int run = (n_e + 1023) / 1024;
+    double acc = 0.0;
+    for (int j = threadIdx.x * run; j < min(n_e, (int)(threadIdx.x + 1) * run); ++j) {
+        const double pj = (double)counts[j] / total;
+        acc += pj * log(pj + 1e-10);
+    }
+    runs[threadIdx.x] = acc;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int t = 0; t < 1024; ++t) s += runs[t];
+    out[0] = (float)exp(-s);
+}
+
+extern "C" int ccvs_code_perplexity(const int32_t* counts, int32_t n_e, int64_t total, float* out, void* stream) {
+    CCVS_REQUIRE(counts && out, "ccvs_code_perplexity: null pointer");
+    CCVS_REQUIRE(n_e > 0 && n_e <= 1048576 && total > 0, "ccvs_code_perplexity: 1 <= n_e <= 2^20, total > 0; got n_e %d, total %ld", n_e, (long)total);
+    hipLaunchKernelGGL(code_perplexity_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, n_e, (double)total, out);
+    CCVS_CHECK_LAUNCH("ccvs_code_perplexity");
+    return CCVS_OK;
+}
+
 // ---- SSIM -------------------------------------------------------------------------------------
 // A workgroup owns a 32 x 32 block of window CENTRES of one plane: the 38 x 38 pixels under them go to LDS, the five window sums
 // (x, y, xx, yy, xy) are formed separably in float64 -- 7 columns, then 7 rows -- and the block's sum of S is written to

@@ -233,6 +233,35 @@ class Generator:
             encoded_data["state_code"] = blurred_encoded["code"]
         return self.transformer_model(encoded_data, mode='transformer', prefix="vid_", log=log, global_iter=global_iter)   # :84
 
+    @torch.no_grad()
+    def autoencoder_report(self, data, max_frames=None):
+        """The frame autoencoder's validation figures for a clip batch: `data["vid"]` [B, T, 3, H, W] as B * T frames through
+        `QVidModel.eval_reconstruction`, in chunks of at most `max_frames` frames (default: batch_size_vid * vid_len, a generation
+        batch).  The chunks are combined exactly: "l1" and "quant_loss" are means weighted by the chunks' element counts (float64 on
+        the device, rounded once), "code_counts" are added, "perplexity" and "codes_used" are taken from the total counts, "code" is
+        [B * T, h * w].  The dict of `eval_reconstruction` without "fake_img"; device tensors, nothing synchronised."""
+        vid = data["vid"]
+        frames = vid.reshape(-1, *vid.shape[-3:])
+        step = int(max_frames) if max_frames is not None else int(self.opt.batch_size_vid) * int(self.opt.vid_len)
+        assert step > 0 and frames.shape[0] > 0, (step, frames.shape)
+        parts = [self.vid_model.eval_reconstruction(frames[lo:lo + step]) for lo in range(0, frames.shape[0], step)]
+        if len(parts) == 1:
+            rep = dict(parts[0])
+        else:
+            w = torch.tensor([min(step, frames.shape[0] - lo) for lo in range(0, frames.shape[0], step)], dtype=torch.float64,
+                             device=parts[0]["l1"].device) / frames.shape[0]   # frames are one size: element counts are frame counts
+            counts = torch.stack([p["code_counts"] for p in parts]).sum(dim=0, dtype=torch.int32)
+            rep = {k: (torch.stack([p[k] for p in parts]).double() * w).sum().float() for k in ("l1", "quant_loss")}
+            rep.update(code_counts=counts, codes_used=(counts > 0).sum(), code=torch.cat([p["code"] for p in parts]),
+                       perplexity=ops.code_perplexity(counts, sum(p["code"].numel() for p in parts)))
+        rep.pop("fake_img", None)
+        return rep
+
+    def autoencoder_loss(self, data):
+        """The frame autoencoder's validation L1 of a clip batch (`autoencoder_report`'s "l1"): the figure of a `qvid_*` checkpoint,
+        beside `transformer_loss`."""
+        return self.autoencoder_report(data)["l1"]
+
     def _frames_to_encode(self, n_frames, size):
         """Frames of the input clip the encoder has to see.  The reference encodes all of them (generator.py:69); with
         `--encode_all false` only those the conditioning crop keeps (generator.py:93-99: the first crop_prop of the codes and of

@@ -20,6 +20,8 @@ EXPORTS = [
     "ccvs_deform_conv3x3_ctx", "ccvs_gconvT4x4s2", "ccvs_flow_mask_toff", "ccvs_gaussian_blur", "ccvs_to_rgb", "ccvs_channel_head", "ccvs_mse",
     "ccvs_token_nll", "ccvs_mean_f32", "ccvs_conv_last_launch",
 ]
+# every symbol include/ccvs_hip_eval.h declares (the frame autoencoder's validation reductions; ccvs_hip.h includes that header)
+EVAL_EXPORTS = ["ccvs_l1_workspace_bytes", "ccvs_l1_mean", "ccvs_vq_stats_workspace_bytes", "ccvs_vq_stats", "ccvs_code_perplexity"]
 
 
 class ConvDesc(C.Structure):
@@ -93,6 +95,10 @@ def load():
     lib.ccvs_gemm_workspace_bytes.argtypes = []
     lib.ccvs_ssim_workspace_bytes.restype = C.c_int64
     lib.ccvs_ssim_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.ccvs_l1_workspace_bytes.restype = C.c_int64
+    lib.ccvs_l1_workspace_bytes.argtypes = [C.c_int64]
+    lib.ccvs_vq_stats_workspace_bytes.restype = C.c_int64
+    lib.ccvs_vq_stats_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     lib.ccvs_gpt_program_bytes.restype = C.c_int64
     lib.ccvs_gpt_program_bytes.argtypes = [C.c_int32]
     lib.ccvs_conv_fetch_bytes_per_lane.restype = C.c_int
@@ -146,6 +152,9 @@ def load():
         "ccvs_mse": [vp, vp, vp, i64, vp],
         "ccvs_token_nll": [vp, i64, vp, vp, i64, i32, vp, vp],
         "ccvs_mean_f32": [vp, i64, vp, vp],
+        "ccvs_l1_mean": [vp, vp, vp, vp, i64, vp],
+        "ccvs_vq_stats": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
+        "ccvs_code_perplexity": [vp, i32, i64, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

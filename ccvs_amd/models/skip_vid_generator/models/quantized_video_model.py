@@ -11,17 +11,19 @@ Differences that do not change results:
   * re-encoding a synthesized frame inside the decode loop (:875-878) skips the vector
     quantiser, whose output that loop discards;
   * `embed_code` + two transposes (:832-833) is one gather kernel writing NCHW.
-Training modes, layout decoders and continuous codes are outside the hot path and raise.
+`eval_img_to_img_generator` (:460-480), the frame autoencoder's validation L1, runs; `eval_reconstruction` adds the quantiser's loss
+and codebook usage from the same pass.  Training modes, layout decoders and continuous codes are outside the hot path and raise.
 """
 import torch
 
 from .skip_autoencoder import SkipGANDecoder, SkipGANEncoder, prepare_packed_modules
 from ..modules.quantize import VectorQuantizer
+from ccvs_amd import ops
 from ccvs_amd.tools.utils import to_cuda
 from ccvs_amd.models import load_network, print_network
 
-_TRAIN_MODES = ("img_to_img_generator", "eval_img_to_img_generator", "vid_to_vid_generator", "img_discriminator",
-                "img_discriminator_reg", "vid_discriminator_reg", "vid_discriminator")
+_TRAIN_MODES = ("img_to_img_generator", "vid_to_vid_generator", "img_discriminator", "img_discriminator_reg", "vid_discriminator_reg",
+                "vid_discriminator")
 
 
 class QVidModel(torch.nn.Module):
@@ -37,9 +39,11 @@ class QVidModel(torch.nn.Module):
     def forward(self, data, fake_data={}, mode='', log=False, suffix="", cond_frames=None, global_iter=None):
         if mode in _TRAIN_MODES:
             raise NotImplementedError(f"mode '{mode}' (training) is outside the MI355X hot path")
-        if mode not in ("img_encoder", "vid_encoder", "img_decoder", "vid_decoder", "vid_step_decoder"):
+        if mode not in ("eval_img_to_img_generator", "img_encoder", "vid_encoder", "img_decoder", "vid_decoder", "vid_step_decoder"):
             raise ValueError(f"mode '{mode}' is invalid")
         real_img, real_vid, code, state_code, inter, interl, cond_inter = self.preprocess_input(data)
+        if mode == 'eval_img_to_img_generator':
+            return self.eval_reconstruction(real_img, log, global_iter)["l1"]
         if mode == 'img_encoder':
             return self.encode(real_img, None, "img", log, suffix, global_iter)
         if mode == 'vid_encoder':
@@ -91,6 +95,29 @@ class QVidModel(torch.nn.Module):
         stream i % D) calls this once and orders those streams behind it: the caches are plain Python attributes, nothing else
         orders a pack kernel on one stream before a reader on another.  Cheap when everything is already packed."""
         prepare_packed_modules(self)
+
+    # ------------------------------------------------------------------ validation
+    @torch.no_grad()
+    def eval_reconstruction(self, img, log=False, global_iter=None):
+        """quantized_video_model.py:460-480 (`compute_eval_img_to_img_generator_loss`) with the quantiser's diagnostics from the same
+        pass: img [N, 3, H, W] -> encoder -> quantiser -> decoder on the frame's own skip features (the decoder's default
+        arguments).  One encode and one decode per call.  Returns device tensors, nothing synchronised:
+          "l1"          0-dim fp32, mean |img - fake_img|: what mode 'eval_img_to_img_generator' returns
+          "quant_loss"  0-dim fp32, (1 + beta) mean((z_q - z)^2) (quantize.py:60-61)
+          "perplexity"  0-dim fp32, exp of the entropy of the code frequencies (quantize.py:67-68)
+          "codes_used"  0-dim int64, codes chosen at least once;  "code_counts" int32 [z_num]
+          "code"        int64 [N, h * w];  "fake_img" [N, 3, H, W]
+        With a logger and `log` the two images are logged under the reference's names (:476-478)."""
+        real_img = img if img.is_cuda else img.cuda()
+        z, inter_enc = self.net_e(real_img)
+        z_q, q_loss, (perplexity, counts, idx) = self.net_q.forward_with_stats(z)
+        fake_img, _ = self.net_g(z_q, [inter_enc])
+        loss = ops.l1_mean(real_img, fake_img)
+        if self.logger and log:
+            self.logger.log_img("qvid_generator/eval_fake_img", fake_img[:16].float().cpu(), 4, global_iter, normalize=True, span=(-1, 1))
+            self.logger.log_img("qvid_generator/eval_real_img", real_img[:16].float().cpu(), 4, global_iter, normalize=True, span=(-1, 1))
+        return {"l1": loss, "quant_loss": q_loss, "perplexity": perplexity, "codes_used": (counts > 0).sum(), "code_counts": counts,
+                "code": idx.view(z.shape[0], -1), "fake_img": fake_img}
 
     # ------------------------------------------------------------------ encode
     @torch.no_grad()

@@ -31,7 +31,8 @@ class VectorQuantizer(nn.Module):
             if pad:  # padding codes sit at distance +inf: never the nearest
                 cbt = torch.cat([cbt, torch.zeros(cbt.shape[0], pad, dtype=cbt.dtype, device=cbt.device)], dim=1).contiguous()
                 esq = torch.cat([esq, torch.full((pad,), float("inf"), dtype=esq.dtype, device=esq.device)]).contiguous()
-            self._packed = (key, cbt, esq)
+            # 1 / ||e_j||_2 per row: `normalize` divides z_q by its norm before the loss (quantize.py:56-61)
+            self._packed = (key, cbt, esq, (1.0 / torch.norm(wd, p=2, dim=1)).contiguous())
         return self._packed[1], self._packed[2]
 
     def _as_nchw(self, z):
@@ -58,6 +59,19 @@ class VectorQuantizer(nn.Module):
         if self.normalize:   # quantize.py:56-57: z_q / ||z_q||_2 over the channels; embed_code keeps the raw rows (quantize.py:76-83)
             zq = ops.l2_normalize_channels_(zq.view(z4.shape[0], -1, z4.shape[2], z4.shape[3]))
         return zq.view(z.shape), None, (None, None, idx.unsqueeze(1))
+
+    @torch.no_grad()
+    def forward_with_stats(self, z):
+        """`forward` with the reference's diagnostics (quantize.py:59-68): (z_q, loss, (perplexity, counts, indices[N,1])).
+        loss = m + beta * m with m = mean((z_q - z)^2) -- the reference's two terms differ in what they detach, not in value; z_q is
+        the normalised row under `normalize`.  perplexity = exp(-sum p log(p + 1e-10)) of the code frequencies.  `counts` (int32
+        [n_e]) stands where the reference returns the [positions, n_e] one-hot matrix, which is never built.  loss and perplexity are
+        0-dim fp32 tensors on the device; nothing is synchronised."""
+        zq, _, (_, _, idx) = self.forward(z)
+        z4 = self._as_nchw(z)
+        m, counts = ops.vq_stats(z4, idx.view(-1), self.embedding.weight.detach(), self._packed[3] if self.normalize else None)
+        perplexity = ops.code_perplexity(counts, idx.numel())
+        return zq, m + self.beta * m, (perplexity, counts, idx)
 
     @torch.no_grad()
     def embed_code(self, code):

@@ -941,6 +941,55 @@ def mean_f32(x):
     return out
 
 
+def l1_mean(a, b):
+    """torch.mean(torch.abs(a - b)) of two fp32 tensors of one shape, float64 inside, as a 0-dim fp32 tensor on the device
+    (`ccvs_l1_mean`: a grid of workgroups, partial sums added in index order; nothing is synchronised)."""
+    _need_gpu(a, b)
+    assert a.shape == b.shape and a.dtype == b.dtype == torch.float32 and a.numel() > 0, (a.shape, b.shape)
+    a, b = a.contiguous(), b.contiguous()
+    L = _lib.load()
+    out = torch.empty((), dtype=torch.float32, device=a.device)
+    ws = torch.empty(int(L.ccvs_l1_workspace_bytes(a.numel())), dtype=torch.uint8, device=a.device)
+    _lib.check(L.ccvs_l1_mean(_p(a), _p(b), _p(out), _p(ws), a.numel(), _stream()), "ccvs_l1_mean")
+    return out
+
+
+def vq_stats(z_nchw, idx, codebook, row_scale=None):
+    """The quantiser's diagnostics (`ccvs_vq_stats`): (mean_sq, counts).  z_nchw [N, C, H, W] fp32, idx int64 [N*H*W] in (n, h, w)
+    order, codebook [n_e, C] fp32, row_scale [n_e] fp32 or None.  mean_sq: 0-dim fp32, the mean over every element of
+    (s * codebook[idx[p]][c] - z[n, c, p])^2 with s = row_scale[idx[p]] or 1, float64 inside; counts: int32 [n_e], how often each
+    code occurs.  An index outside [0, n_e) is not counted and gives a NaN mean -- nothing is synchronised to raise."""
+    _need_gpu(z_nchw, idx, codebook, row_scale)
+    assert z_nchw.dim() == 4 and z_nchw.dtype == torch.float32 and z_nchw.numel() > 0, (z_nchw.shape, z_nchw.dtype)
+    assert codebook.dim() == 2 and codebook.dtype == torch.float32 and codebook.shape[1] == z_nchw.shape[1], (codebook.shape, z_nchw.shape)
+    z, codebook = z_nchw.contiguous(), codebook.contiguous()
+    n, c = z.shape[:2]
+    hw = z.shape[2] * z.shape[3]
+    n_e = codebook.shape[0]
+    idx = idx.reshape(-1).to(torch.int64).contiguous()
+    assert idx.numel() == n * hw, (idx.shape, z.shape)
+    if row_scale is not None:
+        assert row_scale.dtype == torch.float32 and row_scale.shape == (n_e,) and row_scale.is_contiguous(), (row_scale.shape, n_e)
+    L = _lib.load()
+    mean_sq = torch.empty((), dtype=torch.float32, device=z.device)
+    counts = torch.empty(n_e, dtype=torch.int32, device=z.device)
+    ws = torch.empty(int(L.ccvs_vq_stats_workspace_bytes(n, c, hw)), dtype=torch.uint8, device=z.device)
+    _lib.check(L.ccvs_vq_stats(_p(z), _p(idx), _p(codebook), _p(row_scale), _p(mean_sq), _p(counts), _p(ws), n, c, hw, n_e, _stream()),
+               "ccvs_vq_stats")
+    return mean_sq, counts
+
+
+def code_perplexity(counts, total):
+    """exp(-sum_j p_j log(p_j + 1e-10)) with p_j = counts[j] / total (quantize.py:67-68) of an int32 [n_e] device histogram, float64
+    inside, as a 0-dim fp32 tensor on the device (`ccvs_code_perplexity`; nothing is synchronised)."""
+    _need_gpu(counts)
+    assert counts.dim() == 1 and counts.dtype == torch.int32 and counts.numel() > 0 and int(total) > 0, (counts.shape, counts.dtype, total)
+    counts = counts.contiguous()
+    out = torch.empty((), dtype=torch.float32, device=counts.device)
+    _lib.check(_lib.load().ccvs_code_perplexity(_p(counts), counts.numel(), int(total), _p(out), _stream()), "ccvs_code_perplexity")
+    return out
+
+
 def ssim_planes(x, y, data_range=2.0):
     """skimage 0.17.2 `structural_similarity` (defaults) of every 2-D plane of [..., H, W] fp32 tensors: [...] fp64
     (tools/pytorch_metrics/metrics.py:15-22; data_range 2 = what skimage takes for float planes when none is given)."""

@@ -473,6 +473,10 @@ int ccvs_ssim(const float* x, const float* y, double* out, void* workspace, int6
  * False) of [planes, H, W] fp32 planes, in torch's own formulation (source index, blend order). */
 int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, int32_t W, int32_t OH, int32_t OW, void* stream);
 
+/* The frame autoencoder's validation reductions (ccvs_l1_mean, ccvs_vq_stats, ccvs_code_perplexity and their workspace-size calls),
+ * additive to ABI version 6, are declared in their own header: including this one declares them too. */
+#include "ccvs_hip_eval.h"
+
 #ifdef __cplusplus
 }
 #endif
