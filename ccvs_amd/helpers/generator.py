@@ -10,7 +10,7 @@ Differences by design:
   * one process per GPU shards the generation batch along B (`Engine.shard_batch`) and the
     decoded clips of all ranks are all-gathered once at the end (`Engine.all_gather_clips`);
   * with no dataset on disk the input is the seeded synthetic tensor BASELINE.md specifies
-    (`vid = rand(B,T,3,H,W)*2-1`).
+    (`vid = rand(B,T,3,H,W)*2-1`); with `--dataroot` a folder of frames, the folder's clips (`ccvs_amd/data`).
 Deblurring (`--x_deblurring`): the blurred clip's codes are the transformer's ancillary stream and its skip features the decoder's
 (`condition`, `blur`).  Layout conditioning is a "next" row and raises.
 """
@@ -86,7 +86,17 @@ class Generator:
         return {"vid": torch.stack(frames)}
 
     def get_data_info(self, phase, data_type, fold=None, num_folds=None):
-        """Synthetic stand-in for the reference's dataset/loader factory (generator.py:232-246)."""
+        """The reference's dataset/loader factory (generator.py:232-246).  When `--dataroot` is a directory holding the frame folders
+        of `--dataset`, the batches are its clips: `ccvs_amd.data.FrameDataset` / `FrameLoader` (uint8 frames uploaded, crop +
+        Pillow-exact resample + normalise on the GPU); a directory that cannot be read that way raises.  With no such directory the
+        input is the seeded synthetic tensor, as before."""
+        from ccvs_amd.data.frame_dataset import FrameDataset, FrameLoader, frames_root
+        if frames_root(self.opt) is not None:
+            bs = (self.opt.batch_size_img if data_type == "img" else self.opt.batch_size_vid) * (self.opt.batch_size_valid_mult if phase == "valid" else 1)
+            lo, hi = self.engine.shard_batch(bs) if self.engine is not None else (0, bs)
+            loader = FrameLoader(FrameDataset(self.opt, phase=phase, load_vid=data_type == "vid"), bs, lo, hi, cycle=self.opt.iter_function == "cycle")
+            return {"dataloader": loader, "datasampler": None, "epoch": 0, "phase": phase, "data_type": data_type,
+                    "batch_size_per_gpu": hi - lo, "loader_iter": iter(loader), "fold": fold, "num_folds": num_folds}
         bs = self.opt.batch_size_vid * self.opt.batch_size_valid_mult
         lo, hi = self.engine.shard_batch(bs) if self.engine is not None else (0, bs)
         per = hi - lo

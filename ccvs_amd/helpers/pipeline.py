@@ -492,6 +492,11 @@ class PipelinedRun:
             data = self.held.pop() if self.held else next(self.it, None)
             if data is None:
                 break
+            if data["vid"].is_cuda:
+                # a clip the iterator produced on this thread's stream while the run is under way (`ccvs_amd.data.FrameLoader`: its
+                # upload and input kernels are queued there): the encode stream follows that stream and holds the clip's memory
+                self.s_enc.wait_stream(torch.cuda.current_stream())
+                data["vid"].record_stream(self.s_enc)
             if group is None:
                 want = self.ramp[self.n_groups] if self.n_groups < len(self.ramp) else self.lanes
                 group = gen._token_group_size(data["vid"].shape[0], min(want, self.lanes))

@@ -22,6 +22,8 @@ EXPORTS = [
 ]
 # every symbol include/ccvs_hip_eval.h declares (the frame autoencoder's validation reductions; ccvs_hip.h includes that header)
 EVAL_EXPORTS = ["ccvs_l1_workspace_bytes", "ccvs_l1_mean", "ccvs_vq_stats_workspace_bytes", "ccvs_vq_stats", "ccvs_code_perplexity"]
+# every symbol include/ccvs_hip_input.h declares (the input stage: uint8 frames -> the fp32 clip; ccvs_hip.h includes that header too)
+INPUT_EXPORTS = ["ccvs_ingest_u8"]
 
 
 class ConvDesc(C.Structure):
@@ -155,6 +157,7 @@ def load():
         "ccvs_l1_mean": [vp, vp, vp, vp, i64, vp],
         "ccvs_vq_stats": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "ccvs_code_perplexity": [vp, i32, i64, vp, vp],
+        "ccvs_ingest_u8": [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i64, i64, vp, vp],
     }
     for name, argtypes in sigs.items():
         fn = getattr(lib, name)

@@ -1035,3 +1035,103 @@ def pack_u8(vid, lo=-1.0, hi=1.0, out=None):
     L = _lib.load()
     _lib.check(L.ccvs_pack_u8(_p(vid), _p(out), n, h, w, lo, hi, _stream()), "ccvs_pack_u8")
     return out
+
+
+# ------------------------------------------------------------------ input stage (include/ccvs_hip_input.h)
+_RESAMPLE_TABLES = {}
+_NORM_TABLES = {}
+
+
+def resample_tables(in_size, out_size, device=None):
+    """The tables of one axis of Pillow's 8-bit bilinear resampler (`ImagingResample`: `precompute_coeffs` + `normalize_coeffs_8bpc`)
+    for `in_size` -> `out_size` samples, built on the host in float64: (coef int32 [out, ksize], bounds int32 [out, 2]).  bounds[o] =
+    (first tap, number of taps); coef[o][i] = int(w_i * 2^22 + 0.5), w the triangle weights max(0, 1 - |(i + first - center + 0.5) /
+    filterscale|) divided by their sum (added in tap order), zero past the last tap.  ksize = 2 * ceil(max(in / out, 1)) + 1.
+    Cached per (in, out, device); `device` None: the CPU -- no GPU is needed to build or to check them."""
+    in_size, out_size = int(in_size), int(out_size)
+    assert in_size > 0 and out_size > 0, (in_size, out_size)
+    device = torch.device("cpu" if device is None else device)
+    key = (in_size, out_size, str(device))
+    if key in _RESAMPLE_TABLES:
+        return _RESAMPLE_TABLES[key]
+    f64 = torch.float64
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (torch.arange(out_size, dtype=f64) + 0.5) * scale
+    xmin = torch.trunc(center - support + 0.5).clamp_(min=0)
+    xmax = torch.trunc(center + support + 0.5).clamp_(max=in_size) - xmin
+    ss = 1.0 / filterscale
+    w = torch.zeros(out_size, ksize, dtype=f64)
+    ww = torch.zeros(out_size, dtype=f64)
+    for x in range(ksize):
+        v = (1.0 - ((x + xmin - center + 0.5) * ss).abs()).clamp_(min=0)
+        v = torch.where(x < xmax, v, torch.zeros_like(v))
+        w[:, x] = v
+        ww += v
+    w = torch.where((ww != 0)[:, None], w / ww[:, None], w)
+    coef = torch.trunc(w * float(1 << 22) + 0.5).to(torch.int32)
+    bounds = torch.stack([xmin, xmax], dim=1).to(torch.int32)
+    _RESAMPLE_TABLES[key] = (coef.contiguous().to(device), bounds.contiguous().to(device))
+    return _RESAMPLE_TABLES[key]
+
+
+def norm_table(mean, std, device):
+    """float32 [3, 256] on `device`: ToTensor + Normalize of every uint8 value per channel, ((v / 255) - mean[c]) / std[c], computed
+    by the framework on the HOST (where the reference's transforms run: a true fp32 division by 255, then tensor - tensor and tensor /
+    tensor) and uploaded once per (mean, std, device)."""
+    mean, std = tuple(float(m) for m in mean), tuple(float(s) for s in std)
+    assert len(mean) == 3 and len(std) == 3, (mean, std)
+    key = (mean, std, str(torch.device(device)))
+    if key not in _NORM_TABLES:
+        v = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)[None].repeat(3, 1)
+        v = v.sub_(torch.tensor(mean, dtype=torch.float32)[:, None]).div_(torch.tensor(std, dtype=torch.float32)[:, None])
+        _NORM_TABLES[key] = v.contiguous().to(device)
+    return _NORM_TABLES[key]
+
+
+def ingest_u8(frames, box=None, size=None, out=None, mean=None, std=None, as_u8=False):
+    """One crop + resample stage of the input chain (`ccvs_ingest_u8`): uint8 frames [N, Hs, Ws, 3] (or [Hs, Ws, 3]) on the device, any
+    frame stride, `box` = (top, left, h, w) inside the frame (None: all of it), `size` = (Ho, Wo) (None: the box's size).  The
+    resample is `PIL.Image.resize((Wo, Ho), BILINEAR)` of the cropped frame, bit for bit; an axis whose size does not change is not
+    resampled.
+      as_u8=True   -> uint8 [N, Ho, Wo, 3] (`out`: optional contiguous tensor of that shape), the input of a further stage;
+      as_u8=False  -> fp32 [N, 3, Ho, Wo] = ((v / 255) - mean) / std per channel (defaults 0.5 / 0.5: ToTensor + Normalize).  `out`:
+                      optional fp32 tensor of that shape with dense rows and any frame / channel strides, e.g. `clip[b, t0:t1]` of a
+                      [B, T, 3, H, W] clip -- it is written in place and returned.
+    Runs on the current stream; nothing is synchronised."""
+    _need_gpu(frames, out)
+    assert frames.dtype == torch.uint8 and frames.dim() in (3, 4) and frames.shape[-1] == 3, (frames.dtype, frames.shape)
+    if frames.dim() == 3:
+        frames = frames[None]
+    n, hs, ws = frames.shape[:3]
+    if frames.stride()[1:] != (3 * ws, 3, 1) or (n > 1 and frames.stride(0) < hs * ws * 3):
+        frames = frames.contiguous()
+    top, left, hc, wc = (0, 0, hs, ws) if box is None else (int(v) for v in box)
+    ho, wo = (hc, wc) if size is None else (int(size[0]), int(size[1]))
+    if not (0 <= top and 0 <= left and hc > 0 and wc > 0 and top + hc <= hs and left + wc <= ws):
+        raise ValueError(f"ingest_u8: crop box {(top, left, hc, wc)} leaves the {hs} x {ws} frame")
+    dev = frames.device
+    hcoef, hbounds = resample_tables(wc, wo, dev) if wo != wc else (None, None)
+    vcoef, vbounds = resample_tables(hc, ho, dev) if ho != hc else (None, None)
+    lut = None
+    if as_u8:
+        assert mean is None and std is None, "as_u8: the uint8 form is not normalised"
+        if out is None:
+            out = torch.empty(n, ho, wo, 3, dtype=torch.uint8, device=dev)
+        assert out.dtype == torch.uint8 and out.shape == (n, ho, wo, 3) and out.is_contiguous(), (out.dtype, out.shape, out.stride())
+        s_n = s_c = 0
+    else:
+        lut = norm_table((0.5, 0.5, 0.5) if mean is None else mean, (0.5, 0.5, 0.5) if std is None else std, dev)
+        if out is None:
+            out = torch.empty(n, 3, ho, wo, dtype=torch.float32, device=dev)
+        assert out.dtype == torch.float32 and out.shape == (n, 3, ho, wo) and _rows_dense(out), (out.dtype, out.shape, out.stride())
+        s_n, s_c = out.stride(0), out.stride(1)
+        assert s_c >= ho * wo and (n == 1 or s_n >= 2 * s_c + ho * wo), out.stride()
+    _lib.check(_lib.load().ccvs_ingest_u8(_p(frames), frames.stride(0) if n > 1 else hs * ws * 3, n, hs, ws, top, left, hc, wc,
+                                          _p(hcoef), _p(hbounds), hcoef.shape[1] if hcoef is not None else 0,
+                                          _p(vcoef), _p(vbounds), vcoef.shape[1] if vcoef is not None else 0, ho, wo,
+                                          _p(out) if as_u8 else None, None if as_u8 else _p(out), s_n, s_c, _p(lut), _stream()),
+               "ccvs_ingest_u8")
+    return out

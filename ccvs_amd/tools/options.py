@@ -31,9 +31,9 @@ def _flag(parser, name, default=False, help=None):
 # dataset presets applied after a first parse (tools/options.py:396-450)
 _PRESETS = {
     "bairhd": dict(dataroot="datasets/bairhd", true_ratio=1, aspect_ratio=1, true_dim=256, categories=None, fps=4),
-    "kinetics600": dict(dataroot="datasets/kinetics", true_ratio=1, aspect_ratio=1, true_dim=256, imagenet_norm=True),
+    "kinetics600": dict(dataroot="datasets/kinetics", resize_center_crop_img=256, true_ratio=1, aspect_ratio=1, true_dim=256, imagenet_norm=True),
     "drums": dict(dataroot="datasets/drums", true_ratio=1, aspect_ratio=1, true_dim=96, categories=None, fps=30),
-    "ucf101": dict(dataroot="datasets/ucf101", true_ratio=1, aspect_ratio=1, true_dim=256, categories=None, fps=4),
+    "ucf101": dict(dataroot="datasets/ucf101", true_ratio=1, aspect_ratio=1, true_dim=256, categories=None, fps=4, resize_center_crop_img=256),
 }
 
 
@@ -67,6 +67,16 @@ class Options:
         for f in ("rec_only", "step_by_step", "gen_from_img", "keep_state", "custom_state", "layout", "include_id"):
             _flag(p, "--" + f)
         p.add_argument("--down_size", type=int, nargs="+", default=None)
+        # the per-frame transform chain of the frame-folder datasets (tools/options.py:91-108, read by data/base_dataset.py:120-199;
+        # here by ccvs_amd/data/frame_dataset.py)
+        _flag(p, "--shuffle_valid")
+        p.add_argument("--resize_img", type=int, nargs="+", default=None)
+        p.add_argument("--resize_center_crop_img", type=int, default=None)
+        p.add_argument("--fixed_crop", type=int, nargs="+", default=None)
+        _flag(p, "--centered_crop")
+        p.add_argument("--fixed_top_centered_zoom", type=float, default=None)
+        p.add_argument("--one_every_n", type=int, default=1)
+        _flag(p, "--load_state")   # (the annotated-frames dataset: accepted so that the data path can refuse it by name)
         # (ccvs_amd) the teacher-forced "rec" decode of the real codes, which the reference always runs unless gen_from_img
         # (helpers/generator.py:172-189); on by default like the reference, switchable because it is not part of the
         # synthesized-frames metric
@@ -193,8 +203,11 @@ class Options:
         base_opt.log_path = os.path.join(base_opt.save_path, "logs", signature)
         base_opt.result_path = os.path.join(base_opt.save_path, "results", signature)
         assert (base_opt.max_dim & (base_opt.max_dim - 1)) == 0, f"Max dim {base_opt.max_dim} must be power of two."
-        base_opt.width_size = int(base_opt.dim * base_opt.aspect_ratio)
-        base_opt.height_size = int(base_opt.width_size / base_opt.aspect_ratio)
+        if base_opt.fixed_crop is None:
+            base_opt.width_size = int(base_opt.dim * base_opt.aspect_ratio)
+            base_opt.height_size = int(base_opt.width_size / base_opt.aspect_ratio)
+        else:
+            base_opt.height_size, base_opt.width_size = base_opt.fixed_crop
         base_opt.signature = signature
 
     def parse(self, load_qvid_generator=False, load_transformer=False, load_extra_base=False, load_state_estimator=False,

@@ -476,6 +476,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 /* The frame autoencoder's validation reductions (ccvs_l1_mean, ccvs_vq_stats, ccvs_code_perplexity and their workspace-size calls),
  * additive to ABI version 6, are declared in their own header: including this one declares them too. */
 #include "ccvs_hip_eval.h"
+/* The input stage (uint8 frames -> crop, Pillow-exact bilinear resample, normalise -> the fp32 clip), additive to ABI version 6, likewise. */
+#include "ccvs_hip_input.h"
 
 #ifdef __cplusplus
 }
