@@ -163,6 +163,7 @@ struct Gemm16 {
     int kz;            // K slices across workgroups (gridDim.z); > 1 only with a workspace
     float* ws_slabs;   // [tile][kz][64 lanes][4] partial accumulators
     int* ws_count;     // [tile] arrival counters, zero between launches
+    int wt;            // 1: w is in the tiled layout (below: WT) -- the decode forms only
 };
 
 #define GEMM_U 4  // one-block form: K steps (of 16) whose loads are issued together (4 float4 of W + 4 of x per lane: the 48-VGPR budget)
@@ -236,15 +237,21 @@ __device__ __forceinline__ float gemm_epilogue(float v, bool ln, float rstd, flo
 // PT: `Gemm16` (the kernel's own argument block) or `__attribute__((address_space(4))) Gemm16` (an entry of the persistent step's phase
 // table in constant memory: every `p.field` is then a scalar load at its point of use -- the epilogue's operands are not held
 // in registers across the K loop -- and the pointers read from it are generic, hence GP() = the cast through the global address space).
-template <int RB, int CB, int U, bool COH, typename PT>
+// WT: W in the TILED layout (ccvs_gpt_decode.w_tiled; include/ccvs_hip_gemm.h).  Row-major, the 16 lanes of a quarter-wave read 16 bytes each
+// from 16 different rows: one 1-KB wave load touches 16 128-byte lines and uses half of each (the other half is the next K batch's).
+// Tiled, the 1 KB that a wave loads for column tile ct and K batch kb IS one block of memory, at float offset (ct * K / 16 + kb) * 256,
+// lane l = li + 16 g owning floats 4 l .. 4 l + 3 = W[16 ct + li][16 kb + 4 g ..]: 8 whole, aligned lines per wave load, the next batch
+// 1 KB on.  The same floats reach the same lanes: registers, MFMA order, K slices and reduction are untouched, so the bits are too.
+// N is padded to whole column tiles by the packer (last row repeated), so a ragged tile needs no clamp; a column tile wholly outside reads the last one.
+template <int RB, int CB, int U, bool COH, bool WT, typename PT>
 __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const float* __restrict__ w_, long ldx_, int K_, int N_, int M_, int ks_,
                                             int kz_, const PT& p, int bx_, int by_, int bz_, float* __restrict__ red, float* __restrict__ stat,
                                             float* __restrict__ fin) {
 #define GP(ptr) gp_<COH>(ptr)
     constexpr int NB = RB * CB;
     constexpr int XAUX = COH ? 16 : 0;   // sc1 on the activation loads
-    const int tid = thread_id<COH>(), lane = tid & 63, wave = tid >> 6;
-    const int li = lane & 15, g = lane >> 4;
+    int tid = thread_id<COH>(), lane = tid & 63, wave = tid >> 6;
+    int li = lane & 15, g = lane >> 4;
     const int m0 = by_ * 16 * RB, ncol0 = bx_ * 16 * CB;
     const int kper = K_ / (ks_ * kz_);
     const int kbase = bz_ * (K_ / kz_);
@@ -256,15 +263,21 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
     unsigned wofs[CB], xofs[RB];
 #pragma unroll
     for (int cb = 0; cb < CB; ++cb) {   // tails: computed on a valid row, dropped at the store
-        const int nrow = min(ncol0 + 16 * cb + li, N_ - 1);
-        wofs[cb] = ((unsigned)nrow * (unsigned)K_ + koff) * 4u;
+        if constexpr (WT) {   // (every slice boundary is a multiple of 16: gemm16_plan)
+            const int ct = min(bx_ * CB + cb, ((N_ + 15) >> 4) - 1);
+            wofs[cb] = (((unsigned)ct * (unsigned)(K_ >> 4) + ((koff - 4 * g) >> 4)) * 256u + 4u * lane) * 4u;
+        } else {
+            const int nrow = min(ncol0 + 16 * cb + li, N_ - 1);
+            wofs[cb] = ((unsigned)nrow * (unsigned)K_ + koff) * 4u;
+        }
     }
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) {
         const int mrow = min(m0 + 16 * rb + li, M_ - 1);
         xofs[rb] = ((unsigned)mrow * (unsigned)ldx_ + koff) * 4u;
     }
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w_), 0, N_ * K_ * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w_), 0, (WT ? (N_ + 15) & ~15 : N_) * K_ * 4, 0x00020000);
+    constexpr int WSTEP = WT ? 1024 : 64;   // bytes from one 16-deep K batch of a lane's W to the next
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x_), 0, (int)(M_ * ldx_ * 4), 0x00020000);
     f32x4 acc[RB][CB];
     float sx[RB], sxx[RB];
@@ -283,7 +296,7 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
 #pragma unroll
             for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
-                for (int u = 0; u < U; ++u) wv[cb][u] = buf_load4(wr, wofs[cb], k0 * 4 + 64 * u);
+                for (int u = 0; u < U; ++u) wv[cb][u] = buf_load4(wr, wofs[cb], k0 * (WSTEP / 16) + WSTEP * u);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -304,7 +317,7 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
         for (; k0 < kper; k0 += 16) {  // remainder (small K only)
             f32x4 w1[CB], x1[RB];
 #pragma unroll
-            for (int cb = 0; cb < CB; ++cb) w1[cb] = buf_load4(wr, wofs[cb], k0 * 4);
+            for (int cb = 0; cb < CB; ++cb) w1[cb] = buf_load4(wr, wofs[cb], k0 * (WSTEP / 16));
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) x1[rb] = buf_load4<XAUX>(xr, xofs[rb], k0 * 4);
 #pragma unroll
@@ -316,6 +329,15 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
                 if (p.ln_s) ln_accum(x1[rb], sx[rb], sxx[rb]);
             }
         }
+    }
+    if constexpr (WT) {
+        // the lane maps of the reduction and the epilogue, derived again from a thread index the optimiser cannot see through: ONE register
+        // live across the K loop instead of the maps themselves (with them, the tiled 2 x 2 form took 36 + 16 registers, not 32 + 16)
+        asm volatile("" : "+v"(tid));
+        // (the launch form knows threadIdx.x's range and runs the finishing loop below at most once: say so again.  The persistent form never
+        // knew -- thread_id<true> -- and with the loop unrolled its phase loop spills 52-84 bytes)
+        if constexpr (!COH) __builtin_assume(tid >= 0 && tid < 64 * GEMM_WAVES);
+        lane = tid & 63; wave = tid >> 6; li = lane & 15; g = lane >> 4;
     }
     if (p.ln_s) {  // lanes li, li+16, li+32, li+48 hold the four k-groups of row li
 #pragma unroll
@@ -410,13 +432,13 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
 #undef GP
 }
 
-template <int RB, int CB, int U>
+template <int RB, int CB, int U, bool WT>
 __global__ __launch_bounds__(64 * GEMM_WAVES) void gemm16_kernel(const float* __restrict__ x_, const float* __restrict__ w_, long ldx_, int K_, int N_,
                                                                 int M_, int ks_, int kz_, Gemm16 p) {
     __shared__ __attribute__((aligned(16))) float red[GEMM16_RED_WORDS(RB * CB)];
     __shared__ float stat[GEMM16_STAT_WORDS(RB)];
     __shared__ float fin[GEMM16_FIN_WORDS(RB)];
-    gemm16_tile<RB, CB, U, false>(x_, w_, ldx_, K_, N_, M_, ks_, kz_, p, blockIdx.x, blockIdx.y, blockIdx.z, red, stat, fin);
+    gemm16_tile<RB, CB, U, false, WT>(x_, w_, ldx_, K_, N_, M_, ks_, kz_, p, blockIdx.x, blockIdx.y, blockIdx.z, red, stat, fin);
 }
 
 // Prefill form (M > GEMM_DECODE_MAX_M rows): one workgroup computes RB row blocks of 16 against the SAME 16 output columns,
@@ -726,6 +748,12 @@ static GemmForm gemm16_plan(Gemm16& g) {
 // depend on M) or past the workspace's end
 static bool gemm_ws_holds(const Gemm16& g) { return g.kz == 1 || cdiv(g.N, 16) * cdiv(g.M, 16) <= GEMM_WS_TILES; }
 
+// Tiled weights (g.wt; after gemm16_plan): a wave's K slice starts and ends on a 16-deep block -- the plan's slices always do -- and the
+// padded matrix stays below 2^31 bytes (32-bit buffer offsets).  Checked by both forms of the step and by ccvs_gemm_tiled.
+static bool gemm_wt_holds(const Gemm16& g) {
+    return !g.wt || ((long)cdiv(g.N, 16) * 16 * g.K * 4 < (1L << 31) && g.K % (g.ks * g.kz) == 0 && (g.K / (g.ks * g.kz)) % 16 == 0);
+}
+
 static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
     if (!(g.x && g.w && g.y)) { ccvs_set_error("%s: null pointer", name); return CCVS_ERR_ARG; }
     if (!(g.M > 0 && g.N > 0 && g.K > 0)) { ccvs_set_error("%s: empty tensor", name); return CCVS_ERR_ARG; }
@@ -738,6 +766,11 @@ static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
         ccvs_set_error("%s: operand beyond 2^31 bytes (32-bit buffer offsets)", name);
         return CCVS_ERR_ARG;
     }
+    if (g.wt && !decode_form) { ccvs_set_error("%s: tiled weights are read by the decode forms only (single position, M <= %d)", name, GEMM_DECODE_MAX_M); return CCVS_ERR_ARG; }
+    if (!gemm_wt_holds(g)) {
+        ccvs_set_error("%s: tiled weights need K slices of whole 16-deep batches and fewer than 2^31 bytes", name);
+        return CCVS_ERR_ARG;
+    }
     if (!decode_form && g.grp_rows > 0) { ccvs_set_error("%s: row groups need M <= %d", name, GEMM_DECODE_MAX_M); return CCVS_ERR_ARG; }
     if (form == GEMM_FORM_SEQ) {
         const int rt = cdiv(g.M, GS_BM), ct = cdiv(g.N, GS_BM);
@@ -745,10 +778,11 @@ static int launch_gemm16(Gemm16& g, hipStream_t st, const char* name) {
     } else if (form == GEMM_FORM_RB)
         hipLaunchKernelGGL((gemm16_rb_kernel<4>), dim3(cdiv(g.N, 16), cdiv(g.M, 64), 1), dim3(512), 0, st, g);
     else {
-#define GEMM16_LAUNCH(RBv, CBv, Uv)                                                                                                         \
-    hipLaunchKernelGGL((gemm16_kernel<RBv, CBv, Uv>), dim3(cdiv(g.N, 16 * CBv), cdiv(g.M, 16 * RBv), g.kz), dim3(64 * GEMM_WAVES), 0, st, g.x, \
+#define GEMM16_LAUNCH(RBv, CBv, Uv, WTv)                                                                                                         \
+    hipLaunchKernelGGL((gemm16_kernel<RBv, CBv, Uv, WTv>), dim3(cdiv(g.N, 16 * CBv), cdiv(g.M, 16 * RBv), g.kz), dim3(64 * GEMM_WAVES), 0, st, g.x, \
                        g.w, g.ldx, g.K, g.N, g.M, g.ks, g.kz, g)
-        if (form == GEMM_FORM_TILE2) GEMM16_LAUNCH(2, 2, 1); else GEMM16_LAUNCH(1, 1, GEMM_U);
+        if (form == GEMM_FORM_TILE2) { if (g.wt) GEMM16_LAUNCH(2, 2, 1, true); else GEMM16_LAUNCH(2, 2, 1, false); }
+        else { if (g.wt) GEMM16_LAUNCH(1, 1, GEMM_U, true); else GEMM16_LAUNCH(1, 1, GEMM_U, false); }
 #undef GEMM16_LAUNCH
     }
     CCVS_CHECK_LAUNCH(name);
@@ -796,6 +830,31 @@ extern "C" int ccvs_gemm_ln_qkv(const float* x, int64_t ldx, const float* w_gamm
     g.kcache = kcache; g.vcache = vcache; g.C = C; g.H = H; g.D = C / H; g.Tq = Tq; g.Tmax = Tmax; g.pos0 = pos0; g.pos_dev = pos_dev;
     g.seq = Tq > 1 ? 1 : 0;
     return launch_gemm16(g, (hipStream_t)stream, "ccvs_gemm_ln_qkv");
+}
+
+// the most rows the forms that read tiled weights take: a step of more rows runs the row-blocked form, which reads row-major weights only
+extern "C" int32_t ccvs_gemm_tiled_max_rows(void) { return GEMM_DECODE_MAX_M; }
+
+// One decode GEMM (single position, M <= GEMM_DECODE_MAX_M) against TILED weights: the three calls above in one signature, as the
+// decode step issues them (w_rowsum: the folded LayerNorm; kcache / vcache: the QKV scatter with Tq = 1, N = 3 K, y = q).
+extern "C" int ccvs_gemm_tiled(const float* x, int64_t ldx, const float* w_tiled, const float* bias, const float* res, const float* w_rowsum,
+                               float eps, float* y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t epilogue, float* kcache, float* vcache,
+                               int32_t H, int32_t pos0, const int32_t* pos_dev, int32_t Tmax, void* workspace, void* stream) {
+    CCVS_REQUIRE((epilogue & ~0xff) == 0 && M <= GEMM_DECODE_MAX_M, "ccvs_gemm_tiled: a single-position call of at most %d rows", GEMM_DECODE_MAX_M);
+    CCVS_REQUIRE(!w_rowsum || epilogue == 0 || epilogue == 1, "ccvs_gemm_tiled: bad epilogue");
+    CCVS_REQUIRE((kcache != nullptr) == (vcache != nullptr), "ccvs_gemm_tiled: one cache without the other");
+    Gemm16 g = {};
+    g.x = x; g.ldx = ldx; g.w = w_tiled; g.bias = bias; g.res = res; g.y = y; g.ldy = ldy; g.M = M; g.N = N; g.K = K; g.epi = epilogue; g.wt = 1;
+    g.ln_s = w_rowsum; g.ln_eps = eps;
+    if (kcache) {
+        CCVS_REQUIRE(w_rowsum && epilogue == 0 && N == 3 * K && ldy == K && H > 0 && K % H == 0 && pos0 >= 0 && pos0 < Tmax, "ccvs_gemm_tiled: bad QKV shape / position");
+        g.kcache = kcache; g.vcache = vcache; g.C = K; g.H = H; g.D = K / H; g.Tq = 1; g.Tmax = Tmax; g.pos0 = pos0; g.pos_dev = pos_dev;
+    }
+    if (workspace) {
+        g.ws_slabs = (float*)workspace;
+        g.ws_count = (int*)((char*)workspace + GEMM_WS_SLAB_BYTES);
+    }
+    return launch_gemm16(g, (hipStream_t)stream, "ccvs_gemm_tiled");
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1581,7 +1640,7 @@ __device__ __forceinline__ void step_barrier(StepBar* bar, unsigned target, int 
     __syncthreads();
 }
 
-template <int RB, int CB, int U>
+template <int RB, int CB, int U, bool WT>
 __device__ __forceinline__ void step_gemm(const __attribute__((address_space(4))) Gemm16& g, float* smem) {
     float* red = smem;
     float* stat = red + GEMM16_RED_WORDS(RB * CB);
@@ -1596,7 +1655,7 @@ __device__ __forceinline__ void step_gemm(const __attribute__((address_space(4))
     // of 8, so with workgroups dealt to the XCDs round-robin they meet in one L2, as in the launch chain
     for (int vb = blockIdx.x; vb < total; vb += gridDim.x) {
         const int bx = vb % gx, r = vb / gx;
-        gemm16_tile<RB, CB, U, true>(x, w, ldx, K, N, M, ks, kz, g, bx, r % gy, r / gy, red, stat, fin);
+        gemm16_tile<RB, CB, U, true, WT>(x, w, ldx, K, N, M, ks, kz, g, bx, r % gy, r / gy, red, stat, fin);
         __syncthreads();   // the tile's LDS is the next tile's
     }
 }
@@ -1620,7 +1679,7 @@ __device__ __forceinline__ T* as_global(T* p) {
 // hipcc allocates 73 + 16 for this body although no phase needs more than the launch chain's 48: with 256 threads per workgroup it
 // sees no reason to be frugal.  64 fit beside two convolution waves of up to 216 registers per SIMD (the 3 x 3 forms that carry
 // the decoder's time: 208 / 214), not beside the 1 x 1 forms' 225 -- there the step's workgroup waits for one to retire, once per step.
-template <int D, bool T2>
+template <int D, bool T2, bool WT>   // WT: every weight matrix of the phase table is tiled (ccvs_gpt_decode.w_tiled)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void gpt_step_kernel(const StepArgs* __restrict__ ap_) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int RB = T2 ? 2 : 1, CB = T2 ? 2 : 1, U = T2 ? 1 : GEMM_U;
@@ -1667,7 +1726,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                 __syncthreads();
             }
         } else {
-            step_gemm<RB, CB, U>(P->g, smem);
+            step_gemm<RB, CB, U, WT>(P->g, smem);
         }
         target += G; step_barrier(bar, target, ph + 1);
     }
@@ -1739,7 +1798,7 @@ static Advance step_advance(const ccvs_gpt_decode* d, int grp_rows) {
 static Gemm16 step_head_gemm(const ccvs_gpt_decode* d) {
     Gemm16 g = {};
     g.x = d->x; g.ldx = d->C; g.w = d->head_w; g.bias = d->head_b; g.y = d->logits; g.ldy = d->V; g.M = d->B; g.N = d->V; g.K = d->C;
-    g.ln_s = d->head_s; g.ln_eps = d->ln_eps;
+    g.ln_s = d->head_s; g.ln_eps = d->ln_eps; g.wt = d->w_tiled ? 1 : 0;
     return g;
 }
 
@@ -1757,7 +1816,7 @@ static bool step_tile2(const ccvs_gpt_decode* d) {
 // other than CCVS_OK ends the walk and is returned.  `who` names the caller in the layers' null-pointer check.
 template <typename Visit>
 static int step_phases(const ccvs_gpt_decode* d, const char* who, Visit visit) {
-    const int D = d->C / d->H, grp_rows = step_grp_rows(d);
+    const int D = d->C / d->H, grp_rows = step_grp_rows(d), wt = d->w_tiled ? 1 : 0;
     float* ws_slabs = (float*)d->workspace;
     int* ws_count = d->workspace ? (int*)((char*)d->workspace + GEMM_WS_SLAB_BYTES) : nullptr;
     int rc;
@@ -1769,6 +1828,7 @@ static int step_phases(const ccvs_gpt_decode* d, const char* who, Visit visit) {
         g.x = d->x; g.ldx = d->C; g.w = L.qkv_w; g.bias = L.qkv_b; g.y = d->q; g.ldy = d->C; g.M = d->B; g.N = 3 * d->C; g.K = d->C;
         g.ln_s = L.qkv_s; g.ln_eps = d->ln_eps;
         g.kcache = L.kcache; g.vcache = L.vcache; g.C = d->C; g.H = d->H; g.D = D; g.Tq = 1; g.Tmax = d->Tmax; g.pos0 = 0; g.pos_dev = d->len; g.grp_rows = grp_rows;
+        g.wt = wt;
         if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(qkv)")) != CCVS_OK) return rc;
         g = Gemm16{};  // attention over the cache
         g.x = d->q; g.ldx = d->C; g.y = d->att; g.kcache = L.kcache; g.vcache = L.vcache; g.H = d->H; g.M = d->B; g.Tmax = d->Tmax;
@@ -1777,14 +1837,17 @@ static int step_phases(const ccvs_gpt_decode* d, const char* who, Visit visit) {
         g = Gemm16{};  // proj + residual (in place on x)
         g.x = d->att; g.ldx = d->C; g.w = L.proj_w; g.bias = L.proj_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->C; g.epi = 2;
         g.ws_slabs = ws_slabs; g.ws_count = ws_count;
+        g.wt = wt;
         if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(proj)")) != CCVS_OK) return rc;
         g = Gemm16{};  // ln2 + fc + GELU
         g.x = d->x; g.ldx = d->C; g.w = L.fc_w; g.bias = L.fc_b; g.y = d->h; g.ldy = d->F; g.M = d->B; g.N = d->F; g.K = d->C; g.epi = 1;
         g.ln_s = L.fc_s; g.ln_eps = d->ln_eps;
+        g.wt = wt;
         if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(fc)")) != CCVS_OK) return rc;
         g = Gemm16{};  // fc2 + residual (in place on x)
         g.x = d->h; g.ldx = d->F; g.w = L.fc2_w; g.bias = L.fc2_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->F; g.epi = 2;
         g.ws_slabs = ws_slabs; g.ws_count = ws_count;
+        g.wt = wt;
         if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(fc2)")) != CCVS_OK) return rc;
     }
     Gemm16 g = step_head_gemm(d);
@@ -1817,7 +1880,7 @@ extern "C" int ccvs_gpt_decode_prepare(const ccvs_gpt_decode* d, void* stream) {
     const GemmForm tile = step_tile2(d) ? GEMM_FORM_TILE2 : GEMM_FORM_TILE1;
     int n = 0;
     rc = step_phases(d, "ccvs_gpt_decode_prepare", [&](int kind, Gemm16& g, const char* name) -> int {
-        if (n == n_ph || (kind == STEP_GEMM && (gemm16_plan(g) != tile || !gemm_ws_holds(g)))) { ccvs_set_error("ccvs_gpt_decode_prepare: %s does not fit the persistent step's table", name); return CCVS_ERR_ARG; }
+        if (n == n_ph || (kind == STEP_GEMM && (gemm16_plan(g) != tile || !gemm_ws_holds(g) || !gemm_wt_holds(g)))) { ccvs_set_error("ccvs_gpt_decode_prepare: %s does not fit the persistent step's table", name); return CCVS_ERR_ARG; }
         prog[n].kind = kind;
         prog[n++].g = g;
         return CCVS_OK;
@@ -1848,19 +1911,21 @@ static int launch_step_persistent(const ccvs_gpt_decode* d, int D, hipStream_t s
     if (w_att > words) words = w_att;
     if (w_pick > words) words = w_pick;
     const size_t smem = words * sizeof(float);
-#define STEP_LAUNCH(Dv, T2v)                                                                                                          \
+#define STEP_LAUNCH_(Dv, T2v, WTv)                                                                                                        \
     do {                                                                                                                              \
         static bool attr_set = false;                                                                                                 \
         if (!attr_set) {                                                                                                              \
-            (void)hipFuncSetAttribute((const void*)gpt_step_kernel<Dv, T2v>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+            (void)hipFuncSetAttribute((const void*)gpt_step_kernel<Dv, T2v, WTv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             attr_set = true;                                                                                                          \
         }                                                                                                                             \
-        hipLaunchKernelGGL((gpt_step_kernel<Dv, T2v>), dim3(n_cu), dim3(256), smem, st, a);                                           \
+        hipLaunchKernelGGL((gpt_step_kernel<Dv, T2v, WTv>), dim3(n_cu), dim3(256), smem, st, a);                                      \
     } while (0)
+#define STEP_LAUNCH(Dv, T2v) do { if (d->w_tiled) STEP_LAUNCH_(Dv, T2v, true); else STEP_LAUNCH_(Dv, T2v, false); } while (0)
     if (D == 64) { if (t2) STEP_LAUNCH(64, true); else STEP_LAUNCH(64, false); }
     else if (D == 32) { if (t2) STEP_LAUNCH(32, true); else STEP_LAUNCH(32, false); }
     else { if (t2) STEP_LAUNCH(16, true); else STEP_LAUNCH(16, false); }
 #undef STEP_LAUNCH
+#undef STEP_LAUNCH_
     CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(persistent)");
     return CCVS_OK;
 }

@@ -24,6 +24,8 @@ EXPORTS = [
 EVAL_EXPORTS = ["ccvs_l1_workspace_bytes", "ccvs_l1_mean", "ccvs_vq_stats_workspace_bytes", "ccvs_vq_stats", "ccvs_code_perplexity"]
 # every symbol include/ccvs_hip_input.h declares (the input stage: uint8 frames -> the fp32 clip; ccvs_hip.h includes that header too)
 INPUT_EXPORTS = ["ccvs_ingest_u8"]
+# every symbol include/ccvs_hip_gemm.h declares (the tiled weight layout of the decode GEMMs; included by ccvs_hip.h as well)
+GEMM_EXPORTS = ["ccvs_gemm_tiled", "ccvs_gemm_tiled_max_rows"]
 
 
 class ConvDesc(C.Structure):
@@ -69,7 +71,7 @@ class GptDecode(C.Structure):
         ("noise", C.c_void_p), ("rng", C.c_int32), ("top_k", C.c_int32), ("temperature", C.c_float),
         ("workspace", C.c_void_p), ("state", C.c_void_p), ("groups", C.c_int32),
         ("noise_stream", C.c_void_p),
-        ("persistent", C.c_int32), ("program", C.c_void_p),
+        ("persistent", C.c_int32), ("program", C.c_void_p), ("w_tiled", C.c_int32),
     ]
 
 
@@ -101,6 +103,8 @@ def load():
     lib.ccvs_l1_workspace_bytes.argtypes = [C.c_int64]
     lib.ccvs_vq_stats_workspace_bytes.restype = C.c_int64
     lib.ccvs_vq_stats_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    lib.ccvs_gemm_tiled_max_rows.restype = C.c_int32
+    lib.ccvs_gemm_tiled_max_rows.argtypes = []
     lib.ccvs_gpt_program_bytes.restype = C.c_int64
     lib.ccvs_gpt_program_bytes.argtypes = [C.c_int32]
     lib.ccvs_conv_fetch_bytes_per_lane.restype = C.c_int
@@ -130,6 +134,7 @@ def load():
         "ccvs_gemm_nt": [vp, i64, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, vp],
         "ccvs_gemm_ln": [vp, i64, vp, vp, vp, f32, vp, i64, i32, i32, i32, i32, vp],
         "ccvs_gemm_ln_qkv": [vp, i64, vp, vp, vp, f32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i32, vp],
+        "ccvs_gemm_tiled": [vp, i64, vp, vp, vp, vp, f32, vp, i64, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp],
         "ccvs_attention": [vp, i64, i64, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp],
         "ccvs_kv_append": [vp, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp],
         "ccvs_sample_topk": [vp, i64, vp, vp, i64, i32, i32, i32, f32, vp],

@@ -84,6 +84,17 @@ class Block(nn.Module):
             nn.Dropout(config.resid_pdrop),
         )
         self._folded = None
+        self._tiled = None
+
+    def tiled(self):
+        """(key, the block's four decode-step matrices in the tiled layout of the decode GEMM -- `ops.tile_weight`), cached like `folded()`."""
+        (qw, _, _), (fw, _, _) = self.folded()
+        src = (self.attn.proj.weight, self.mlp[3].weight)
+        key = (self._folded[0],) + tuple((t.data_ptr(), t._version) for t in src)
+        if self._tiled is None or self._tiled[0] != key:
+            self._tiled = (key, dict(qkv_w=ops.tile_weight(qw), proj_w=ops.tile_weight(src[0]), fc_w=ops.tile_weight(fw),
+                                     fc2_w=ops.tile_weight(src[1])))
+        return self._tiled
 
     def folded(self):
         """(ln1 folded into the stacked QKV weight, ln2 folded into mlp[0]) -- `ops.pack_ln_linear`."""
@@ -172,6 +183,10 @@ class GPT(nn.Module):
         # token loop in flight (`Generator.run_pipelined` with chains = 1).  CCVS_DECODE_PERSISTENT=1 turns it on.
         import os
         self.persistent_step = os.environ.get("CCVS_DECODE_PERSISTENT", "0") == "1"
+        # tiled_weights: the decode step streams its weight matrices from copies in the tiled layout of the decode GEMM (`ops.tile_weight`;
+        # include/ccvs_hip_gemm.h, ccvs_gemm_tiled): every wave load is 1 KB of whole 128-byte lines.  Same bits (tests/test_gemm_tiled_gpu.py);
+        # costs a second copy of the weights (prefill and the eager forward keep the row-major ones).  Steps of more than 256 rows keep the row-major weights.  CCVS_DECODE_TILED_W=0 / 1.
+        self.tiled_weights = os.environ.get("CCVS_DECODE_TILED_W", "1") == "1"
 
     @property
     def _graphs(self):
@@ -418,6 +433,14 @@ class GPT(nn.Module):
             hf = self._head_folded = (key, ops.pack_ln_linear(self.head.weight, None, self.ln_f.weight, self.ln_f.bias))
         return hf
 
+    def _head_tiled(self):
+        """The folded head weight in the tiled layout (`ops.tile_weight`), cached on the key of `_head_packed`."""
+        key, (hw, _, _) = self._head_packed()
+        ht = getattr(self, "_head_tiled_w", None)
+        if ht is None or ht[0] != key:
+            ht = self._head_tiled_w = (key, ops.tile_weight(hw))
+        return ht[1]
+
     def _head(self, x):
         return ops.gemm_ln(x, *self._head_packed()[1], eps=self.ln_f.eps)
 
@@ -512,9 +535,12 @@ class GPT(nn.Module):
         folded = [blk.folded() for blk in self.blocks]
         head_key, (hw, hb, hs) = self._head_packed()
         device_rng = sampler["sample"] and sampler["noise"] == "device"
+        # (a step of more rows than the weight-stream GEMM takes runs the row-blocked form, which reads the row-major weights)
+        tiled = self.tiled_weights and c["B"] <= ops.gemm_tiled_max_rows()
         host_stream = bool(sampler["sample"] and not device_rng and sampler.get("stream"))   # host noise read from a pre-drawn stream
         key = (tuple(blk._folded[0] for blk in self.blocks), head_key, sampler["sample"], sampler["top_k"],
-               sampler["temperature"], device_rng, host_stream, c["frame_pos0"], bool(self.persistent_step))
+               sampler["temperature"], device_rng, host_stream, c["frame_pos0"], bool(self.persistent_step),
+               tuple(blk.tiled()[0] for blk in self.blocks) if tiled else None)
         if c["desc"] is None or c["desc"][0] != key:
             layers = []
             for i, blk in enumerate(self.blocks):
@@ -529,7 +555,8 @@ class GPT(nn.Module):
                 x=c["x"], q=c["q"], att=c["att"], h=c["h"], logits=c["logits"],
                 noise=c["noise"] if (sampler["sample"] and not device_rng and not host_stream) else None, rng=device_rng,
                 noise_stream=c["noise_ptrs"] if host_stream else None,
-                top_k=sampler["top_k"], temperature=sampler["temperature"], state=c["state"], persistent=self.persistent_step)
+                top_k=sampler["top_k"], temperature=sampler["temperature"], state=c["state"], persistent=self.persistent_step,
+                tiled=([blk.tiled()[1] for blk in self.blocks], self._head_tiled()) if tiled else None)
             c["desc"] = (key, desc)
             c["graphs"] = {}   # captured graphs replay the OLD descriptor's pointers (packed weights are freed with it)
         return c["desc"][1]

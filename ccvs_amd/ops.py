@@ -735,6 +735,47 @@ def gemm_ln_qkv(x, wg, bb, s, kcache, vcache, b, tq, pos0, pos_dev=None, eps=1e-
     return q
 
 
+def tile_weight(w):
+    """W [N,K] -> the tiled layout of the decode GEMMs (include/ccvs_hip_gemm.h, ccvs_gemm_tiled), flat [ceil(N / 16) * 16 * K]: N padded to
+    whole column tiles by repeating the last row, then block (ct, kb) of 16 rows x 16 columns = 256 contiguous floats at
+    (ct * K / 16 + kb) * 256, float 4 * (li + 16 g) + j of a block = W[16 ct + li][16 kb + 4 g + j]."""
+    w = w.detach()
+    n, k = w.shape
+    assert w.dtype == torch.float32 and k % 16 == 0
+    npad = -(-n // 16) * 16
+    if npad != n:
+        w = torch.cat([w, w[-1:].expand(npad - n, k)], dim=0)
+    return w.reshape(npad // 16, 16, k // 16, 4, 4).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+
+
+def gemm_tiled_max_rows():
+    """The most rows of a GEMM -- hence of a decode step -- that reads tiled weights (`ccvs_gemm_tiled_max_rows`)."""
+    return int(_lib.load().ccvs_gemm_tiled_max_rows())
+
+
+def gemm_tiled(x, wt, n, bias=None, epilogue=EPI_NONE, residual=None, out=None, ln_s=None, eps=1e-5, kcache=None, vcache=None, pos0=0,
+               pos_dev=None):
+    """One decode GEMM on `wt` = tile_weight(W [n,K]) (`ccvs_gemm_tiled`): gemm_nt (ln_s None), gemm_ln (ln_s = the packed row sums,
+    bias = the packed bias) or gemm_ln_qkv with one position per row (kcache / vcache given: `out` is q).  Bit-identical to those."""
+    _need_gpu(x, wt, bias, residual, out, ln_s, kcache, vcache, pos_dev)
+    m, k = x.shape
+    assert x.stride(1) == 1 and wt.is_contiguous() and wt.numel() == -(-n // 16) * 16 * k
+    if out is None:
+        out = torch.empty(m, k if kcache is not None else n, dtype=torch.float32, device=x.device)
+    assert out.stride(1) == 1
+    if residual is not None:
+        assert residual.stride(1) == 1 and residual.stride(0) == out.stride(0)
+    h = tmax = 0
+    if kcache is not None:
+        _, h, tmax, d = kcache.shape
+        assert n == 3 * k and h * d == k and out.shape == (m, k) and out.is_contiguous() and kcache.shape[0] == m
+    ws = _gemm_workspace(x.device) if ln_s is None else None   # (as gemm_nt / gemm_ln: only the plain form splits K over workgroups)
+    L = _lib.load()
+    _lib.check(L.ccvs_gemm_tiled(_p(x), x.stride(0), _p(wt), _p(bias), _p(residual), _p(ln_s), eps, _p(out), out.stride(0), m, n, k, epilogue,
+                                 _p(kcache), _p(vcache), h, pos0, _p(pos_dev), tmax, _p(ws), _stream()), "ccvs_gemm_tiled")
+    return out
+
+
 def kv_append(k, v, kcache, vcache, pos0, pos_dev=None):
     """k, v [B,Tq,H*D] views (row stride shared) -> caches [B,H,Tmax,D] at pos0 (+ *pos_dev).."""
     b, tq, hd = k.shape
@@ -801,7 +842,10 @@ class GptDecodeStep:
     `launch()` enqueues one whole decode step on the current stream."""
 
     def __init__(self, layers, B, C, H, Tmax, ln_eps, tok_emb, pos_table, pos_off, head, tok, codes, widx, length,
-                 x, q, att, h, logits, noise, top_k, temperature, state, rng=False, groups=1, noise_stream=None, persistent=False):
+                 x, q, att, h, logits, noise, top_k, temperature, state, rng=False, groups=1, noise_stream=None, persistent=False,
+                 tiled=None):
+        """tiled: None, or ([{qkv_w, proj_w, fc_w, fc2_w} per layer], head_w) = `tile_weight` of the matrices in `layers` / `head`: the
+        step then reads those (`ccvs_gpt_decode.w_tiled`); the row-major ones still give the shapes."""
         hw, hb, hs = head
         keep = [tok_emb, pos_table, hw, hb, hs, tok, codes, widx, length, x, q, att, h, logits, noise, state, noise_stream]
         for t in keep:
@@ -821,6 +865,10 @@ class GptDecodeStep:
                 t = t.detach()
                 _need_gpu(t)
                 assert t.dtype == torch.float32 and t.is_contiguous(), name
+                if tiled is not None and name in tiled[0][i]:
+                    n_k, t = t.shape, tiled[0][i][name]
+                    _need_gpu(t)
+                    assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == -(-n_k[0] // 16) * 16 * n_k[1], name
                 keep.append(t)
                 setattr(arr[i], name, _p(t))
         F = layers[0]["fc_w"].shape[0]
@@ -832,6 +880,12 @@ class GptDecodeStep:
         d.layers = arr
         d.tok_emb, d.pos_table, d.pos_off = _p(tok_emb.detach()), _p(pos_table), int(pos_off)
         d.head_w, d.head_b, d.head_s = _p(hw), _p(hb), _p(hs)
+        if tiled is not None:
+            assert all(set(t) == {"qkv_w", "proj_w", "fc_w", "fc2_w"} for t in tiled[0]) and len(tiled[0]) == len(layers)
+            _need_gpu(tiled[1])
+            assert tiled[1].dtype == torch.float32 and tiled[1].is_contiguous() and tiled[1].numel() == -(-hw.shape[0] // 16) * 16 * C
+            keep.append(tiled[1])
+            d.head_w, d.w_tiled = _p(tiled[1]), 1
         d.tok, d.codes, d.codes_sB = _p(tok), _p(codes), codes.stride(0)
         d.widx, d.len = _p(widx), _p(length)
         d.x, d.q, d.att, d.h, d.logits = _p(x), _p(q), _p(att), _p(h), _p(logits)

@@ -385,6 +385,9 @@ typedef struct ccvs_gpt_decode {
      * for each other's slots).  Check ccvs_gpt_decode_status(workspace, stream) when a sequence is done. */
     int32_t persistent;
     void* program;                      /* persistent = 1: device buffer of ccvs_gpt_program_bytes(n_layer) bytes, filled by ccvs_gpt_decode_prepare */
+    /* Additive (ABI stays 6; 0 = as before).  1: the `*_w` pointers of `layers` and `head_w` hold the TILED layout of the
+     * same matrices (ccvs_hip_gemm.h, included below: the layout, and an entry point that runs ONE decode GEMM on it); both forms of the step then load whole 1-KB blocks.  Tokens and every buffer stay bit-identical. */
+    int32_t w_tiled;
 } ccvs_gpt_decode;
 int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream);
 /* Synchronises `stream` and returns 0 unless a grid barrier of a persistent decode step launched with this workspace gave up (a
@@ -478,6 +481,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_eval.h"
 /* The input stage (uint8 frames -> crop, Pillow-exact bilinear resample, normalise -> the fp32 clip), additive to ABI version 6, likewise. */
 #include "ccvs_hip_input.h"
+/* the tiled weight layout of the decode GEMMs (additive, ABI version 6) */
+#include "ccvs_hip_gemm.h"
 
 #ifdef __cplusplus
 }
