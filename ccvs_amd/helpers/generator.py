@@ -591,20 +591,22 @@ class Generator:
     # ------------------------------------------------------------------ output stage
     def save_results(self, out, global_iter):
         bs = out["real"].shape[0]
+        fmt = getattr(self.opt, "video_format", "auto")
+        how = dict(video_format=None if fmt == "auto" else fmt, quality=getattr(self.opt, "video_quality", 90), return_clip=False)
         for name in ("real", "fake", "rec", "blur"):                       # generator.py:191-212
             item = out.get(name)
             if item is None:
                 continue
             vid = item["vid"] if isinstance(item, dict) else item
             save_video_batch(vid, bs, global_iter, os.path.join(self.opt.result_path, name), self.opt.fps, True,
-                             self.opt.imagenet_norm, [-1, 1], self.opt.dataset)
+                             self.opt.imagenet_norm, [-1, 1], self.opt.dataset, **how)
             stft = item.get("stft") if self.decode_stft and isinstance(item, dict) else None
             if stft is not None:                                            # (ccvs_amd) --decode_stft: one float32 [T, H, W] .npy per clip
                 save_stft_batch(stft, bs, global_iter, os.path.join(self.opt.result_path, name + "_stft"))
             state = out.get("real_state") if name == "real" else (item.get("state") if isinstance(item, dict) else None)
             if self.opt.state and state is not None:                        # generator.py:213-223: clips with the state marker
                 save_video_batch(vid, bs, global_iter, os.path.join(self.opt.result_path, name + "_state"), self.opt.fps, True,
-                                 self.opt.imagenet_norm, [-1, 1], self.opt.dataset, state=state)
+                                 self.opt.imagenet_norm, [-1, 1], self.opt.dataset, state=state, **how)
 
     def run(self, save=True):
         """The reference's entry point (helpers/generator.py:248-282): build the models, then `n_iter` batches through
@@ -699,18 +701,27 @@ class _ResultWriter:
 
 
 def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, span, dataset, state=None, cat=None, idx=None,
-                     is_layout=False):
-    """helpers/generator.py:285-333.  The clamp / rescale / uint8 / channels-last pack runs on the
-    GPU; files are written as mp4 when torchvision is importable, else as .npy uint8 [T,H,W,3]."""
+                     is_layout=False, video_format=None, quality=90, return_clip=True):
+    """helpers/generator.py:285-333.  The clamp / rescale / uint8 / channels-last pack runs on the GPU.  video_format:
+      None    mp4 when torchvision is importable, else .npy uint8 [T,H,W,3];
+      "npy"   the arrays, whatever imports;
+      "avi"   Motion-JPEG AVI (`ccvs_amd.tools.mjpeg`): the packed clip is JPEG-encoded on the device at `quality` (`ops.mjpeg_encode`,
+              libjpeg's bytes) and the compressed scans are what is copied out for the files.
+    Returns the uint8 clip on the host; `return_clip=False` lets the "avi" form skip that copy where no state marker needs it (then
+    only the compressed scans cross to the host, and None is returned)."""
     if is_layout:
         raise NotImplementedError("layout colour maps are not on the MI355X path (SURVEY 8f)")
+    if video_format not in (None, "npy", "avi"):
+        raise ValueError(f"save_video_batch: video_format {video_format!r} is none of None, 'npy', 'avi'")
     if normalize and imagenet_norm:
         u8 = ops.pack_u8_norm(vid, (0.229, 0.224, 0.225), (0.485, 0.456, 0.406))   # generator.py:303-305, same op order
     elif normalize:
         u8 = ops.pack_u8(vid.contiguous(), float(span[0]), float(span[1]))
     else:
         u8 = (vid.permute(0, 1, 3, 4, 2) * 255).to(torch.uint8)
-    u8 = u8.cpu()
+    dev_u8 = u8
+    if return_clip or video_format != "avi" or state is not None:
+        u8 = u8.cpu()
     if state is not None:  # generator.py:311-323: mark the (x, y) state on every frame
         res = {"bair": 64, "bairhd": 256}.get(dataset)
         if res is not None:
@@ -719,21 +730,31 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
                 for j in range(u8.size(1)):
                     x, y = st[i, j]
                     u8[i, j] = draw_cross(u8[i, j], min(int(res * x), res - 1), min(int(res * y), res - 1))
+            dev_u8 = None  # the marked clip is the one to write: "avi" uploads it again (rare and small)
     os.makedirs(path, exist_ok=True)
-    try:
-        from torchvision.io import write_video
-    except ImportError:
-        write_video = None
+    write_video = None
+    if video_format is None:
+        try:
+            from torchvision.io import write_video
+        except ImportError:
+            pass
+    elif video_format == "avi":
+        from ccvs_amd.tools import mjpeg
+        t, (h, w) = u8.size(1), u8.shape[2:4]
+        scans, off = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), quality)
+        head = mjpeg.jpeg_header(h, w, quality)
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'
         stem = os.path.join(path, f"vid_{bs * global_iter + i:05d}{suffix}")
-        if write_video is not None:
+        if video_format == "avi":
+            mjpeg.write_avi(stem + ".avi", [head + scans[off[k]:off[k + 1]] + mjpeg.EOI for k in range(i * t, (i + 1) * t)], fps, h, w)
+        elif write_video is not None:
             write_video(stem + ".mp4", u8[i], fps)
         else:
             import numpy as np
             np.save(stem + ".npy", u8[i].numpy())
-    return u8
+    return u8 if u8.device.type == "cpu" else None
 
 
 def save_stft_batch(stft, bs, global_iter, path):

@@ -26,6 +26,8 @@ EVAL_EXPORTS = ["ccvs_l1_workspace_bytes", "ccvs_l1_mean", "ccvs_vq_stats_worksp
 INPUT_EXPORTS = ["ccvs_ingest_u8"]
 # every symbol include/ccvs_hip_gemm.h declares (the tiled weight layout of the decode GEMMs; included by ccvs_hip.h as well)
 GEMM_EXPORTS = ["ccvs_gemm_tiled", "ccvs_gemm_tiled_max_rows"]
+# every symbol include/ccvs_hip_output.h declares (the output stage: uint8 clips -> libjpeg-exact JPEG scans; included by ccvs_hip.h too)
+OUTPUT_EXPORTS = ["ccvs_mjpeg_workspace_bytes", "ccvs_mjpeg_encode"]
 
 
 class ConvDesc(C.Structure):
@@ -105,6 +107,8 @@ def load():
     lib.ccvs_vq_stats_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
     lib.ccvs_gemm_tiled_max_rows.restype = C.c_int32
     lib.ccvs_gemm_tiled_max_rows.argtypes = []
+    lib.ccvs_mjpeg_workspace_bytes.restype = C.c_size_t
+    lib.ccvs_mjpeg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_gpt_program_bytes.restype = C.c_int64
     lib.ccvs_gpt_program_bytes.argtypes = [C.c_int32]
     lib.ccvs_conv_fetch_bytes_per_lane.restype = C.c_int
@@ -162,6 +166,7 @@ def load():
         "ccvs_l1_mean": [vp, vp, vp, vp, i64, vp],
         "ccvs_vq_stats": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "ccvs_code_perplexity": [vp, i32, i64, vp, vp],
+        "ccvs_mjpeg_encode": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_ingest_u8": [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i64, i64, vp, vp],
     }
     for name, argtypes in sigs.items():

@@ -28,6 +28,13 @@ def _flag(parser, name, default=False, help=None):
     parser.add_argument(name, type=str2bool, nargs="?", const=True, default=default, help=help)
 
 
+def _jpeg_quality(text):
+    q = int(text)
+    if not 1 <= q <= 100:
+        raise argparse.ArgumentTypeError(f"JPEG quality {q} outside 1 .. 100")
+    return q
+
+
 # dataset presets applied after a first parse (tools/options.py:396-450)
 _PRESETS = {
     "bairhd": dict(dataroot="datasets/bairhd", true_ratio=1, aspect_ratio=1, true_dim=256, categories=None, fps=4),
@@ -88,6 +95,10 @@ class Options:
         # off and no state / audio / point-to-point conditioning, encode just the frames the conditioning crop keeps (the same
         # bits for `fake`: frames are encoded independently); `enc_code` then holds those frames' codes only.
         _flag(p, "--encode_all", default=True)
+        # (ccvs_amd) the clips' files: auto -- mp4 where torchvision.io.write_video imports, else uint8 .npy arrays; npy -- the arrays;
+        # avi -- Motion-JPEG AVI, the JPEG encoder on the GPU (csrc/jpeg.hip: libjpeg's bytes at --video_quality)
+        p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi"])
+        p.add_argument("--video_quality", type=_jpeg_quality, default=90)
         # ---- q_: quantised video model (tools/options.py:159-264)
         p.add_argument("--q_enc_model", type=str, default="taming")
         p.add_argument("--q_dec_model", type=str, default="stylegan2")

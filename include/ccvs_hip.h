@@ -483,6 +483,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_input.h"
 /* the tiled weight layout of the decode GEMMs (additive, ABI version 6) */
 #include "ccvs_hip_gemm.h"
+/* the output stage (uint8 clips -> libjpeg-exact baseline JPEG scans for a Motion-JPEG AVI), additive to ABI version 6, likewise */
+#include "ccvs_hip_output.h"
 
 #ifdef __cplusplus
 }
