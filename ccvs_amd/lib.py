@@ -28,6 +28,8 @@ INPUT_EXPORTS = ["ccvs_ingest_u8"]
 GEMM_EXPORTS = ["ccvs_gemm_tiled", "ccvs_gemm_tiled_max_rows"]
 # every symbol include/ccvs_hip_output.h declares (the output stage: uint8 clips -> libjpeg-exact JPEG scans; included by ccvs_hip.h too)
 OUTPUT_EXPORTS = ["ccvs_mjpeg_workspace_bytes", "ccvs_mjpeg_encode"]
+# every symbol include/ccvs_hip_decode.h declares (the way back: baseline JPEG scans -> libjpeg-exact uint8 frames; included by ccvs_hip.h too)
+DECODE_EXPORTS = ["ccvs_mjpeg_decode_workspace_bytes", "ccvs_mjpeg_decode"]
 
 
 class ConvDesc(C.Structure):
@@ -109,6 +111,8 @@ def load():
     lib.ccvs_gemm_tiled_max_rows.argtypes = []
     lib.ccvs_mjpeg_workspace_bytes.restype = C.c_size_t
     lib.ccvs_mjpeg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ccvs_mjpeg_decode_workspace_bytes.restype = C.c_size_t
+    lib.ccvs_mjpeg_decode_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_gpt_program_bytes.restype = C.c_int64
     lib.ccvs_gpt_program_bytes.argtypes = [C.c_int32]
     lib.ccvs_conv_fetch_bytes_per_lane.restype = C.c_int
@@ -167,6 +171,7 @@ def load():
         "ccvs_vq_stats": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "ccvs_code_perplexity": [vp, i32, i64, vp, vp],
         "ccvs_mjpeg_encode": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
+        "ccvs_mjpeg_decode": [vp, C.c_long, vp, vp, C.c_long, vp, i32, vp, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_ingest_u8": [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i64, i64, vp, vp],
     }
     for name, argtypes in sigs.items():

@@ -1239,3 +1239,101 @@ def mjpeg_encode_to_host(u8, quality=90, restart_mcus=None):
     if off[-1] > stream.numel():
         stream, _ = mjpeg_encode(u8, quality, restart_mcus, capacity=off[-1])
     return stream[:off[-1]].cpu().numpy().tobytes(), off
+
+
+# ------------------------------------------------------------------ the way back (include/ccvs_hip_decode.h)
+_MJPEG_STATUS = {1: "its table entry points outside the call's frames, stream, MCUs or tables", 2: "no Huffman code starts so",
+                 3: "the MCUs need more bits than the unit has", 4: "a run leads past coefficient 63",
+                 5: "bytes are left behind the last MCU, or a 0xFF that no 0x00 follows"}
+
+
+def mjpeg_decode_upload(plan):
+    """A plan of `ccvs_amd.tools.mjpeg.plan_frames` on the device: the unit table, the table records, the frames' record indices and
+    the scans go up in ONE copy (each part at the alignment `ccvs_mjpeg_decode` asks for).  Returns what `mjpeg_decode_uploaded` takes."""
+    import numpy as np
+    n, h, w, sampling = (int(plan[k]) for k in ("n", "h", "w", "sampling"))
+    units = np.ascontiguousarray(plan["units"], dtype=np.int64).reshape(-1, 5)
+    tables = np.ascontiguousarray(plan["tables"], dtype=np.uint8).reshape(-1)
+    frame_table = np.ascontiguousarray(plan["frame_table"], dtype=np.int32).reshape(-1)
+    scans = np.ascontiguousarray(plan["scans"], dtype=np.uint8).reshape(-1)
+    assert frame_table.size == n and tables.size % 4008 == 0, (frame_table.size, n, tables.size)
+    o_tab = units.nbytes                                  # (a multiple of 8; 4008 is one too)
+    o_ft = o_tab + tables.nbytes
+    o_scan = (o_ft + frame_table.nbytes + 7) & ~7
+    blob = np.zeros(o_scan + max(scans.size, 1), dtype=np.uint8)
+    blob[:o_tab] = units.view(np.uint8).reshape(-1)
+    blob[o_tab:o_ft] = tables
+    blob[o_ft:o_ft + frame_table.nbytes] = frame_table.view(np.uint8)
+    blob[o_scan:o_scan + scans.size] = scans
+    return {"n": n, "h": h, "w": w, "sampling": sampling, "blob": torch.from_numpy(blob).to("cuda"), "units_host": units, "o_tab": o_tab, "o_ft": o_ft,
+            "o_scan": o_scan, "scan_bytes": scans.size, "n_tables": tables.size // 4008}
+
+
+def mjpeg_decode_uploaded(up, out=None, status=None, work=None):
+    """`ccvs_mjpeg_decode` on an uploaded plan: (frames uint8 [n, H, W, 3], status int32 [units]), both on the device; status[k] == 0:
+    unit k (row k of the plan's unit table) decoded exactly its MCUs within its bytes.  out: optional uint8 [n, H, W, 3] to write into,
+    frames dense, any frame stride of at least a frame (a slice of a larger clip); only its own bytes are written.  status / work:
+    optional buffers to reuse.  Runs on the current stream; nothing is synchronised."""
+    n, h, w, sampling = up["n"], up["h"], up["w"], up["sampling"]
+    dev = up["blob"].device
+    if out is not None:
+        _need_gpu(out)
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride()[1:] == (3 * w, 3, 1) and (n == 1 or out.stride(0) >= 3 * h * w), \
+            (out.dtype, out.shape, out.stride())
+    else:
+        out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    units = up["units_host"]
+    L = _lib.load()
+    if status is None:
+        status = torch.empty(units.shape[0], dtype=torch.int32, device=dev)
+    if work is None:
+        work = torch.empty(max(int(L.ccvs_mjpeg_decode_workspace_bytes(n, h, w, sampling)), 16), dtype=torch.uint8, device=dev)
+    base = up["blob"].data_ptr()
+    _lib.check(L.ccvs_mjpeg_decode(C.c_void_p(base + up["o_scan"]), up["scan_bytes"], C.c_void_p(base), units.ctypes.data_as(C.c_void_p), units.shape[0],
+                                   C.c_void_p(base + up["o_tab"]), up["n_tables"], C.c_void_p(base + up["o_ft"]), n, h, w, sampling,
+                                   _p(out), out.stride(0) if n > 1 else 3 * h * w, _p(status), _p(work), _stream()), "ccvs_mjpeg_decode")
+    return out, status
+
+
+def mjpeg_decode_planned(plan, out=None):
+    """Upload and decode a plan of `ccvs_amd.tools.mjpeg.plan_frames`: (frames, status) as `mjpeg_decode_uploaded` returns them."""
+    return mjpeg_decode_uploaded(mjpeg_decode_upload(plan), out)
+
+
+def mjpeg_decode(jpegs, out=None, check=True):
+    """uint8 [T, H, W, 3] on the device of T baseline JPEG files (bytes) of one size and sampling -- libjpeg's pixels, bit for bit
+    (DESIGN.md section 4.16).  The files are parsed on the host (`ccvs_amd.tools.mjpeg.plan_frames`: ValueError names the frame and what
+    is malformed or not decoded), everything else runs on the GPU.  check=True reads the units' status words back -- the call's one
+    synchronisation -- and raises ValueError naming the frame and the unit that failed; check=False returns (frames, status) on the
+    device for callers that batch (see `mjpeg_decode_uploaded`)."""
+    from .tools import mjpeg as _mjpeg
+    plan = _mjpeg.plan_frames(jpegs)
+    frames, status = mjpeg_decode_planned(plan, out)
+    if not check:
+        return frames, status
+    st = status.cpu().numpy()
+    if st.any():
+        k = int(st.nonzero()[0][0])
+        frame = int(plan["units"][k, 0])
+        unit = k - int((plan["units"][:k, 0] < frame).sum())
+        raise ValueError(f"mjpeg_decode: frame {frame}, unit {unit} (MCUs {int(plan['units'][k, 3])} .. {int(plan['units'][k, 3] + plan['units'][k, 4]) - 1}) "
+                         f"failed with status {int(st[k])}: {_MJPEG_STATUS.get(int(st[k]), 'unknown')}; {int((st != 0).sum())} of {st.size} units failed")
+    return frames
+
+
+def read_avi_clips(paths):
+    """uint8 [N, T, H, W, 3] on the device of N Motion-JPEG AVI files of equal size and length (`tools.mjpeg.read_avi`), all frames in
+    one decode call."""
+    from .tools import mjpeg as _mjpeg
+    clips = [_mjpeg.read_avi(p) for p in paths]
+    if not clips:
+        raise ValueError("read_avi_clips: no files")
+    h, w, t = clips[0][1], clips[0][2], len(clips[0][3])
+    for p, c in zip(paths, clips):
+        if (c[1], c[2], len(c[3])) != (h, w, t) or t == 0:
+            raise ValueError(f"read_avi_clips: {p} holds {len(c[3])} frames of {c[1]} x {c[2]}, {paths[0]} {t} of {h} x {w}")
+    try:
+        frames = mjpeg_decode([f for c in clips for f in c[3]])
+    except ValueError as exc:
+        raise ValueError(f"read_avi_clips: {exc} (frames count through the files in order, {t} per file; the first is {paths[0]})") from None
+    return frames.view(len(paths), t, h, w, 3)

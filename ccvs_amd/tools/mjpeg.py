@@ -5,8 +5,18 @@
   write_avi(path, frames, fps, h, w)         RIFF 'AVI ': hdrl (avih, one strl: strh vids/MJPG + strf BITMAPINFOHEADER), a movi list of
                                              '00dc' chunks padded to even length, idx1.
   read_avi(path) -> (fps, h, w, [jpeg])      the frames of such a file, byte for byte.
-  decode_frames(jpegs) -> uint8 [T, H, W, 3] with Pillow (ImportError where it is missing): the `loader=` a caller can hand to
-                                             `metrics_from_files` after `read_avi`.
+  decode_frames(jpegs) -> uint8 [T, H, W, 3] with Pillow (ImportError where it is missing), on the host.
+
+The way back on the GPU (`ops.mjpeg_decode`) has its host half here -- everything up to the bytes that go up:
+  parse_jpeg(data)                           the marker walk of one baseline file: size, sampling, quantiser and Huffman tables, restart
+                                             interval, where the scan lies.  ValueError with the reason for what is malformed or not decoded
+                                             (progressive, arithmetic, 12 bit, greyscale, CMYK, other sampling factors, several scans).
+  find_units(scans, offsets, ri, n_mcu)      the unit table of the frames' scans -- a unit is one restart interval, or the whole scan without
+                                             DRI: int64 [units, 5] of frame, byte offset, byte length, first MCU, MCUs (one numpy pass finds
+                                             the markers of all frames).
+  huffman_table(bits, vals)                  a DHT table in the decoder's form (T.81 F.2.2.3 plus an 8-bit lookup).
+  decode_tables(parsed)                      the 4008-byte table record of a frame (include/ccvs_hip_decode.h).
+  plan_frames(jpegs)                         all of it for the frames of one call: scans, unit table, table records, record per frame.
 """
 import struct
 
@@ -152,3 +162,243 @@ def decode_frames(jpegs):
     import io
     import numpy as np
     return np.stack([np.asarray(Image.open(io.BytesIO(j)).convert("RGB")) for j in jpegs])
+
+
+# ------------------------------------------------------------------ the host half of the decoder
+_UNSUPPORTED_SOF = {0xC1: "extended sequential", 0xC2: "progressive", 0xC3: "lossless", 0xC5: "differential sequential", 0xC6: "differential progressive",
+                    0xC7: "differential lossless", 0xC9: "arithmetic-coded", 0xCA: "arithmetic-coded progressive", 0xCB: "arithmetic-coded lossless",
+                    0xCD: "arithmetic-coded differential", 0xCE: "arithmetic-coded differential progressive", 0xCF: "arithmetic-coded differential lossless"}
+SAMPLING = {(1, 1): 0, (2, 1): 1, (2, 2): 2}      # luminance (h, v) factors -> Pillow's `subsampling` number: 4:4:4, 4:2:2, 4:2:0
+TABLE_BYTES = 4008
+
+
+def parse_jpeg(data):
+    """dict of one baseline JPEG file: h, w, sampling (0 / 1 / 2), quant (per component, 64 values in natural order), huffman
+    ({class/id byte: (bits, vals)}; the Annex K tables for a file without DHT), dc_tables / ac_tables (table id per component),
+    restart_interval (0: none), scan_offset, scan_length (the entropy-coded bytes between the SOS header and EOI).  ValueError
+    says what is malformed or outside what the decoder takes."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise ValueError("parse_jpeg: no SOI marker at the start")
+    if len(data) < 4 or data[-2:] != EOI:
+        raise ValueError("parse_jpeg: no EOI marker at the end")
+    qt, huff, sof, ri, pos = {}, {}, None, 0, 2
+    while True:
+        if pos + 4 > len(data) - 2:
+            raise ValueError(f"parse_jpeg: truncated: no segment header at byte {pos}, no SOS so far")
+        if data[pos] != 0xFF or data[pos + 1] in (0x00, 0xFF):
+            raise ValueError(f"parse_jpeg: no marker at byte {pos}")
+        marker, length = data[pos + 1], (data[pos + 2] << 8) | data[pos + 3]
+        if length < 2 or pos + 2 + length > len(data) - 2:
+            raise ValueError(f"parse_jpeg: truncated segment {marker:#04x} at byte {pos}: length {length}")
+        p = data[pos + 4:pos + 2 + length]
+        pos += 2 + length
+        if marker in _UNSUPPORTED_SOF:
+            raise ValueError(f"parse_jpeg: {_UNSUPPORTED_SOF[marker]} JPEG (SOF{marker - 0xC0}) is not decoded, only baseline (SOF0)")
+        if marker == 0xCC:
+            raise ValueError("parse_jpeg: arithmetic coding (DAC) is not decoded")
+        if marker == 0xDB:
+            i = 0
+            while i < len(p):
+                if p[i] >> 4:
+                    raise ValueError("parse_jpeg: 16-bit quantiser tables belong to 12-bit JPEG, which is not decoded")
+                if (p[i] & 15) > 3 or i + 65 > len(p):
+                    raise ValueError("parse_jpeg: malformed DQT segment")
+                nat = [0] * 64
+                for k in range(64):
+                    nat[ZIGZAG[k]] = p[i + 1 + k]
+                qt[p[i] & 15] = tuple(nat)
+                i += 65
+        elif marker == 0xC4:
+            i = 0
+            while i < len(p):
+                if i + 17 > len(p) or (p[i] >> 4) > 1 or (p[i] & 15) > 1:
+                    raise ValueError("parse_jpeg: malformed DHT segment, or a table id that baseline JPEG does not have")
+                bits = bytes(p[i + 1:i + 17])
+                if sum(bits) > 256 or i + 17 + sum(bits) > len(p):
+                    raise ValueError("parse_jpeg: malformed DHT segment")
+                huff[p[i]] = (bits, bytes(p[i + 17:i + 17 + sum(bits)]))
+                i += 17 + sum(bits)
+        elif marker == 0xC0:
+            if sof is not None or len(p) < 6 or len(p) != 6 + 3 * p[5]:
+                raise ValueError("parse_jpeg: malformed or repeated SOF0 segment")
+            if p[0] != 8:
+                raise ValueError(f"parse_jpeg: {p[0]}-bit samples are not decoded, only 8 bit")
+            if p[5] != 3:
+                raise ValueError(f"parse_jpeg: {p[5]} component(s) ({ {1: 'greyscale', 4: 'CMYK'}.get(p[5], 'unusual') }) are not decoded, only three (YCbCr)")
+            sof = ((p[1] << 8) | p[2], (p[3] << 8) | p[4], [(p[6 + 3 * c], p[7 + 3 * c] >> 4, p[7 + 3 * c] & 15, p[8 + 3 * c]) for c in range(3)])
+        elif marker == 0xDD:
+            if len(p) != 2:
+                raise ValueError("parse_jpeg: malformed DRI segment")
+            ri = (p[0] << 8) | p[1]
+        elif marker == 0xDA:
+            if sof is None:
+                raise ValueError("parse_jpeg: SOS before SOF0")
+            if len(p) < 1 or p[0] != 3 or len(p) != 10:
+                raise ValueError("parse_jpeg: not one interleaved scan of the three components")
+            if [p[1 + 2 * c] for c in range(3)] != [c[0] for c in sof[2]] or tuple(p[7:10]) != (0, 63, 0):
+                raise ValueError("parse_jpeg: the scan header does not name the frame's components in order with Ss = 0, Se = 63, Ah = Al = 0")
+            dc, ac = [p[2 + 2 * c] >> 4 for c in range(3)], [p[2 + 2 * c] & 15 for c in range(3)]
+            break
+        elif not (0xE0 <= marker <= 0xEF or marker == 0xFE):
+            raise ValueError(f"parse_jpeg: marker {marker:#04x} is not expected in a baseline file")
+    h, w, comps = sof
+    if h < 1 or w < 1:
+        raise ValueError(f"parse_jpeg: frame size {h} x {w}")
+    factors = [c[1:3] for c in comps]
+    if factors[1] != (1, 1) or factors[2] != (1, 1) or factors[0] not in SAMPLING:
+        raise ValueError(f"parse_jpeg: sampling factors {factors} are not decoded, only luminance 1x1, 2x1 or 2x2 against 1x1 chrominance")
+    sampling = SAMPLING[factors[0]]
+    if sampling and w <= 4:
+        raise ValueError(f"parse_jpeg: a subsampled frame {w} pixels wide has fewer than 3 chrominance columns; libjpeg takes another path there, which is not reproduced")
+    if any(c[3] not in qt for c in comps):
+        raise ValueError("parse_jpeg: a component names a quantiser table the file does not define")
+    if not huff:
+        huff = dict(HUFF)                       # Motion-JPEG frames may rely on the Annex K tables, as libjpeg lets them
+    if any(d > 1 or a > 1 or d not in huff or (0x10 | a) not in huff for d, a in zip(dc, ac)):
+        raise ValueError("parse_jpeg: the scan names a Huffman table the file does not define")
+    return {"h": h, "w": w, "sampling": sampling, "quant": tuple(qt[c[3]] for c in comps), "huffman": huff, "dc_tables": tuple(dc), "ac_tables": tuple(ac),
+            "restart_interval": ri, "scan_offset": pos, "scan_length": len(data) - 2 - pos}
+
+
+def mcu_grid(h, w, sampling):
+    """(MCUs per row, MCU rows) of an h x w frame."""
+    hs, vs = ((1, 1), (2, 1), (2, 2))[sampling]
+    return -(-w // (8 * hs)), -(-h // (8 * vs))
+
+
+def find_units(scans, offsets, restart_intervals, n_mcu):
+    """The unit table of the scans of a call's frames: int64 [units, 5] of (frame, byte offset, byte length, first MCU, MCUs).  scans:
+    the entropy-coded bytes of all frames one behind the other, frame f at scans[offsets[f]:offsets[f + 1]]; restart_intervals: per
+    frame, 0 = no DRI (the whole scan is one unit); n_mcu: the MCUs of a frame.  The RSTn markers of all frames are found in one numpy
+    pass.  ValueError, naming the frame, for any other marker inside a scan, a 0xFF at its end, markers out of order (RSTn counts modulo
+    8 from 0) or a number of units other than ceil(n_mcu / restart interval)."""
+    import numpy as np
+    a = np.frombuffer(bytes(scans), dtype=np.uint8) if not isinstance(scans, np.ndarray) else scans
+    offsets = np.asarray(offsets, dtype=np.int64)
+    ri = np.asarray(restart_intervals, dtype=np.int64)
+    n = ri.size
+    assert offsets.size == n + 1 and offsets[0] == 0 and offsets[-1] == a.size and (np.diff(offsets) >= 0).all()
+    ff = np.flatnonzero(a == 0xFF)
+    fr = np.searchsorted(offsets, ff, side="right") - 1            # the frame of every 0xFF
+    at_end = ff == offsets[fr + 1] - 1
+    if at_end.any():
+        raise ValueError(f"find_units: frame {int(fr[at_end][0])}: the scan ends in 0xFF")
+    nxt = a[ff + 1]
+    is_rst = (nxt >= 0xD0) & (nxt <= 0xD7)
+    other = (nxt != 0) & ~is_rst
+    if other.any():
+        k = int(np.flatnonzero(other)[0])
+        raise ValueError(f"find_units: frame {int(fr[k])}: marker 0xff{int(nxt[k]):02x} at byte {int(ff[k] - offsets[fr[k]])} of the scan (only RSTn may stand there)")
+    rst, rfr = ff[is_rst], fr[is_rst]
+    counts = np.bincount(rfr, minlength=n)                          # markers per frame
+    want = np.where(ri > 0, -(-n_mcu // np.maximum(ri, 1)), 1)
+    if (counts + 1 != want).any():
+        f = int(np.flatnonzero(counts + 1 != want)[0])
+        raise ValueError(f"find_units: frame {f}: {int(counts[f]) + 1} unit(s) in the scan, {int(want[f])} expected for {n_mcu} MCUs at restart interval {int(ri[f])}")
+    k = np.arange(rst.size) - np.repeat(np.cumsum(counts) - counts, counts)      # a marker's number within its frame
+    wrong = nxt[is_rst] - 0xD0 != k % 8
+    if wrong.any():
+        m = int(np.flatnonzero(wrong)[0])
+        raise ValueError(f"find_units: frame {int(rfr[m])}: restart marker {int(k[m])} is RST{int(nxt[is_rst][m]) - 0xD0}, RST{int(k[m]) % 8} expected")
+    first_unit = np.cumsum(want) - want                             # a frame's first row of the table
+    units = np.empty((int(want.sum()), 5), dtype=np.int64)
+    is_first = np.zeros(units.shape[0], dtype=bool)
+    is_first[first_unit] = True
+    is_last = np.zeros(units.shape[0], dtype=bool)
+    is_last[first_unit + counts] = True
+    units[:, 0] = np.repeat(np.arange(n), want)
+    units[is_first, 1], units[~is_first, 1] = offsets[:-1], rst + 2
+    ends = np.empty(units.shape[0], dtype=np.int64)
+    ends[is_last], ends[~is_last] = offsets[1:], rst
+    units[:, 2] = ends - units[:, 1]
+    step = ri[units[:, 0]]
+    units[:, 3] = (np.arange(units.shape[0]) - first_unit[units[:, 0]]) * step
+    units[:, 4] = np.minimum(np.where(step > 0, step, n_mcu), n_mcu - units[:, 3])
+    return units
+
+
+_HUFF_DTYPE = [("look", "<u2", 256), ("maxcode", "<i4", 17), ("valoff", "<i4", 17), ("vals", "u1", 256)]
+_TABLE_DTYPE = [("q", "<u2", (3, 64)), ("dc_sel", "u1", 3), ("ac_sel", "u1", 3), ("pad", "u1", 2), ("huff", _HUFF_DTYPE, 4)]
+
+
+def huffman_table(bits, vals):
+    """(look [256], maxcode [17], valoff [17], vals [256]) of a DHT table: codes assigned as T.81 Annex C does, decoded as F.2.2.3
+    does -- maxcode[l] the largest code of length l (-1: none), valoff[l] the index of its first symbol minus its first code -- behind
+    look[8 bits ahead] = (length << 8) | symbol for the codes of up to 8 bits.  ValueError where the lengths do not form a prefix code."""
+    import numpy as np
+    bits, vals = list(bits), list(vals)
+    if len(bits) != 16 or len(vals) != sum(bits) or len(vals) > 256:
+        raise ValueError("huffman_table: bits / vals of the wrong length")
+    look, maxcode, valoff = np.zeros(256, np.uint16), np.full(17, -1, np.int32), np.zeros(17, np.int32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        if bits[length - 1]:
+            valoff[length] = k - code
+            for _ in range(bits[length - 1]):
+                if length <= 8:
+                    look[code << (8 - length):(code + 1) << (8 - length)] = (length << 8) | vals[k]
+                code, k = code + 1, k + 1
+            maxcode[length] = code - 1
+            if code > (1 << length):
+                raise ValueError("huffman_table: the code lengths do not form a prefix code")
+        code <<= 1
+    out = np.zeros(256, np.uint8)
+    out[:len(vals)] = vals
+    return look, maxcode, valoff, out
+
+
+_HUFF_CACHE = {}
+
+
+def decode_tables(parsed):
+    """The table record of a parsed frame: TABLE_BYTES bytes as include/ccvs_hip_decode.h lays them out."""
+    import numpy as np
+    rec = np.zeros((), dtype=_TABLE_DTYPE)
+    rec["q"] = np.asarray(parsed["quant"], dtype=np.uint16)
+    rec["dc_sel"], rec["ac_sel"] = parsed["dc_tables"], parsed["ac_tables"]
+    for slot, key in enumerate((0x00, 0x01, 0x10, 0x11)):
+        if key in parsed["huffman"]:
+            bv = tuple(bytes(x) for x in parsed["huffman"][key])
+            if bv not in _HUFF_CACHE:
+                _HUFF_CACHE[bv] = huffman_table(*bv)
+            for name, value in zip(("look", "maxcode", "valoff", "vals"), _HUFF_CACHE[bv]):
+                rec["huff"][name][slot] = value
+        else:
+            rec["huff"]["maxcode"][slot] = -1            # a table no component uses: no code is valid
+    out = rec.tobytes()
+    assert len(out) == TABLE_BYTES
+    return out
+
+
+def plan_frames(jpegs):
+    """Everything `ccvs_mjpeg_decode` takes for the frames of one call (files of one size and sampling): dict of n, h, w, sampling, scans
+    (uint8, all scans one behind the other), units (int64 [units, 5]), tables (uint8, the distinct table records), frame_table
+    (int32 [n], the record of every frame).  ValueError names the frame that does not parse or does not match frame 0."""
+    import numpy as np
+    if not len(jpegs):
+        raise ValueError("plan_frames: no frames")
+    scans, intervals, records, frame_table, first = [], [], {}, [], None
+    head = p = record = None
+    for f, data in enumerate(jpegs):
+        data = bytes(data)
+        # the frames of a clip mostly share their header byte for byte: the same bytes parse to the same fields and the same record
+        if head is None or not (data.startswith(head) and data.endswith(EOI) and len(data) >= len(head) + 2):
+            try:
+                p = parse_jpeg(data)
+            except ValueError as exc:
+                raise ValueError(f"frame {f}: {exc}") from None
+            head, record = data[:p["scan_offset"]], decode_tables(p)
+            geom = (p["h"], p["w"], p["sampling"])
+            if first is None:
+                first = geom
+            elif geom != first:
+                raise ValueError(f"frame {f}: size and sampling {geom} differ from frame 0's {first}")
+        scans.append(data[len(head):-2])
+        intervals.append(p["restart_interval"])
+        frame_table.append(records.setdefault(record, len(records)))
+    mx, my = mcu_grid(*first)
+    stream = np.frombuffer(b"".join(scans), dtype=np.uint8)
+    units = find_units(stream, np.cumsum([0] + [len(x) for x in scans]), intervals, mx * my)
+    return {"n": len(jpegs), "h": first[0], "w": first[1], "sampling": first[2], "scans": stream,
+            "units": units, "tables": np.frombuffer(b"".join(records), dtype=np.uint8), "frame_table": np.asarray(frame_table, dtype=np.int32)}

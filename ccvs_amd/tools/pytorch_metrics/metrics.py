@@ -7,15 +7,28 @@ Same function names and argument meaning as the reference:
   get_ssim(x, y)      mean over images of the mean over the 3 channel planes of
                       skimage.metrics.structural_similarity (scikit-image 0.17.2 defaults)  metrics.py:15-22 -> ccvs_ssim
   upscale(videos)     F.interpolate(..., mode='bilinear') up to 161 pixels                  metrics.py:115-124 -> ccvs_resize_bilinear
-  metrics_from_files  the batching / aggregation of metrics.py:27-78 over a caller-supplied mp4 decoder (the reference's is
-                      OpenCV, absent here); `metrics_from_videos` is the same loop on uint8 tensors [N, T, H, W, 3] such as
-                      `save_video_batch` packs.  The folder / CLI glue of metrics.py:99-186 is not mirrored.
+  metrics_from_files  the batching / aggregation of metrics.py:27-78; `metrics_from_videos` is the same loop on uint8 tensors
+                      [N, T, H, W, 3] such as `save_video_batch` packs.  Files named .avi (the Motion-JPEG files `--video_format avi`
+                      writes) or .npy are loaded by `load_videos` below, on the GPU; for .mp4 the caller brings a `loader=` (the
+                      reference's decoder is OpenCV, absent here).
+  load_video(s)       metrics.py:80-97: .avi through `read_avi` and `ops.mjpeg_decode` (the JPEG decoder in HIP, DESIGN.md section
+                      4.16: libjpeg's pixels), .npy the uint8 [T, H, W, 3] arrays `run()` writes; the clips stay on the device.
+                      `resize` other than None raises NotImplementedError (the reference's is OpenCV INTER_AREA, not reproduced).
+  get_video_files, get_folder(s), print_scores, main, and the argparse block      metrics.py:92-186:
+                      python -m ccvs_amd.tools.pytorch_metrics.metrics --exp_tag TAG [--real_tag --real_folder --fake_folder
+                      --num_folds --idx --print_256] prints the reference's lines for results/*TAG/{real,fake}; the LPIPS lines say
+                      "not available (needs pretrained weights)".
   get_lpips           NOT available: piq.LPIPS is a pretrained VGG16 plus learned linear heads whose weights are downloaded;
                       no such file exists offline and the network is not on the synthesis path.  Raises NotImplementedError;
                       the aggregate functions return None in its place.
 
 x, y: [N, 3, H, W] fp32 CUDA tensors in [0, 1].  No CPU fallback: the kernels live in libccvs_hip.so.
 """
+import argparse
+import os
+from glob import glob
+
+import numpy as np
 import torch
 
 from ccvs_amd import ops
@@ -92,12 +105,14 @@ def metrics_from_videos(real_videos_u8, generated_videos_u8, print_256=False, id
 
 
 def metrics_from_files(real_video_files, generated_video_files, resize, num_workers, print_256, idx, loader=None):
-    """metrics.py:27-78 with the decoding of the mp4 files left to `loader(files, resize) -> uint8 [B, T, H, W, 3]`: the reference
-    decodes with OpenCV (metrics.py:80-97), which this image does not have, and writing / reading mp4 is outside the path
-    (SURVEY 8 f4).  Without a loader the call raises; clips already in memory go to `metrics_from_videos`."""
+    """metrics.py:27-78.  loader: `loader(files, resize) -> uint8 [B, T, H, W, 3]` (numpy or torch) in place of `load_videos`; it is
+    needed for .mp4 names only -- the reference decodes those with OpenCV (metrics.py:80-97), which this image does not have, so
+    without a loader they raise."""
     if loader is None:
-        raise RuntimeError("metrics_from_files: no mp4 decoder here (the reference uses OpenCV); pass loader=..., or call "
-                           "metrics_from_videos on the uint8 clips")
+        if any(os.path.splitext(str(f))[1].lower() not in (".avi", ".npy") for f in list(real_video_files) + list(generated_video_files)):
+            raise RuntimeError("metrics_from_files: no mp4 decoder here (the reference uses OpenCV); pass loader=..., or call "
+                               "metrics_from_videos on the uint8 clips")
+        loader = lambda files, size: load_videos(files, size, num_workers)  # noqa: E731
     batch_size = 16
     total = len(real_video_files)
     ssim, psnr = ([], []) if len(idx) == 0 else ([[] for _ in idx], [[] for _ in idx])
@@ -108,3 +123,123 @@ def metrics_from_files(real_video_files, generated_video_files, resize, num_work
             fake = torch.as_tensor(loader(generated_video_files[sl], resize)).cuda() / 255
             _scores(real, fake, idx, None, ssim, psnr)
     return _aggregate(ssim, psnr, print_256, idx, batch_size)
+
+
+def load_video(file, resize):
+    """metrics.py:80-90: uint8 [T, H, W, 3] on the device of one .avi (Motion-JPEG, decoded on the GPU) or .npy file."""
+    return load_videos([file], resize, 1)[0]
+
+
+def get_video_files(folder):
+    """metrics.py:92-93, for the kinds of file a run writes here: the folder's *.mp4, else its *.avi, else its *.npy, sorted."""
+    for ext in ("mp4", "avi", "npy"):
+        files = sorted(glob(os.path.join(folder, "*." + ext)))
+        if files:
+            return files
+    return []
+
+
+def load_videos(video_files, resize, num_workers):
+    """metrics.py:95-97: uint8 [B, T, H, W, 3] on the device.  The .avi files of a batch are decoded by one call; `num_workers` is
+    accepted and unused (the files are read by this process, the frames decoded by the GPU)."""
+    if resize is not None:
+        raise NotImplementedError("load_videos: resize is OpenCV's INTER_AREA in the reference, which is not reproduced here; pass resize=None")
+    kinds = {os.path.splitext(str(f))[1].lower() for f in video_files}
+    if kinds == {".avi"}:
+        return ops.read_avi_clips([str(f) for f in video_files])
+    if kinds == {".npy"}:
+        clips = [np.load(str(f)) for f in video_files]
+        for f, c in zip(video_files, clips):
+            if c.dtype != np.uint8 or c.ndim != 4 or c.shape[-1] != 3 or c.shape != clips[0].shape:
+                raise ValueError(f"load_videos: {f} holds {c.dtype} {c.shape}, not a uint8 [T, H, W, 3] clip of the batch's shape")
+        return torch.from_numpy(np.stack(clips)).cuda()
+    raise RuntimeError(f"load_videos: files of kind(s) {sorted(kinds)}: one batch is all .avi or all .npy (no mp4 decoder here)")
+
+
+def get_folder(exp_tag, fold_i=None):
+    """metrics.py:99-104."""
+    if fold_i is not None:
+        exp_tag += f"_{fold_i}"
+    all_folders = glob(f"results/*{exp_tag}")
+    assert len(all_folders) == 1, f"Too many possibilities for this tag {exp_tag}:\n{all_folders}"
+    return all_folders[0]
+
+
+def get_folders(exp_tag, num_folds):
+    """metrics.py:106-113."""
+    if num_folds is not None:
+        return [get_folder(exp_tag, i) for i in range(num_folds)]
+    return [get_folder(exp_tag)]
+
+
+def print_scores(scores, name):
+    """metrics.py:126-130; a metric that is not available here (LPIPS: its scores are None) says so instead of a number."""
+    if any(s is None for s in scores):
+        print(f"{name} scores: not available (needs pretrained weights)")
+        return
+    print(f"Individual {name} scores")
+    print(scores)
+    print(f"Mean/std of {name} across {len(scores)} runs")
+    print(np.mean(scores), np.std(scores))
+
+
+def main(args):
+    """metrics.py:132-172."""
+    fake_folders = get_folders(args.exp_tag, args.num_folds)
+    real_tag = args.exp_tag if args.real_tag is None else args.real_tag
+    real_folders = get_folders(real_tag, args.num_folds)
+
+    if len(args.idx) == 0:
+        lpips, ssim, psnr = [], [], []
+    else:
+        lpips, ssim, psnr = [[] for _ in args.idx], [[] for _ in args.idx], [[] for _ in args.idx]
+    for i, (real_root, fake_root) in enumerate(zip(sorted(real_folders), sorted(fake_folders))):
+        print(f"[{i}] Loading real")
+        real_video_files = get_video_files(os.path.join(real_root, args.real_folder))
+        print(f"Found {len(real_video_files)} {args.real_folder} video files")
+
+        print(f"[{i}] Loading fake")
+        fake_video_files = get_video_files(os.path.join(fake_root, args.fake_folder))
+        print(f"Found {len(fake_video_files)} {args.fake_folder} video files")
+
+        assert len(real_video_files) == len(fake_video_files)
+
+        print(f"[{i}] Computing metrics")
+        lpips_i, ssim_i, psnr_i = metrics_from_files(real_video_files, fake_video_files, args.resize, args.num_workers, args.print_256, args.idx)
+        if len(args.idx) == 0:
+            lpips.append(lpips_i)
+            ssim.append(ssim_i)
+            psnr.append(psnr_i)
+        else:
+            for k in range(len(args.idx)):
+                lpips[k].append(None if lpips_i is None else lpips_i[k])
+                ssim[k].append(ssim_i[k])
+                psnr[k].append(psnr_i[k])
+
+    if len(args.idx) == 0:
+        print_scores(lpips, "LPIPS")
+        print_scores(ssim, "SSIM")
+        print_scores(psnr, "PSNR")
+    else:
+        for k in range(len(args.idx)):
+            print_scores(lpips[k], f"LPIPS-{k}")
+            print_scores(ssim[k], f"SSIM-{k}")
+            print_scores(psnr[k], f"PSNR-{k}")
+
+
+def parse_args(argv=None):
+    parser = argparse.ArgumentParser()
+    parser.add_argument('--exp_tag', type=str, default=None)
+    parser.add_argument('--real_tag', type=str, default=None)
+    parser.add_argument('--real_folder', type=str, default="real")
+    parser.add_argument('--fake_folder', type=str, default="fake")
+    parser.add_argument('--num_folds', type=int, default=None)
+    parser.add_argument('--idx', type=int, nargs="+", default=[])
+    parser.add_argument('--num_workers', type=int, default=8)
+    parser.add_argument('--print_256', action='store_true')
+    parser.add_argument('--resize', type=int, nargs="+", default=None)
+    return parser.parse_args(argv)
+
+
+if __name__ == "__main__":
+    main(parse_args())

@@ -485,6 +485,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_gemm.h"
 /* the output stage (uint8 clips -> libjpeg-exact baseline JPEG scans for a Motion-JPEG AVI), additive to ABI version 6, likewise */
 #include "ccvs_hip_output.h"
+/* the way back (baseline JPEG scans -> libjpeg-exact uint8 frames), additive to ABI version 6, likewise */
+#include "ccvs_hip_decode.h"
 
 #ifdef __cplusplus
 }
