@@ -248,3 +248,150 @@ extern "C" int ccvs_ingest_u8(const uint8_t* src, int64_t src_frame_bytes, int32
     CCVS_CHECK_LAUNCH("ccvs_ingest_u8");
     return CCVS_OK;
 }
+
+// ================================================================== ccvs_ingest_f32
+// The input stage of the video-file datasets (include/ccvs_hip_video.h): the reference's tensor transform chain
+// -- uint8 frames / 255, up to three (crop, torch-bilinear resize) stages with fp32 values between them, Normalize -- per output pixel.
+// One device function evaluates a stage from the values of the stage below it; the kernel instantiated for ONE stage is the staged
+// form (one launch per stage, intermediates in HBM), the one instantiated for all stages the fused form.  Every operation is a single
+// correctly rounded fp32 one: contraction is switched off for this part of the file AND inside every function body, so no multiply and
+// add fuse into an FMA (plain operators, not __fmul_rn / __fadd_rn: those are header functions compiled under the default contraction
+// mode and fuse again once inlined), and a value handed from stage to stage in a register has the bits it would have had in memory,
+// so the two forms agree bit for bit.
+// HBM-bound at most: a lane takes 4 consecutive output pixels of a row and writes them with one 16-byte store; the reads hit the small
+// source (or the previous stage's tensor) through the caches.  No LDS.
+#pragma clang fp contract(off)
+
+struct F32Stage {
+    int top, left, hin, win, ho, wo;   // the crop box inside the stage's input (hin x win pixels of it) and the output size
+    float sh, sw;                      // (float)hin / (float)ho, (float)win / (float)wo
+};
+struct IngestF32Args {
+    const void* src;
+    long src_sN, src_sC;
+    int Ws, N, C, pre, post;
+    F32Stage st[CCVS_INGEST_MAX_STAGES];
+    float* out;
+    long out_sN, out_sC;
+    float mean[3], std[3];
+};
+
+// (first sample, second sample, weights) of output index `dst` on an axis of `in` samples: torch's area_pixel_compute_source_index
+__device__ __forceinline__ void axis_taps(float scale, int dst, int in, int& i0, int& i1, float& l0, float& l1) {
+#pragma clang fp contract(off)
+    const float s = fmaxf(scale * ((float)dst + 0.5f) - 0.5f, 0.f);
+    i0 = (int)s;
+    i0 = i0 < in - 1 ? i0 : in - 1;   // (arithmetically never taken: s < in - 0.5; keeps every read inside the box whatever the arguments)
+    i1 = i0 + (i0 < in - 1 ? 1 : 0);
+    l1 = s - (float)i0;
+    l0 = 1.f - l1;
+}
+
+// the value of stage S's output at (y, x) of frame `frame` (a pointer to the frame's first source element), channel c; S == -1: the source
+template <int S, bool U8>
+__device__ __forceinline__ float chain_value(const IngestF32Args& a, const void* frame, int c, int y, int x) {
+#pragma clang fp contract(off)
+    if constexpr (S < 0) {
+        float v;
+        if constexpr (U8) v = (float)((const uint8_t*)frame)[((long)y * a.Ws + x) * 3 + c];
+        else v = ((const float*)frame)[c * a.src_sC + (long)y * a.Ws + x];
+        if (a.pre == CCVS_INGEST_PRE_DIV255) v = v / 255.f;
+        else if (a.pre == CCVS_INGEST_PRE_X2M1) v = v * 2.f - 1.f;
+        return v;
+    } else {
+        const F32Stage& s = a.st[S];
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        axis_taps(s.sh, y, s.hin, y0, y1, ly0, ly1);
+        axis_taps(s.sw, x, s.win, x0, x1, lx0, lx1);
+        const float p00 = chain_value<S - 1, U8>(a, frame, c, s.top + y0, s.left + x0);
+        const float p01 = chain_value<S - 1, U8>(a, frame, c, s.top + y0, s.left + x1);
+        const float p10 = chain_value<S - 1, U8>(a, frame, c, s.top + y1, s.left + x0);
+        const float p11 = chain_value<S - 1, U8>(a, frame, c, s.top + y1, s.left + x1);
+        const float r0 = lx0 * p00 + lx1 * p01;
+        const float r1 = lx0 * p10 + lx1 * p11;
+        return ly0 * r0 + ly1 * r1;
+    }
+}
+
+template <int NS, bool U8>
+__global__ __launch_bounds__(256) void ingest_f32_kernel(IngestF32Args a) {
+#pragma clang fp contract(off)
+    const int Ho = a.st[NS - 1].ho, Wo = a.st[NS - 1].wo;
+    const int groups = (Wo + 3) >> 2;
+    const long total = (long)a.N * a.C * Ho * groups;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int g = (int)(i % groups);
+        long r = i / groups;
+        const int y = (int)(r % Ho);
+        r /= Ho;
+        const int c = (int)(r % a.C);
+        const long n = r / a.C;
+        const int x = 4 * g;
+        const int npx = Wo - x < 4 ? Wo - x : 4;
+        const void* frame = U8 ? (const void*)((const uint8_t*)a.src + n * a.src_sN) : (const void*)((const float*)a.src + n * a.src_sN);
+        F32Quad v;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float t = 0.f;
+            if (k < npx) {
+                t = chain_value<NS - 1, U8>(a, frame, c, y, x + k);
+                if (a.post) t = (t - a.mean[c]) / a.std[c];
+            }
+            v.v[k] = t;
+        }
+        float* o = a.out + n * a.out_sN + c * a.out_sC + (long)y * Wo + x;
+        if (npx == 4) *(F32Quad*)o = v;
+        else
+            for (int k = 0; k < npx; ++k) o[k] = v.v[k];
+    }
+}
+
+template <bool U8>
+static void launch_ingest_f32(const IngestF32Args& a, int n_stages, unsigned blocks, hipStream_t stream) {
+    if (n_stages == 1) hipLaunchKernelGGL((ingest_f32_kernel<1, U8>), dim3(blocks), dim3(256), 0, stream, a);
+    else if (n_stages == 2) hipLaunchKernelGGL((ingest_f32_kernel<2, U8>), dim3(blocks), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL((ingest_f32_kernel<3, U8>), dim3(blocks), dim3(256), 0, stream, a);
+}
+
+extern "C" int ccvs_ingest_f32(const void* src, int32_t src_is_u8, int64_t src_sN, int64_t src_sC, int32_t N, int32_t C, int32_t Hs, int32_t Ws,
+                               int32_t pre, const int32_t* stages, int32_t n_stages, const float* mean_std, float* out, int64_t out_sN,
+                               int64_t out_sC, void* stream) {
+    CCVS_REQUIRE(src && out && stages, "ccvs_ingest_f32: null source, output or stage list");
+    CCVS_REQUIRE(N > 0 && Hs > 0 && Ws > 0 && (long)Hs * Ws < (1L << 30), "ccvs_ingest_f32: empty shape, or a frame of 2^30 pixels or more");
+    CCVS_REQUIRE(src_is_u8 ? C == 3 : (C == 1 || C == 3), "ccvs_ingest_f32: %d channels (uint8 frames have 3, fp32 planes 1 or 3)", C);
+    CCVS_REQUIRE(pre >= CCVS_INGEST_PRE_NONE && pre <= CCVS_INGEST_PRE_X2M1, "ccvs_ingest_f32: pre-op %d is none of CCVS_INGEST_PRE_*", pre);
+    CCVS_REQUIRE(n_stages >= 1 && n_stages <= CCVS_INGEST_MAX_STAGES, "ccvs_ingest_f32: %d stages, 1 .. %d are evaluated", n_stages, CCVS_INGEST_MAX_STAGES);
+    if (src_is_u8) CCVS_REQUIRE(N == 1 || src_sN >= (int64_t)Hs * Ws * 3, "ccvs_ingest_f32: frame stride smaller than a frame");
+    else CCVS_REQUIRE((C == 1 || src_sC >= (int64_t)Hs * Ws) && (N == 1 || src_sN >= (int64_t)Hs * Ws), "ccvs_ingest_f32: source plane or frame stride smaller than a plane");
+    IngestF32Args a;
+    a.src = src; a.src_sN = src_sN; a.src_sC = src_sC; a.Ws = Ws; a.N = N; a.C = C; a.pre = pre; a.post = mean_std ? 1 : 0;
+    int hin = Hs, win = Ws;
+    for (int s = 0; s < CCVS_INGEST_MAX_STAGES; ++s) {
+        F32Stage& st = a.st[s];
+        if (s >= n_stages) {
+            st = a.st[n_stages - 1];
+            continue;
+        }
+        const int32_t* e = stages + 6 * s;
+        CCVS_REQUIRE(e[0] >= 0 && e[1] >= 0 && e[2] > 0 && e[3] > 0 && (long)e[0] + e[2] <= hin && (long)e[1] + e[3] <= win,
+                     "ccvs_ingest_f32: stage %d: crop box (%d, %d, %d, %d) leaves its %d x %d input", s, e[0], e[1], e[2], e[3], hin, win);
+        CCVS_REQUIRE(e[4] > 0 && e[5] > 0 && (long)e[4] * e[5] < (1L << 30), "ccvs_ingest_f32: stage %d: output size %d x %d", s, e[4], e[5]);
+        st.top = e[0]; st.left = e[1]; st.hin = e[2]; st.win = e[3]; st.ho = e[4]; st.wo = e[5];
+        st.sh = (float)st.hin / (float)st.ho;
+        st.sw = (float)st.win / (float)st.wo;
+        hin = st.ho; win = st.wo;
+    }
+    CCVS_REQUIRE((C == 1 || out_sC >= (int64_t)hin * win) && out_sN >= 0, "ccvs_ingest_f32: output plane stride smaller than a plane, or a negative frame stride");
+    for (int c = 0; c < 3; ++c) {
+        a.mean[c] = mean_std && c < C ? mean_std[c] : 0.f;
+        a.std[c] = mean_std && c < C ? mean_std[C + c] : 1.f;
+    }
+    a.out = out; a.out_sN = out_sN; a.out_sC = out_sC;
+    const long work = (long)N * C * hin * ((win + 3) / 4);
+    const unsigned blocks = strided_grid(work, stream, 8);
+    if (src_is_u8) launch_ingest_f32<true>(a, n_stages, blocks, (hipStream_t)stream);
+    else launch_ingest_f32<false>(a, n_stages, blocks, (hipStream_t)stream);
+    CCVS_CHECK_LAUNCH("ccvs_ingest_f32");
+    return CCVS_OK;
+}

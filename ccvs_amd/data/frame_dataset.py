@@ -7,7 +7,10 @@ crop geometry (`get_augmentation_parameters`, :120-165) and the chain Resize / R
 the chain: `plan` folds it into stages (box, size) that `ops.ingest_u8` executes -- every Resize a `PIL.Image.resize(BILINEAR)`,
 bit for bit.  `FrameLoader` batches items, decodes ahead in threads, uploads the uint8 frames and returns the fp32 clip.
 
-Video files (`from_vid=True`: kinetics600, drums, ucf101), `--load_state`, STFT inputs and layouts are outside this path and raise."""
+The datasets of video files (`from_vid=True`: kinetics600, drums, ucf101) and their STFT stream are `video_dataset.py`'s: Motion-JPEG
+AVI files decoded on the GPU, the reference's tensor transform chain (`ops.ingest_f32`); `frames_root` routes them there when the
+dataset's folder holds at least one `.avi` and raises when it holds none.  `--load_state` and layouts are outside both paths and raise.
+The geometry both share (`resize_target`, `_Chain`, the crop parameters, `plan`) lives in `transform_plan.py`."""
 import os
 import random
 from collections import deque
@@ -17,17 +20,16 @@ import numpy as np
 import torch
 
 from .folder_dataset import NPY_EXTENSION, make_dataset
+from .transform_plan import IMAGENET_MEAN, IMAGENET_STD, ChainGeometry, _Chain, resize_target   # noqa: F401  (moved there; still importable from here)
 
 # --dataset -> the folder of frames under dataroot for the validation phase (bairhd_dataset.py:10,23: "valid" reads "test")
 FRAME_FOLDERS = {"bairhd": os.path.join("original_frames_256", "test")}
 # datasets the reference reads from video files (tools/options.py:421-449: from_vid)
 VIDEO_DATASETS = ("kinetics600", "drums", "ucf101")
 
-IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
-
 
 def frames_root(opt):
-    """The folder `FrameDataset` would read for `opt`, or None when `opt.dataroot` is no directory (then there is no dataset on disk
+    """The folder `FrameDataset` would read for `opt` (for a dataset of video files: the dataroot `VideoDataset` reads), or None when `opt.dataroot` is no directory (then there is no dataset on disk
     and the caller keeps its synthetic input).  A directory that cannot be read as frames raises, naming the reason."""
     root = getattr(opt, "dataroot", None)
     if not root or not os.path.isdir(root):
@@ -36,11 +38,15 @@ def frames_root(opt):
         raise NotImplementedError("--layout: label-map inputs are not on the MI355X path")
     if getattr(opt, "load_state", False):
         raise NotImplementedError("--load_state: the annotated-frames dataset (frame states) is not read here")
-    if getattr(opt, "stft", False):
-        raise NotImplementedError(f"--x_stft reads STFT pickles beside video files: not read from {root} (no video decoder on this path)")
     if opt.dataset in VIDEO_DATASETS:
-        raise NotImplementedError(f"--dataset {opt.dataset} is read from video files (.mp4 / .avi through a video decoder), which this "
-                                  f"path does not decode; export the clips as frame folders and use a frame-folder dataset")
+        from .video_dataset import find_videos
+        if find_videos(opt) is None:
+            raise NotImplementedError(f"--dataset {opt.dataset} is read from video files: no Motion-JPEG .avi file of it was found under {root} "
+                                      f"(.mp4 and MPEG-4 files are not decoded on this path; re-encode the clips once as Motion-JPEG AVI, "
+                                      f"INTEGRATION.md, or export them as frame folders and use a frame-folder dataset)")
+        return root                                                      # `ccvs_amd.data.VideoDataset` reads it (video_dataset.py)
+    if getattr(opt, "stft", False):
+        raise NotImplementedError(f"--x_stft reads STFT pickles beside video files: --dataset {opt.dataset} under {root} is not a video dataset")
     if opt.dataset not in FRAME_FOLDERS:
         raise NotImplementedError(f"--dataset {opt.dataset}: no frame-folder layout is known for it (known: {sorted(FRAME_FOLDERS)})")
     path = os.path.join(root, FRAME_FOLDERS[opt.dataset])
@@ -49,56 +55,12 @@ def frames_root(opt):
     return path
 
 
-def resize_target(h, w, size):
-    """Output (h, w) of torchvision 0.8.1's `Resize(size)` on an h x w frame: an int or a one-element list sizes the smaller edge, the
-    other edge is int(size * long / short), a frame whose smaller edge already has that size is returned untouched; a two-element
-    list is exactly (h, w)."""
-    if isinstance(size, (list, tuple)) and len(size) == 1:
-        size = size[0]
-    if isinstance(size, (list, tuple)):
-        assert len(size) == 2, size
-        return int(size[0]), int(size[1])
-    size = int(size)
-    if (w <= h and w == size) or (h <= w and h == size):
-        return h, w
-    if w < h:
-        return int(size * h / w), size
-    return size, int(size * w / h)
-
-
-class _Chain:
-    """Folds the reference's chain into stages (box, size): a crop that follows a resize waits for the next resize and becomes its
-    box; steps that change nothing are dropped."""
-
-    def __init__(self, h, w):
-        self.h, self.w, self.box, self.stages = h, w, None, []
-
-    def resize(self, size):
-        th, tw = resize_target(self.h, self.w, size)
-        if (th, tw) != (self.h, self.w):
-            self.stages.append((self.box, (th, tw)))
-            self.box, self.h, self.w = None, th, tw
-
-    def crop(self, top, left, h, w, what):
-        if not (0 <= top and 0 <= left and h > 0 and w > 0 and top + h <= self.h and left + w <= self.w):
-            raise ValueError(f"{what}: the crop (top {top}, left {left}, {h} x {w}) leaves the {self.h} x {self.w} image -- PIL would pad "
-                             f"it with black; --true_dim / --true_ratio do not describe these frames")
-        if (top, left, h, w) == (0, 0, self.h, self.w):
-            return
-        base = self.box or (0, 0, self.h, self.w)
-        self.box, self.h, self.w = (base[0] + top, base[1] + left, h, w), h, w
-
-    def done(self):
-        if self.box is not None:
-            self.stages.append((self.box, (self.h, self.w)))
-            self.box = None
-        return self.stages
-
-
-class FrameDataset:
+class FrameDataset(ChainGeometry):
     def __init__(self, opt, phase="valid", load_vid=True):
         if phase != "valid":
             raise NotImplementedError("FrameDataset is the validation-phase dataset (no flips, zooms, colour jitter): phase must be 'valid'")
+        if opt.dataset in VIDEO_DATASETS:
+            raise NotImplementedError(f"--dataset {opt.dataset} is read from video files: that is `ccvs_amd.data.VideoDataset`")
         self.opt, self.phase, self.load_vid = opt, phase, bool(load_vid)
         root = frames_root(opt)
         if root is None:
@@ -110,64 +72,10 @@ class FrameDataset:
         for path in sorted(self.frame_paths):                           # bairhd_dataset.py:24-31: one directory is one video
             groups.setdefault(os.path.dirname(path), []).append(path)
         self.vid_frame_paths = list(groups.values())
-        dims = [2 ** k for k in range(2, int(np.log2(opt.max_dim)) + 1)]  # base_dataset.py:74-75
-        self.dim = dims[int(np.log2(opt.dim)) - 2]
-        self.out_size = (self.dim, int(self.dim * opt.aspect_ratio))    # the clip the reference allocates (:265)
-        self.norm = (IMAGENET_MEAN, IMAGENET_STD) if getattr(opt, "imagenet_norm", False) else ((0.5,) * 3, (0.5,) * 3)
+        self.init_geometry()
 
     def __len__(self):
         return len(self.vid_frame_paths) if self.load_vid else len(self.frame_paths)
-
-    # ---- geometry
-    def crop_offsets(self):
-        """The draws of `get_augmentation_parameters` in validation (:141): two `random.random()` for `fixed_crop` without
-        `centered_crop`, none otherwise."""
-        o = self.opt
-        if not o.fixed_top_centered_zoom and o.fixed_crop and not o.centered_crop:
-            return random.random(), random.random()
-        return 0.5, 0.5
-
-    def augmentation(self, offsets=(0.5, 0.5)):
-        """(top, left, h_crop, w_crop, scale) of `get_augmentation_parameters` in validation (:120-165)."""
-        o = self.opt
-        h, w = int(o.true_dim), int(o.true_dim * o.true_ratio)
-        if o.fixed_top_centered_zoom:
-            h_crop = int(h / o.fixed_top_centered_zoom)
-            w_crop = int(h_crop * o.aspect_ratio)
-            assert w >= w_crop, (w, w_crop)
-            return 0, int((w - w_crop) / 2), h_crop, w_crop, None
-        if o.fixed_crop:
-            h_crop, w_crop = o.fixed_crop[0], o.fixed_crop[1]
-            h_scaled, w_scaled = int(h * 1.), int(w * 1.)
-            assert h_scaled - h_crop >= 0 and w_scaled - w_crop >= 0, (h_scaled, w_scaled, o.fixed_crop)
-            return int(offsets[0] * (h_scaled - h_crop)), int(offsets[1] * (w_scaled - w_crop)), h_crop, w_crop, (h_scaled, w_scaled)
-        zoom = max(1., o.aspect_ratio / o.true_ratio)
-        h_crop = int(h / zoom)
-        w_crop = int(h_crop * o.aspect_ratio)
-        assert h >= h_crop and w >= w_crop, (h, w, h_crop, w_crop)
-        return 0, 0, h_crop, w_crop, None
-
-    def plan(self, src_h, src_w, offsets=(0.5, 0.5)):
-        """The stages [(box, size), ...] the reference's chain (`get_transform`, :348-357) amounts to for a src_h x src_w frame: each
-        is a crop to `box` = (top, left, h, w) (None: the whole image) followed by a bilinear resize to `size` = (h, w).  [] when the
-        frame already is the clip's frame.  Raises when a crop leaves the image or the result is not the clip's frame size."""
-        o = self.opt
-        top, left, h_crop, w_crop, scale = self.augmentation(offsets)
-        c = _Chain(int(src_h), int(src_w))
-        if o.resize_img is not None:
-            c.resize(list(o.resize_img))
-        if o.resize_center_crop_img is not None:
-            s = int(o.resize_center_crop_img)
-            c.resize(s)
-            c.crop(int(round((c.h - s) / 2.)), int(round((c.w - s) / 2.)), s, s, "--resize_center_crop_img")
-        if scale is not None:
-            c.resize(list(scale))
-        c.crop(top, left, h_crop, w_crop, "the crop of --true_dim / --fixed_crop / --fixed_top_centered_zoom")
-        c.resize(self.dim)
-        if (c.h, c.w) != self.out_size:
-            raise ValueError(f"the transform chain turns a {src_h} x {src_w} frame into {c.h} x {c.w}, not the clip's {self.out_size[0]} x "
-                             f"{self.out_size[1]} (--dim {self.dim}, --aspect_ratio {o.aspect_ratio})")
-        return c.done()
 
     # ---- items
     def choose(self, index):

@@ -88,13 +88,17 @@ class Generator:
     def get_data_info(self, phase, data_type, fold=None, num_folds=None):
         """The reference's dataset/loader factory (generator.py:232-246).  When `--dataroot` is a directory holding the frame folders
         of `--dataset`, the batches are its clips: `ccvs_amd.data.FrameDataset` / `FrameLoader` (uint8 frames uploaded, crop +
-        Pillow-exact resample + normalise on the GPU); a directory that cannot be read that way raises.  With no such directory the
-        input is the seeded synthetic tensor, as before."""
-        from ccvs_amd.data.frame_dataset import FrameDataset, FrameLoader, frames_root
+        Pillow-exact resample + normalise on the GPU), or, for the datasets of video files, the clips of its Motion-JPEG `.avi` files
+        (`VideoDataset` / `VideoLoader`: compressed bytes uploaded, JPEG decode + the tensor transform chain on the GPU); a directory
+        that cannot be read that way raises.  With no such directory the input is the seeded synthetic tensor, as before."""
+        from ccvs_amd.data.frame_dataset import VIDEO_DATASETS, FrameDataset, FrameLoader, frames_root
         if frames_root(self.opt) is not None:
+            Dataset, Loader = FrameDataset, FrameLoader
+            if self.opt.dataset in VIDEO_DATASETS:                           # Motion-JPEG AVI files: decoded and transformed on the GPU
+                from ccvs_amd.data.video_dataset import VideoDataset as Dataset, VideoLoader as Loader
             bs = (self.opt.batch_size_img if data_type == "img" else self.opt.batch_size_vid) * (self.opt.batch_size_valid_mult if phase == "valid" else 1)
             lo, hi = self.engine.shard_batch(bs) if self.engine is not None else (0, bs)
-            loader = FrameLoader(FrameDataset(self.opt, phase=phase, load_vid=data_type == "vid"), bs, lo, hi, cycle=self.opt.iter_function == "cycle")
+            loader = Loader(Dataset(self.opt, phase=phase, load_vid=data_type == "vid"), bs, lo, hi, cycle=self.opt.iter_function == "cycle")
             return {"dataloader": loader, "datasampler": None, "epoch": 0, "phase": phase, "data_type": data_type,
                     "batch_size_per_gpu": hi - lo, "loader_iter": iter(loader), "fold": fold, "num_folds": num_folds}
         bs = self.opt.batch_size_vid * self.opt.batch_size_valid_mult
@@ -652,6 +656,9 @@ class Generator:
             finally:
                 if writer is not None:
                     writer.close()
+            loader = self.valid_data_info["dataloader"]
+            if hasattr(loader, "check"):                                    # the JPEG decoder's status words of every batch read: one
+                loader.check()                                              # read-back here, where the run has synchronised anyway
             print('Generation was successfully finished.')
             return last.wait() if last is not None else None
 

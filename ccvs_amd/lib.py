@@ -30,6 +30,8 @@ GEMM_EXPORTS = ["ccvs_gemm_tiled", "ccvs_gemm_tiled_max_rows"]
 OUTPUT_EXPORTS = ["ccvs_mjpeg_workspace_bytes", "ccvs_mjpeg_encode"]
 # every symbol include/ccvs_hip_decode.h declares (the way back: baseline JPEG scans -> libjpeg-exact uint8 frames; included by ccvs_hip.h too)
 DECODE_EXPORTS = ["ccvs_mjpeg_decode_workspace_bytes", "ccvs_mjpeg_decode"]
+# every symbol include/ccvs_hip_video.h declares (the video-file datasets' input stage: the tensor transform chain in fp32; included by ccvs_hip.h too)
+VIDEO_EXPORTS = ["ccvs_ingest_f32"]
 
 
 class ConvDesc(C.Structure):
@@ -172,6 +174,7 @@ def load():
         "ccvs_code_perplexity": [vp, i32, i64, vp, vp],
         "ccvs_mjpeg_encode": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_mjpeg_decode": [vp, C.c_long, vp, vp, C.c_long, vp, i32, vp, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
+        "ccvs_ingest_f32": [vp, i32, i64, i64, i32, i32, i32, i32, i32, vp, i32, vp, vp, i64, i64, vp],
         "ccvs_ingest_u8": [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i64, i64, vp, vp],
     }
     for name, argtypes in sigs.items():

@@ -12,10 +12,38 @@ for a whole sequence, mingpt.py:232-305) is the same engine run as one prefill. 
 a libccvs_hip.so call: fused QKV GEMM, cache append, cached causal attention, projection GEMM
 with the residual add in its epilogue, LayerNorm, MLP GEMMs with GELU / residual epilogues.
 """
+import contextlib
+import gc
+import threading
+
 import torch
 import torch.nn as nn
 
 from ccvs_amd import ops
+
+_GC_PAUSE = {"lock": threading.Lock(), "depth": 0, "was_enabled": False}
+
+
+@contextlib.contextmanager
+def _no_gc_while_capturing():
+    """Dead reference cycles are collected BEFORE a stream capture begins and the automatic collector is paused (for every thread:
+    the switch is the process's) while one lasts.  A collection that lands inside a capture runs the finalizers of whatever device
+    objects the cycles hold -- the hipGraphs and cache tensors of an earlier model, for one -- and destroying those on a capturing
+    thread aborts the process inside the HIP runtime; `torch.cuda.graph` no longer collects on entry itself."""
+    p = _GC_PAUSE
+    gc.collect()
+    with p["lock"]:
+        if p["depth"] == 0:
+            p["was_enabled"] = gc.isenabled()
+            gc.disable()
+        p["depth"] += 1
+    try:
+        yield
+    finally:
+        with p["lock"]:
+            p["depth"] -= 1
+            if p["depth"] == 0 and p["was_enabled"]:
+                gc.enable()
 
 
 class GPTConfig:
@@ -639,7 +667,7 @@ class GPT(nn.Module):
             graph = torch.cuda.CUDAGraph()
             # thread_local: with torch.distributed initialised the RCCL watchdog thread issues HIP calls of its own, which the
             # default 'global' capture mode would treat as capture violations
-            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            with _no_gc_while_capturing(), torch.cuda.graph(graph, capture_error_mode="thread_local"):
                 for _ in range(steps):
                     self._decode_body(sampler)
             for k, v in state.items():   # capture does not execute; kept for clarity

@@ -1191,6 +1191,89 @@ def ingest_u8(frames, box=None, size=None, out=None, mean=None, std=None, as_u8=
     return out
 
 
+# ------------------------------------------------------------------ input stage of the video-file datasets (include/ccvs_hip_video.h)
+INGEST_PRE = {None: 0, "div255": 1, "x2m1": 2}
+# the launch form when the caller does not choose: fused up to this many RESIZING stages, staged beyond (DESIGN.md section 4.17 has the
+# timings that decide it)
+INGEST_F32_FUSED_MAX_RESIZES = 2
+
+
+def ingest_stages(hs, ws, stages):
+    """`stages` = [(box, size), ...] (box (top, left, h, w) or None: the whole input; size (Ho, Wo) or None: the box's size) for an
+    hs x ws source as rows (top, left, hc, wc, Ho, Wo); ValueError where a box leaves its stage's input."""
+    rows, h, w = [], int(hs), int(ws)
+    for k, (box, size) in enumerate(stages):
+        top, left, hc, wc = (0, 0, h, w) if box is None else (int(v) for v in box)
+        ho, wo = (hc, wc) if size is None else (int(size[0]), int(size[1]))
+        if not (0 <= top and 0 <= left and hc > 0 and wc > 0 and top + hc <= h and left + wc <= w and ho > 0 and wo > 0):
+            raise ValueError(f"ingest_f32: stage {k}: crop box {(top, left, hc, wc)} leaves its {h} x {w} input, or an empty size {(ho, wo)}")
+        rows.append((top, left, hc, wc, ho, wo))
+        h, w = ho, wo
+    return rows
+
+
+def ingest_f32(src, stages=(), out=None, pre="div255", mean=None, std=None, fused=None):
+    """The reference's TENSOR transform chain (`ccvs_ingest_f32`) on N frames: `src` uint8 [N, Hs, Ws, 3] (any
+    frame stride) or fp32 [N, C, Hs, Ws] (C 1 or 3, rows dense) on the device -> `pre` ("div255": v / 255, "x2m1": v * 2 - 1, None) ->
+    the `stages` [(box, size), ...] (1 to 3; none: a copy), each a crop and torch's `F.interpolate(size, mode="bilinear",
+    align_corners=False)` in fp32 -> (y - mean[c]) / std[c] when `mean` / `std` are given -> fp32 [N, C, Ho, Wo].  `out`: optional
+    tensor of that shape with dense rows and any frame / channel strides (`clip[b, t0:t1]`), written in place and returned.
+      fused=True   all stages in ONE launch, evaluated per output pixel: no intermediate tensor;
+      fused=False  one launch per stage through fp32 intermediates in HBM -- the same bits;
+      fused=None   fused when at most INGEST_F32_FUSED_MAX_RESIZES stages change a size, staged otherwise.
+    Runs on the current stream; nothing is synchronised."""
+    _need_gpu(src, out)
+    if pre not in INGEST_PRE:
+        raise ValueError(f"ingest_f32: pre-op {pre!r} is none of {list(INGEST_PRE)}")
+    if src.dtype == torch.uint8:
+        assert src.dim() == 4 and src.shape[-1] == 3, src.shape
+        n, hs, ws, c = src.shape[0], src.shape[1], src.shape[2], 3
+        if src.stride()[1:] != (3 * ws, 3, 1) or (n > 1 and src.stride(0) < hs * ws * 3):
+            src = src.contiguous()
+        s_n, s_c = (src.stride(0) if n > 1 else hs * ws * 3), 0
+    else:
+        assert src.dtype == torch.float32 and src.dim() == 4 and src.shape[1] in (1, 3), (src.dtype, src.shape)
+        n, c, hs, ws = src.shape
+        if not _rows_dense(src) or (c > 1 and src.stride(1) < hs * ws) or (n > 1 and src.stride(0) < hs * ws):
+            src = src.contiguous()
+        s_n, s_c = src.stride(0), src.stride(1)
+    if (mean is None) != (std is None):
+        raise ValueError("ingest_f32: mean and std go together")
+    rows = ingest_stages(hs, ws, list(stages) or [(None, None)])
+    if len(rows) > 3:
+        raise ValueError(f"ingest_f32: {len(rows)} stages, at most 3 are evaluated")
+    ho, wo = rows[-1][4:]
+    dev = src.device
+    if out is None:
+        out = torch.empty(n, c, ho, wo, dtype=torch.float32, device=dev)
+    assert out.dtype == torch.float32 and tuple(out.shape) == (n, c, ho, wo) and _rows_dense(out), (out.dtype, out.shape, out.stride())
+    assert (c == 1 or out.stride(1) >= ho * wo) and (n == 1 or out.stride(0) >= (c - 1) * out.stride(1) + ho * wo), out.stride()
+    if fused is None:
+        fused = sum(1 for r in rows if r[2:4] != r[4:6]) <= INGEST_F32_FUSED_MAX_RESIZES
+    ms = None
+    if mean is not None:
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        assert len(mean) == c and len(std) == c, (mean, std, c)
+        ms = (C.c_float * (2 * c))(*mean, *std)
+    L = _lib.load()
+
+    def launch(x, x_u8, x_sn, x_sc, h, w, pre_op, part, norm, dst):
+        flat = (C.c_int32 * (6 * len(part)))(*[v for r in part for v in r])
+        _lib.check(L.ccvs_ingest_f32(_p(x), 1 if x_u8 else 0, x_sn, x_sc, n, c, h, w, INGEST_PRE[pre_op], flat, len(part), norm,
+                                     _p(dst), dst.stride(0), dst.stride(1), _stream()), "ccvs_ingest_f32")
+
+    if fused or len(rows) == 1:
+        launch(src, src.dtype == torch.uint8, s_n, s_c, hs, ws, pre, rows, ms, out)
+        return out
+    x, x_u8, x_sn, x_sc, h, w = src, src.dtype == torch.uint8, s_n, s_c, hs, ws
+    for k, r in enumerate(rows):
+        last = k == len(rows) - 1
+        dst = out if last else torch.empty(n, c, r[4], r[5], dtype=torch.float32, device=dev)
+        launch(x, x_u8, x_sn, x_sc, h, w, pre if k == 0 else None, [r], ms if last else None, dst)
+        x, x_u8, x_sn, x_sc, h, w = dst, False, dst.stride(0), dst.stride(1), r[4], r[5]
+    return out
+
+
 # ------------------------------------------------------------------ output stage (include/ccvs_hip_output.h)
 def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None):
     """Baseline JPEG scans of uint8 frames [..., H, W, 3] on the device (`ccvs_mjpeg_encode`: libjpeg's bytes, bit for bit): returns
@@ -1247,9 +1330,11 @@ _MJPEG_STATUS = {1: "its table entry points outside the call's frames, stream, M
                  5: "bytes are left behind the last MCU, or a 0xFF that no 0x00 follows"}
 
 
-def mjpeg_decode_upload(plan):
-    """A plan of `ccvs_amd.tools.mjpeg.plan_frames` on the device: the unit table, the table records, the frames' record indices and
-    the scans go up in ONE copy (each part at the alignment `ccvs_mjpeg_decode` asks for).  Returns what `mjpeg_decode_uploaded` takes."""
+def mjpeg_decode_pack(plan):
+    """A plan of `ccvs_amd.tools.mjpeg.plan_frames` as ONE host blob (uint8 numpy): the unit table, the table records, the frames' record
+    indices and the scans, each part at the alignment `ccvs_mjpeg_decode` asks for.  Returns (meta, blob): `meta` with the blob on the
+    device under "blob" (a uint8 tensor whose first byte is 8-byte aligned) is what `mjpeg_decode_uploaded` takes -- callers that
+    batch several plans into one upload (`ccvs_amd.data.VideoLoader`) place the blobs themselves."""
     import numpy as np
     n, h, w, sampling = (int(plan[k]) for k in ("n", "h", "w", "sampling"))
     units = np.ascontiguousarray(plan["units"], dtype=np.int64).reshape(-1, 5)
@@ -1265,8 +1350,16 @@ def mjpeg_decode_upload(plan):
     blob[o_tab:o_ft] = tables
     blob[o_ft:o_ft + frame_table.nbytes] = frame_table.view(np.uint8)
     blob[o_scan:o_scan + scans.size] = scans
-    return {"n": n, "h": h, "w": w, "sampling": sampling, "blob": torch.from_numpy(blob).to("cuda"), "units_host": units, "o_tab": o_tab, "o_ft": o_ft,
-            "o_scan": o_scan, "scan_bytes": scans.size, "n_tables": tables.size // 4008}
+    return {"n": n, "h": h, "w": w, "sampling": sampling, "units_host": units, "o_tab": o_tab, "o_ft": o_ft,
+            "o_scan": o_scan, "scan_bytes": scans.size, "n_tables": tables.size // 4008}, blob
+
+
+def mjpeg_decode_upload(plan):
+    """A plan of `ccvs_amd.tools.mjpeg.plan_frames` on the device: the unit table, the table records, the frames' record indices and
+    the scans go up in ONE copy (each part at the alignment `ccvs_mjpeg_decode` asks for).  Returns what `mjpeg_decode_uploaded` takes."""
+    meta, blob = mjpeg_decode_pack(plan)
+    meta["blob"] = torch.from_numpy(blob).to("cuda")
+    return meta
 
 
 def mjpeg_decode_uploaded(up, out=None, status=None, work=None):

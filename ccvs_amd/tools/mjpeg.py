@@ -5,6 +5,9 @@
   write_avi(path, frames, fps, h, w)         RIFF 'AVI ': hdrl (avih, one strl: strh vids/MJPG + strf BITMAPINFOHEADER), a movi list of
                                              '00dc' chunks padded to even length, idx1.
   read_avi(path) -> (fps, h, w, [jpeg])      the frames of such a file, byte for byte.
+  probe_avi(path) -> (fps, h, w, n, index)   the same of ANY writer's MJPG AVI (JUNK, LIST INFO / odml / rec, other streams, idx1 from either
+                                             base, no idx1) from the headers and the index alone; it says what it refuses and why.
+  read_avi_frames(path, numbers, index)      the JPEG bytes of those frames only: one seek + read each (the video-file datasets).
   decode_frames(jpegs) -> uint8 [T, H, W, 3] with Pillow (ImportError where it is missing), on the host.
 
 The way back on the GPU (`ops.mjpeg_decode`) has its host half here -- everything up to the bytes that go up:
@@ -151,6 +154,136 @@ def read_avi(path):
     if fps is None or h is None:
         raise ValueError(f"{path}: no video stream header")
     return fps, h, w, frames
+
+
+# ---- reading other writers' files frame by frame: headers and index only, payloads by seek + read
+_REENCODE = "re-encode it once as Motion-JPEG AVI (e.g. `ffmpeg -i IN -c:v mjpeg -q:v 2 -an OUT.avi`)"
+
+
+def _head(fh, pos, n=8):
+    fh.seek(pos)
+    return fh.read(n)
+
+
+def probe_avi(path):
+    """(fps, h, w, n_frames, index) of a Motion-JPEG AVI file without reading a frame: `index` is a list of (payload offset in the file,
+    payload bytes) per video frame, from `idx1` (offsets counted from the 'movi' tag or from the file start) or, where there is none,
+    from a walk over the chunk headers of 'movi' with seeks.  JUNK chunks, LIST INFO / odml, 'LIST rec ' groups and other streams'
+    chunks (01wb) are stepped over.  ValueError, naming the file and the reason: not RIFF AVI, a RIFF length that is not the file's,
+    RIFF AVIX extensions (OpenDML), no or a non-MJPG video stream, zero-length video chunks (dropped frames: a frame number would no
+    longer mean a picture), an index that points outside 'movi'."""
+    import os
+    size = os.path.getsize(path)
+    with open(path, "rb") as fh:
+        head = fh.read(12)
+        if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"AVI ":
+            raise ValueError(f"{path}: not a RIFF AVI file ({_REENCODE})")
+        riff_end = struct.unpack_from("<I", head, 4)[0] + 8
+        if riff_end < size and _head(fh, riff_end + (riff_end & 1), 12)[8:12] == b"AVIX":
+            raise ValueError(f"{path}: RIFF AVIX extensions (an OpenDML file of several RIFF chunks) are not read; {_REENCODE}")
+        if riff_end != size:
+            raise ValueError(f"{path}: the RIFF length says {riff_end} bytes, the file has {size}")
+        fps = h = w = stream = movi = idx1 = None
+        pos = 12
+        while pos + 8 <= size:
+            tag, n = struct.unpack("<4sI", _head(fh, pos))
+            if pos + 8 + n > size:
+                raise ValueError(f"{path}: chunk {tag!r} at {pos} runs past the file")
+            if tag == b"LIST":
+                kind = fh.read(4)
+                if kind == b"hdrl":
+                    hdrl = fh.read(n - 4)
+                    number = 0
+                    try:
+                        streams = [(o2, s2) for t2, o2, s2 in _chunks(hdrl, 0, len(hdrl)) if t2 == b"LIST" and hdrl[o2:o2 + 4] == b"strl"]
+                        streams = [list(_chunks(hdrl, o2 + 4, o2 + s2)) for o2, s2 in streams]
+                    except ValueError as exc:
+                        raise ValueError(f"{path}: {exc} (inside the header list)") from None
+                    for parts in streams:
+                        strh = strf = None
+                        for t3, o3, s3 in parts:
+                            if t3 == b"strh":
+                                strh = hdrl[o3:o3 + s3]
+                            elif t3 == b"strf":
+                                strf = hdrl[o3:o3 + s3]
+                        if strh is not None and strh[:4] == b"vids" and stream is None:
+                            if strf is None or len(strh) < 28 or len(strf) < 20:
+                                raise ValueError(f"{path}: truncated video stream header")
+                            if strh[4:8].upper() != b"MJPG" and strf[16:20].upper() != b"MJPG":
+                                raise ValueError(f"{path}: the video stream is {strh[4:8]!r} / {strf[16:20]!r}, not MJPG; {_REENCODE}")
+                            scale, rate = struct.unpack_from("<II", strh, 20)
+                            if scale == 0 or rate // scale < 1:
+                                raise ValueError(f"{path}: frame rate {rate} / {scale}")
+                            fps = rate // scale
+                            w, h = struct.unpack_from("<ii", strf, 4)
+                            w, h, stream = abs(w), abs(h), number
+                        number += 1
+                elif kind == b"movi":
+                    movi = (pos + 8, pos + 8 + n)                     # from the 'movi' tag to the end of the list
+            elif tag == b"idx1":
+                idx1 = (pos + 8, n)
+            pos += 8 + n + (n & 1)
+        if stream is None:
+            raise ValueError(f"{path}: no video stream header; {_REENCODE}")
+        if movi is None:
+            raise ValueError(f"{path}: no 'movi' list")
+        tags = (b"%02ddc" % stream, b"%02ddb" % stream)
+        index = []
+        if idx1 is not None and idx1[1] >= 16:
+            fh.seek(idx1[0])
+            raw = fh.read(idx1[1] - idx1[1] % 16)
+            entries = [(off, n) for tag, _, off, n in struct.iter_unpack("<4sIII", raw) if tag in tags]
+            if entries:
+                # the base of the offsets: the 'movi' tag (the AVI specification) or the file start (some writers); the first entry's own
+                # chunk header tells which
+                want = [struct.pack("<4sI", t, entries[0][1]) for t in tags]
+                for base in (movi[0], 0):
+                    at = base + entries[0][0]
+                    if movi[0] + 4 <= at and at + 8 <= movi[1] and _head(fh, at) in want:
+                        break
+                else:
+                    raise ValueError(f"{path}: idx1 points at no video chunk, neither counted from 'movi' nor from the file start")
+                index = [(base + off + 8, n) for off, n in entries]
+        if not index:                                                  # no index: the chunk headers of 'movi', payloads skipped
+            pos = movi[0] + 4
+            while pos + 8 <= movi[1]:
+                tag, n = struct.unpack("<4sI", _head(fh, pos))
+                if tag == b"LIST":                                     # 'LIST rec ': its chunks follow its 12-byte header
+                    pos += 12
+                    continue
+                if pos + 8 + n > movi[1]:
+                    raise ValueError(f"{path}: chunk {tag!r} at {pos} runs past the 'movi' list")
+                if tag in tags:
+                    index.append((pos + 8, n))
+                pos += 8 + n + (n & 1)
+    if not index:
+        raise ValueError(f"{path}: no video frames")
+    if any(n == 0 for _, n in index):
+        k = [n for _, n in index].index(0)
+        raise ValueError(f"{path}: video chunk {k} has zero length (a dropped frame): frame numbers would not name pictures; {_REENCODE}")
+    if any(off < movi[0] + 12 or off + n > movi[1] for off, n in index):
+        raise ValueError(f"{path}: the index points outside the 'movi' list")
+    return fps, h, w, len(index), index
+
+
+def read_avi_frames(path, frame_numbers, index=None):
+    """The JPEG files (bytes) of the frames `frame_numbers` of a Motion-JPEG AVI file, in that order: one seek + read per frame,
+    nothing else of the file is read.  index: `probe_avi(path)[4]` where the caller has it."""
+    if index is None:
+        index = probe_avi(path)[4]
+    out = []
+    with open(path, "rb") as fh:
+        for k in frame_numbers:
+            k = int(k)
+            if not 0 <= k < len(index):
+                raise IndexError(f"{path}: frame {k} of {len(index)}")
+            off, n = index[k]
+            fh.seek(off)
+            data = fh.read(n)
+            if len(data) != n:
+                raise ValueError(f"{path}: frame {k} is cut short")
+            out.append(data)
+    return out
 
 
 def decode_frames(jpegs):

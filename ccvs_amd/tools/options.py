@@ -83,6 +83,13 @@ class Options:
         _flag(p, "--centered_crop")
         p.add_argument("--fixed_top_centered_zoom", type=float, default=None)
         p.add_argument("--one_every_n", type=int, default=1)
+        # the video-file datasets (tools/options.py:77-90, read by data/base_dataset.py:30-35, 58-60, 114-118, 211-216; here by
+        # ccvs_amd/data/video_dataset.py)
+        p.add_argument("--data_specs", type=str, default=None)
+        p.add_argument("--load_vid_len", type=int, default=None)
+        p.add_argument("--max_vid_step", type=int, default=1000)
+        p.add_argument("--vid_skip", type=int, default=1)
+        _flag(p, "--load_data")
         _flag(p, "--load_state")   # (the annotated-frames dataset: accepted so that the data path can refuse it by name)
         # (ccvs_amd) the teacher-forced "rec" decode of the real codes, which the reference always runs unless gen_from_img
         # (helpers/generator.py:172-189); on by default like the reference, switchable because it is not part of the

@@ -487,6 +487,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_output.h"
 /* the way back (baseline JPEG scans -> libjpeg-exact uint8 frames), additive to ABI version 6, likewise */
 #include "ccvs_hip_decode.h"
+/* the input stage of the video-file datasets (the reference's tensor transform chain: torch-bilinear stages in fp32), additive to ABI version 6, likewise */
+#include "ccvs_hip_video.h"
 
 #ifdef __cplusplus
 }
