@@ -4,6 +4,9 @@
 // an interval's bytes go depends on the sizes of all the intervals before it, so the kernel runs twice: a first pass writes every
 // interval's size, one workgroup scans the sizes into offsets (and the frames' offsets), a second pass encodes again and writes at the
 // final offsets.  No atomic decides an offset; the LDS atomics below only OR disjoint bits into shared words.
+// The kernel is a template over the sampling (include/ccvs_hip_output_sampled.h): 0 is the kernel above word
+// for word; 1 (4:2:2) and 2 (4:2:0) have MCUs of 16 x 8 / 16 x 16 pixels and 4 / 6 blocks, stage finished planes instead of raw RGB and
+// know dummy blocks.  An interval never has more than 96 blocks, so every buffer keeps its size.
 #include "common.h"
 
 #define JP_THREADS 128
@@ -76,6 +79,7 @@ struct JpegArgs {
     const uint8_t* rgb;
     long frame_stride;
     int h, w, R, mcux, nmcu, nI;   // per frame: MCUs per row, MCUs, intervals
+    int wby, hby;                  // the luminance component's width and height in blocks (subsampled forms: blocks beyond are dummies)
     long T;                        // intervals of all frames
     uint8_t* stream;
     long capacity;
@@ -194,8 +198,45 @@ __device__ __forceinline__ int code_block(const short* coef, int diff, const uns
     return pos;
 }
 
+// The two DCT passes of a block in registers and the quantiser: the DC value to `dc`, the AC coefficients in zigzag order to coef[1 .. 63].
+__device__ __forceinline__ void transform_block(int* d, const unsigned short* qd, int* dc, short* coef) {
+#pragma unroll
+    for (int r = 0; r < 8; ++r) fdct_pass<true, 1>(d + 8 * r);
+#pragma unroll
+    for (int c = 0; c < 8; ++c) fdct_pass<false, 8>(d + c);
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+        const int nat = k_zigzag[k];
+        const int q = qd[nat], v = d[nat];
+        const int m = ((v < 0 ? -v : v) + (q >> 1)) / q;
+        const int s = v < 0 ? -m : m;
+        if (k == 0) *dc = s;
+        else coef[k] = (short)s;
+    }
+}
+
+// Sampling S (1: 4:2:2, 2: 4:2:0): whether luminance block k (raster order inside the MCU) of MCU (mx, my) lies outside the component.
+template <int S>
+__device__ __forceinline__ bool dummy_block(const JpegArgs& a, int mx, int my, int k) {
+    return k < 2 * S && (2 * mx + (k & 1) >= a.wby || (S == 2 && 2 * my + (k >> 1) >= a.hby));
+}
+// ... and the block of the interval whose DC value block t of the interval carries: itself, or for a dummy the nearest real block
+// before it in its MCU (block 0 of an MCU is always real).
+template <int S>
+__device__ __forceinline__ int dc_source(const JpegArgs& a, int first, int t) {
+    constexpr int BPM = 2 * S + 2;
+    const int m = t / BPM, g = first + m, my = g / a.mcux, mx = g - my * a.mcux;
+    int k = t - m * BPM;
+    while (dummy_block<S>(a, mx, my, k)) --k;
+    return m * BPM + k;
+}
+
+template <int S>
 __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
-    __shared__ unsigned s_px[JP_MAXR * 48];               // the interval's MCUs: [MCU][row][24 bytes RGB], 6 KB
+    constexpr int BPM = S == 0 ? 3 : 2 * S + 2;           // blocks per MCU: Y Cb Cr, Y0 Y1 Cb Cr, Y00 Y01 Y10 Y11 Cb Cr
+    constexpr int VS = S == 2 ? 2 : 1;                    // luminance rows per chrominance row
+    // S = 0: the interval's MCUs as [MCU][row][24 bytes RGB]; else finished samples, [block in stream order][64 bytes]: 6 KB either way
+    __shared__ unsigned s_px[JP_MAXR * 48];
     __shared__ short s_coef[JP_MAXBLK * JP_CSTRIDE];      // quantised coefficients in zigzag order, 12.4 KB
     __shared__ unsigned s_words[JP_WORDS];                // the bit stream before byte stuffing, 19.5 KB
     __shared__ unsigned s_huff[4 * 256];
@@ -204,15 +245,17 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
     const int tid = threadIdx.x;
     for (int i = tid; i < 4 * 256; i += JP_THREADS) s_huff[i] = c_huff.t[i >> 8][i & 255];
     if (tid < 128) s_qd[tid] = a.qd[tid >> 6][tid & 63];
-    const int comp = tid % 3, mcu = tid / 3;
+    const int mcu = tid / BPM;
+    const int comp = S == 0 ? tid % 3 : (tid - mcu * BPM < BPM - 2 ? 0 : tid - mcu * BPM - (BPM - 3));
     for (long iv = blockIdx.x; iv < a.T; iv += gridDim.x) {
         const long n = iv / a.nI;
         const int ii = (int)(iv - n * a.nI);
         const int first = ii * a.R;
         const int nm = a.nmcu - first < a.R ? a.nmcu - first : a.R;   // MCUs of this interval
-        const int nb = 3 * nm;                                         // its blocks, in stream order: block t = (MCU t / 3, component t % 3)
+        const int nb = BPM * nm;                                       // its blocks, in stream order: block t = (MCU t / BPM, block t % BPM of it)
         const uint8_t* frame = a.rgb + n * a.frame_stride;
         // 1. the MCUs' pixels, a dword at a time; rows below the frame and pixels right of it replicate the last row / pixel
+        if constexpr (S == 0)
         for (int it = tid; it < nm * 48; it += JP_THREADS) {
             const int m = it / 48, rem = it - m * 48, row = rem / 6, k = rem - row * 6;
             const int g = first + m, my = g / a.mcux, mx = g - my * a.mcux;
@@ -233,8 +276,60 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
             }
             s_px[it] = v;
         }
+        // 1s. subsampled: a lane per chrominance sample.  It converts the 2 x VS pixels under it once, stores their Y and the box-filtered
+        // Cb and Cr (bias by the output column's parity).  Columns right of the frame replicate the last one.  Rows: luminance replicates
+        // the last row; chrominance replicates the last row up to a multiple of VS BEFORE the filter and the last FILTERED row below that.
+        if constexpr (S != 0) {
+            uint8_t* planes = (uint8_t*)s_px;
+            const int last_crow = (a.h + VS - 1) / VS - 1;
+            for (int it = tid; it < nm * 64; it += JP_THREADS) {
+                const int m = it >> 6, cy = (it >> 3) & 7, cx = it & 7;
+                const int g = first + m, my = g / a.mcux, mx = g - my * a.mcux;
+                const int crow = my * 8 + cy < last_crow ? my * 8 + cy : last_crow;
+                int cb = 0, cr = 0;
+#pragma unroll
+                for (int j = 0; j < VS; ++j) {
+                    const int yl = VS * cy + j;                                                  // the luminance row inside the MCU
+                    const int ysrc = my * 8 * VS + yl < a.h ? my * 8 * VS + yl : a.h - 1;
+                    const int csrc = VS * crow + j < a.h ? VS * crow + j : a.h - 1;
+#pragma unroll
+                    for (int i = 0; i < 2; ++i) {
+                        const int xl = 2 * cx + i;
+                        const int x = mx * 16 + xl < a.w ? mx * 16 + xl : a.w - 1;
+                        const uint8_t* q = frame + ((long)csrc * a.w + x) * 3;
+                        int r = q[0], gg = q[1], b = q[2];
+                        cb += (-11059 * r - 21709 * gg + 32768 * b + (128 << 16) + 32767) >> 16;
+                        cr += (32768 * r - 27439 * gg - 5329 * b + (128 << 16) + 32767) >> 16;
+                        if (ysrc != csrc) {
+                            q = frame + ((long)ysrc * a.w + x) * 3;
+                            r = q[0], gg = q[1], b = q[2];
+                        }
+                        const int kb = (S == 2 ? (yl >> 3) * 2 : 0) + (xl >> 3);
+                        planes[(m * BPM + kb) * 64 + (yl & 7) * 8 + (xl & 7)] = (uint8_t)((19595 * r + 38470 * gg + 7471 * b + 32768) >> 16);
+                    }
+                }
+                const int bias = S == 2 ? 1 + (cx & 1) : (cx & 1);
+                planes[(m * BPM + BPM - 2) * 64 + cy * 8 + cx] = (uint8_t)((cb + bias) >> S);
+                planes[(m * BPM + BPM - 1) * 64 + cy * 8 + cx] = (uint8_t)((cr + bias) >> S);
+            }
+        }
         __syncthreads();
+        // 2s. subsampled: a lane per block reads its 64 finished samples; a dummy block has no AC coefficients and is not transformed
+        if constexpr (S != 0)
+        if (tid < nb) {
+            const int g = first + mcu, my = g / a.mcux, mx = g - my * a.mcux;
+            if (dummy_block<S>(a, mx, my, tid - mcu * BPM)) {
+                for (int k = 1; k < 64; ++k) s_coef[tid * JP_CSTRIDE + k] = 0;
+            } else {
+                const uint8_t* p = (const uint8_t*)s_px + tid * 64;
+                int d[64];
+#pragma unroll
+                for (int i = 0; i < 64; ++i) d[i] = (int)p[i] - 128;
+                transform_block(d, s_qd + (comp == 0 ? 0 : 64), &s_dc[tid], s_coef + tid * JP_CSTRIDE);
+            }
+        }
         // 2. a lane per block: colour conversion of its component, the two DCT passes in registers, the quantiser
+        if constexpr (S == 0)
         if (tid < nb) {
             const int cr = comp == 0 ? 19595 : (comp == 1 ? -11059 : 32768);
             const int cg = comp == 0 ? 38470 : (comp == 1 ? -21709 : -27439);
@@ -244,20 +339,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
             int d[64];
 #pragma unroll
             for (int i = 0; i < 64; ++i) d[i] = ((cr * (int)p[3 * i] + cg * (int)p[3 * i + 1] + cb * (int)p[3 * i + 2] + c0) >> 16) - 128;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) fdct_pass<true, 1>(d + 8 * r);
-#pragma unroll
-            for (int c = 0; c < 8; ++c) fdct_pass<false, 8>(d + c);
-            const unsigned short* qd = s_qd + (comp == 0 ? 0 : 64);
-#pragma unroll
-            for (int k = 0; k < 64; ++k) {
-                const int nat = k_zigzag[k];
-                const int q = qd[nat], v = d[nat];
-                const int m = ((v < 0 ? -v : v) + (q >> 1)) / q;
-                const int s = v < 0 ? -m : m;
-                if (k == 0) s_dc[tid] = s;
-                else s_coef[tid * JP_CSTRIDE + k] = (short)s;
-            }
+            transform_block(d, s_qd + (comp == 0 ? 0 : 64), &s_dc[tid], s_coef + tid * JP_CSTRIDE);
         }
         __syncthreads();
         // 3. every block's length in bits
@@ -265,7 +347,15 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
         const unsigned* dc = s_huff + (comp == 0 ? 0 : 256);
         const unsigned* ac = s_huff + (comp == 0 ? 512 : 768);
         if (tid < nb) {
-            diff = s_dc[tid] - (tid >= 3 ? s_dc[tid - 3] : 0);
+            // the block before this one in its component: 3 blocks back for Y Cb Cr; subsampled, the luminance block before (the last one
+            // of the MCU before lies 3 back as well) or the MCU before's chrominance block -- each read through dc_source, dummies included
+            if constexpr (S == 0) {
+                diff = s_dc[tid] - (tid >= 3 ? s_dc[tid - 3] : 0);
+            } else {
+                const int kb = tid - mcu * BPM;
+                const int prev = comp != 0 ? tid - BPM : (kb > 0 ? tid - 1 : tid - 3);
+                diff = s_dc[dc_source<S>(a, first, tid)] - (prev >= 0 ? s_dc[dc_source<S>(a, first, prev)] : 0);
+            }
             s_cnt[tid] = code_block<false>(s_coef + tid * JP_CSTRIDE, diff, dc, ac, nullptr, 0);
         }
         __syncthreads();
@@ -353,31 +443,37 @@ __global__ __launch_bounds__(JP_SCAN_THREADS) void jpeg_scan_kernel(const int* s
     if (tid == 0) offsets[T / nI] = total;
 }
 
-static inline long jpeg_intervals(int n, int h, int w, int R) {
-    const long nmcu = (long)((w + 7) / 8) * ((h + 7) / 8);
+// MCUs are 8 x 8, 16 x 8 or 16 x 16 pixels; an interval holds at most JP_MAXBLK blocks: 32, 24 or 16 MCUs
+static inline int jpeg_max_restart(int sampling) { return JP_MAXBLK / (sampling == 0 ? 3 : 2 * sampling + 2); }
+static inline long jpeg_intervals(int n, int h, int w, int sampling, int R) {
+    const int mw = sampling ? 16 : 8, mh = sampling == 2 ? 16 : 8;
+    const long nmcu = (long)((w + mw - 1) / mw) * ((h + mh - 1) / mh);
     return (long)n * ((nmcu + R - 1) / R);
 }
-static inline bool jpeg_shape_ok(int n, int h, int w, int R) {
-    return n >= 1 && h >= 1 && h <= 65535 && w >= 1 && w <= 65535 && R >= 1 && R <= JP_MAXR;
+static inline bool jpeg_shape_ok(int n, int h, int w, int sampling, int R) {
+    return n >= 1 && h >= 1 && h <= 65535 && w >= 1 && w <= 65535 && sampling >= 0 && sampling <= 2 && R >= 1 && R <= jpeg_max_restart(sampling);
 }
-
-extern "C" size_t ccvs_mjpeg_workspace_bytes(int n, int h, int w, int restart_mcus) {
-    if (!jpeg_shape_ok(n, h, w, restart_mcus)) return 0;
-    const size_t T = (size_t)jpeg_intervals(n, h, w, restart_mcus);
+static inline size_t jpeg_workspace(int n, int h, int w, int sampling, int R) {
+    if (!jpeg_shape_ok(n, h, w, sampling, R)) return 0;
+    const size_t T = (size_t)jpeg_intervals(n, h, w, sampling, R);
     return 8 * T + ((4 * T + 7) & ~(size_t)7);   // long ioff[T], then int sizes[T]
 }
 
-extern "C" int ccvs_mjpeg_encode(const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int restart_mcus, uint8_t* stream,
-                                 long capacity, long* offsets, void* workspace, void* hip_stream) {
-    CCVS_REQUIRE(quality >= 1 && quality <= 100, "ccvs_mjpeg_encode: quality %d outside 1 .. 100", quality);
-    CCVS_REQUIRE(restart_mcus >= 1 && restart_mcus <= JP_MAXR, "ccvs_mjpeg_encode: restart interval %d outside 1 .. %d MCUs", restart_mcus, JP_MAXR);
-    CCVS_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "ccvs_mjpeg_encode: frame size %d x %d outside 1 .. 65535", h, w);
-    CCVS_REQUIRE(n >= 1 && frame_stride >= 0 && capacity >= 0, "ccvs_mjpeg_encode: no frames, or a negative frame stride or capacity");
-    CCVS_REQUIRE(rgb && offsets && workspace && (stream || capacity == 0), "ccvs_mjpeg_encode: null frames, stream, offsets or workspace");
+// `who`: the entry point's name for the messages; `sampling` has been checked by the caller.
+static int jpeg_encode(const char* who, const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int sampling, int restart_mcus,
+                       uint8_t* stream, long capacity, long* offsets, void* workspace, void* hip_stream) {
+    const int maxr = jpeg_max_restart(sampling);
+    CCVS_REQUIRE(quality >= 1 && quality <= 100, "%s: quality %d outside 1 .. 100", who, quality);
+    CCVS_REQUIRE(restart_mcus >= 1 && restart_mcus <= maxr, "%s: restart interval %d outside 1 .. %d MCUs", who, restart_mcus, maxr);
+    CCVS_REQUIRE(h >= 1 && h <= 65535 && w >= 1 && w <= 65535, "%s: frame size %d x %d outside 1 .. 65535", who, h, w);
+    CCVS_REQUIRE(n >= 1 && frame_stride >= 0 && capacity >= 0, "%s: no frames, or a negative frame stride or capacity", who);
+    CCVS_REQUIRE(rgb && offsets && workspace && (stream || capacity == 0), "%s: null frames, stream, offsets or workspace", who);
+    const int mw = sampling ? 16 : 8, mh = sampling == 2 ? 16 : 8;
     JpegArgs a;
     a.rgb = rgb; a.frame_stride = frame_stride;
-    a.h = h; a.w = w; a.R = restart_mcus; a.mcux = (w + 7) / 8;
-    const long nmcu = (long)a.mcux * ((h + 7) / 8);
+    a.h = h; a.w = w; a.R = restart_mcus; a.mcux = (w + mw - 1) / mw;
+    a.wby = (w + 7) / 8; a.hby = (h + 7) / 8;
+    const long nmcu = (long)a.mcux * ((h + mh - 1) / mh);
     a.nmcu = (int)nmcu;                                  // <= 8192^2
     a.nI = (int)((nmcu + restart_mcus - 1) / restart_mcus);
     a.T = (long)n * a.nI;
@@ -394,11 +490,31 @@ extern "C" int ccvs_mjpeg_encode(const uint8_t* rgb, long frame_stride, int n, i
             a.qd[t][i] = (unsigned short)(q << 3);
         }
     const unsigned grid = limited_grid(a.T, hip_stream, 8);
+    void (*const kernel)(JpegArgs) = sampling == 0 ? jpeg_interval_kernel<0> : (sampling == 1 ? jpeg_interval_kernel<1> : jpeg_interval_kernel<2>);
     a.write = 0;
-    hipLaunchKernelGGL(jpeg_interval_kernel, dim3(grid), dim3(JP_THREADS), 0, (hipStream_t)hip_stream, a);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(JP_THREADS), 0, (hipStream_t)hip_stream, a);
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(JP_SCAN_THREADS), 0, (hipStream_t)hip_stream, a.sizes, ioff, offsets, a.T, a.nI);
     a.write = 1;
-    hipLaunchKernelGGL(jpeg_interval_kernel, dim3(grid), dim3(JP_THREADS), 0, (hipStream_t)hip_stream, a);
-    CCVS_CHECK_LAUNCH("ccvs_mjpeg_encode");
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(JP_THREADS), 0, (hipStream_t)hip_stream, a);
+    CCVS_CHECK_LAUNCH(who);
     return CCVS_OK;
+}
+
+extern "C" size_t ccvs_mjpeg_workspace_bytes(int n, int h, int w, int restart_mcus) { return jpeg_workspace(n, h, w, 0, restart_mcus); }
+
+extern "C" int ccvs_mjpeg_encode(const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int restart_mcus, uint8_t* stream,
+                                 long capacity, long* offsets, void* workspace, void* hip_stream) {
+    return jpeg_encode("ccvs_mjpeg_encode", rgb, frame_stride, n, h, w, quality, 0, restart_mcus, stream, capacity, offsets, workspace, hip_stream);
+}
+
+// ---- include/ccvs_hip_output_sampled.h
+extern "C" size_t ccvs_mjpeg_sampled_workspace_bytes(int n, int h, int w, int sampling, int restart_mcus) {
+    return jpeg_workspace(n, h, w, sampling, restart_mcus);
+}
+
+extern "C" int ccvs_mjpeg_encode_sampled(const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int sampling, int restart_mcus,
+                                         uint8_t* stream, long capacity, long* offsets, void* workspace, void* hip_stream) {
+    CCVS_REQUIRE(sampling >= 0 && sampling <= 2, "ccvs_mjpeg_encode_sampled: sampling %d is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)", sampling);
+    return jpeg_encode("ccvs_mjpeg_encode_sampled", rgb, frame_stride, n, h, w, quality, sampling, restart_mcus, stream, capacity, offsets, workspace,
+                       hip_stream);
 }

@@ -596,7 +596,8 @@ class Generator:
     def save_results(self, out, global_iter):
         bs = out["real"].shape[0]
         fmt = getattr(self.opt, "video_format", "auto")
-        how = dict(video_format=None if fmt == "auto" else fmt, quality=getattr(self.opt, "video_quality", 90), return_clip=False)
+        how = dict(video_format=None if fmt == "auto" else fmt, quality=getattr(self.opt, "video_quality", 90), return_clip=False,
+                   subsampling=getattr(self.opt, "video_subsampling", "444"))
         for name in ("real", "fake", "rec", "blur"):                       # generator.py:191-212
             item = out.get(name)
             if item is None:
@@ -707,19 +708,25 @@ class _ResultWriter:
                 self.error = exc
 
 
+_SUBSAMPLING = {"444": 0, "422": 1, "420": 2}     # --video_subsampling -> the encoder's sampling code
+
+
 def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, span, dataset, state=None, cat=None, idx=None,
-                     is_layout=False, video_format=None, quality=90, return_clip=True):
+                     is_layout=False, video_format=None, quality=90, return_clip=True, subsampling="444"):
     """helpers/generator.py:285-333.  The clamp / rescale / uint8 / channels-last pack runs on the GPU.  video_format:
       None    mp4 when torchvision is importable, else .npy uint8 [T,H,W,3];
       "npy"   the arrays, whatever imports;
       "avi"   Motion-JPEG AVI (`ccvs_amd.tools.mjpeg`): the packed clip is JPEG-encoded on the device at `quality` (`ops.mjpeg_encode`,
-              libjpeg's bytes) and the compressed scans are what is copied out for the files.
+              libjpeg's bytes) and the compressed scans are what is copied out for the files.  subsampling: "444" (full chrominance),
+              "422" or "420" -- the chrominance sampling of these files; the other formats do not look at it.
     Returns the uint8 clip on the host; `return_clip=False` lets the "avi" form skip that copy where no state marker needs it (then
     only the compressed scans cross to the host, and None is returned)."""
     if is_layout:
         raise NotImplementedError("layout colour maps are not on the MI355X path (SURVEY 8f)")
     if video_format not in (None, "npy", "avi"):
         raise ValueError(f"save_video_batch: video_format {video_format!r} is none of None, 'npy', 'avi'")
+    if subsampling not in _SUBSAMPLING:
+        raise ValueError(f"save_video_batch: subsampling {subsampling!r} is none of '444', '422', '420'")
     if normalize and imagenet_norm:
         u8 = ops.pack_u8_norm(vid, (0.229, 0.224, 0.225), (0.485, 0.456, 0.406))   # generator.py:303-305, same op order
     elif normalize:
@@ -748,8 +755,9 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
     elif video_format == "avi":
         from ccvs_amd.tools import mjpeg
         t, (h, w) = u8.size(1), u8.shape[2:4]
-        scans, off = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), quality)
-        head = mjpeg.jpeg_header(h, w, quality)
+        sampling = _SUBSAMPLING[subsampling]
+        scans, off = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), quality, sampling=sampling)
+        head = mjpeg.jpeg_header(h, w, quality, sampling=sampling)
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'

@@ -32,6 +32,8 @@ OUTPUT_EXPORTS = ["ccvs_mjpeg_workspace_bytes", "ccvs_mjpeg_encode"]
 DECODE_EXPORTS = ["ccvs_mjpeg_decode_workspace_bytes", "ccvs_mjpeg_decode"]
 # every symbol include/ccvs_hip_video.h declares (the video-file datasets' input stage: the tensor transform chain in fp32; included by ccvs_hip.h too)
 VIDEO_EXPORTS = ["ccvs_ingest_f32"]
+# every symbol include/ccvs_hip_output_sampled.h declares (the output stage writing 4:2:2 and 4:2:0 as well; included by ccvs_hip.h too)
+OUTPUT_SAMPLED_EXPORTS = ["ccvs_mjpeg_sampled_workspace_bytes", "ccvs_mjpeg_encode_sampled"]
 
 
 class ConvDesc(C.Structure):
@@ -113,6 +115,8 @@ def load():
     lib.ccvs_gemm_tiled_max_rows.argtypes = []
     lib.ccvs_mjpeg_workspace_bytes.restype = C.c_size_t
     lib.ccvs_mjpeg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ccvs_mjpeg_sampled_workspace_bytes.restype = C.c_size_t
+    lib.ccvs_mjpeg_sampled_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_mjpeg_decode_workspace_bytes.restype = C.c_size_t
     lib.ccvs_mjpeg_decode_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_gpt_program_bytes.restype = C.c_int64
@@ -173,6 +177,7 @@ def load():
         "ccvs_vq_stats": [vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp],
         "ccvs_code_perplexity": [vp, i32, i64, vp, vp],
         "ccvs_mjpeg_encode": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
+        "ccvs_mjpeg_encode_sampled": [vp, C.c_long, i32, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_mjpeg_decode": [vp, C.c_long, vp, vp, C.c_long, vp, i32, vp, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_ingest_f32": [vp, i32, i64, i64, i32, i32, i32, i32, i32, vp, i32, vp, vp, i64, i64, vp],
         "ccvs_ingest_u8": [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i64, i64, vp, vp],

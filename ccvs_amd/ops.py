@@ -1275,15 +1275,17 @@ def ingest_f32(src, stages=(), out=None, pre="div255", mean=None, std=None, fuse
 
 
 # ------------------------------------------------------------------ output stage (include/ccvs_hip_output.h)
-def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None):
+def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None, sampling=0):
     """Baseline JPEG scans of uint8 frames [..., H, W, 3] on the device (`ccvs_mjpeg_encode`: libjpeg's bytes, bit for bit): returns
     (stream uint8 [capacity], offsets int64 [n + 1]), both on the device -- frame i's scan is stream[offsets[i]:offsets[i + 1]].
     Leading axes are flattened in order; rows and pixels must be dense, a frame axis of any regular stride is passed on as it is
-    (`clip[:, 1::2]` of a contiguous clip is not copied).  restart_mcus: the restart interval in MCUs, 1 .. 32 (None: one row of
-    MCUs, 32 at the most).  capacity: bytes of `stream` (None: the raw size of the frames); the offsets are complete also when
+    (`clip[:, 1::2]` of a contiguous clip is not copied).  sampling: 0 = 4:4:4 (the default), 1 = 4:2:2, 2 = 4:2:0 -- the
+    subsampled forms go through `ccvs_mjpeg_encode_sampled` (include/ccvs_hip_output_sampled.h), libjpeg's bytes as well.  restart_mcus:
+    the restart interval in MCUs of the sampling's size (8 x 8, 16 x 8, 16 x 16 pixels), 1 .. 32 / 24 / 16 (None: one row of MCUs,
+    capped at that limit).  capacity: bytes of `stream` (None: the raw size of the frames); the offsets are complete also when
     offsets[n] > capacity, nothing at or beyond `capacity` is written, and the CALLER runs again with a larger one once it has
     the offsets on the host (`mjpeg_encode_to_host` does).  out: optional uint8 stream to write into (its length is the capacity).
-    `ccvs_amd.tools.mjpeg.jpeg_header(h, w, quality, restart_mcus)` + scan + EOI is a JPEG file.  Runs on the current stream; nothing
+    `ccvs_amd.tools.mjpeg.jpeg_header(h, w, quality, restart_mcus, sampling)` + scan + EOI is a JPEG file.  Runs on the current stream; nothing
     is synchronised."""
     _need_gpu(u8, out)
     assert u8.dtype == torch.uint8 and u8.dim() >= 3 and u8.shape[-1] == 3, (u8.dtype, u8.shape)
@@ -1297,7 +1299,11 @@ def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None):
         except RuntimeError:
             frames = frames.reshape(-1, h, w, 3)
     n = int(frames.shape[0])
-    r = min((w + 7) // 8, 32) if restart_mcus is None else int(restart_mcus)
+    sampling = int(sampling)
+    if sampling not in (0, 1, 2):
+        raise ValueError(f"mjpeg_encode: sampling {sampling} is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)")
+    mw = 16 if sampling else 8
+    r = min((w + mw - 1) // mw, (32, 24, 16)[sampling]) if restart_mcus is None else int(restart_mcus)
     if out is not None:
         assert out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous() and capacity in (None, out.numel()), (out.dtype, out.shape)
         capacity = out.numel()
@@ -1307,20 +1313,26 @@ def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None):
     dev = u8.device
     stream = out if out is not None else torch.empty(int(capacity), dtype=torch.uint8, device=dev)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    work = torch.empty(max(int(L.ccvs_mjpeg_workspace_bytes(n, h, w, r)), 8), dtype=torch.uint8, device=dev)
-    _lib.check(L.ccvs_mjpeg_encode(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), r, _p(stream), int(capacity),
-                                   _p(offsets), _p(work), _stream()), "ccvs_mjpeg_encode")
+    if sampling == 0:
+        work = torch.empty(max(int(L.ccvs_mjpeg_workspace_bytes(n, h, w, r)), 8), dtype=torch.uint8, device=dev)
+        _lib.check(L.ccvs_mjpeg_encode(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), r, _p(stream), int(capacity),
+                                       _p(offsets), _p(work), _stream()), "ccvs_mjpeg_encode")
+    else:
+        work = torch.empty(max(int(L.ccvs_mjpeg_sampled_workspace_bytes(n, h, w, sampling, r)), 8), dtype=torch.uint8, device=dev)
+        _lib.check(L.ccvs_mjpeg_encode_sampled(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), sampling, r, _p(stream),
+                                               int(capacity), _p(offsets), _p(work), _stream()), "ccvs_mjpeg_encode_sampled")
     return stream, offsets
 
 
-def mjpeg_encode_to_host(u8, quality=90, restart_mcus=None):
-    """`mjpeg_encode`, then the scans on the host: (bytes of all scans, list of n + 1 offsets).  The first run's stream has the
+def mjpeg_encode_to_host(u8, quality=90, restart_mcus=None, sampling=0):
+    """`mjpeg_encode` (sampling: 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0), then the scans on the host: (bytes of all scans, list of n + 1
+    offsets).  The first run's stream has the
     frames' raw size; where the scans are larger than that (noise at quality 100) the offsets say by how much and a second run with
     that capacity is exact.  What crosses to the host is the offsets and the compressed bytes, not the stream's capacity."""
-    stream, offsets = mjpeg_encode(u8, quality, restart_mcus)
+    stream, offsets = mjpeg_encode(u8, quality, restart_mcus, sampling=sampling)
     off = offsets.cpu().tolist()
     if off[-1] > stream.numel():
-        stream, _ = mjpeg_encode(u8, quality, restart_mcus, capacity=off[-1])
+        stream, _ = mjpeg_encode(u8, quality, restart_mcus, capacity=off[-1], sampling=sampling)
     return stream[:off[-1]].cpu().numpy().tobytes(), off
 
 

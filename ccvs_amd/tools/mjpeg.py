@@ -1,7 +1,8 @@
 """Motion-JPEG AVI files around the scans `ops.mjpeg_encode` writes.  Host only: no torch, no GPU.
 
-  jpeg_header(h, w, quality, restart_mcus)   the bytes in front of a frame's scan: SOI, DQT x 2, SOF0 (8 bit, three components sampled
-                                             1 x 1), DHT x 4 (the Annex K tables), DRI, SOS.  header + scan + EOI is a JPEG file.
+  jpeg_header(h, w, quality, restart_mcus,   the bytes in front of a frame's scan: SOI, DQT x 2, SOF0 (8 bit, three components; luminance
+              sampling)                      sampled 1 x 1, 2 x 1 or 2 x 2 for sampling 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0, chrominance 1 x 1),
+                                             DHT x 4 (the Annex K tables), DRI, SOS.  header + scan + EOI is a JPEG file.
   write_avi(path, frames, fps, h, w)         RIFF 'AVI ': hdrl (avih, one strl: strh vids/MJPG + strf BITMAPINFOHEADER), a movi list of
                                              '00dc' chunks padded to even length, idx1.
   read_avi(path) -> (fps, h, w, [jpeg])      the frames of such a file, byte for byte.
@@ -49,9 +50,17 @@ HUFF = {
 }
 
 
-def default_restart(w):
-    """The encoder's default restart interval in MCUs: one row of MCUs, 32 at the most."""
-    return min((int(w) + 7) // 8, 32)
+MAX_RESTART = (32, 24, 16)    # per sampling 0 / 1 / 2: the encoder's interval holds 96 blocks, an MCU has 3 / 4 / 6
+_Y_FACTORS = (0x11, 0x21, 0x22)
+
+
+def default_restart(w, sampling=0):
+    """The encoder's default restart interval in MCUs: one row of MCUs (8 pixels wide in 4:4:4, 16 in 4:2:2 and 4:2:0), capped at the
+    sampling's limit of 32 / 24 / 16."""
+    if sampling not in (0, 1, 2):
+        raise ValueError(f"default_restart: sampling {sampling!r} is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)")
+    mw = 16 if sampling else 8
+    return min((int(w) + mw - 1) // mw, MAX_RESTART[sampling])
 
 
 def quant_tables(quality):
@@ -67,16 +76,19 @@ def _segment(marker, payload):
     return bytes([0xFF, marker]) + struct.pack(">H", len(payload) + 2) + payload
 
 
-def jpeg_header(h, w, quality, restart_mcus=None):
-    """Everything in front of the scan of an h x w frame encoded at `quality` with a restart interval of `restart_mcus` MCUs."""
+def jpeg_header(h, w, quality, restart_mcus=None, sampling=0):
+    """Everything in front of the scan of an h x w frame encoded at `quality` with a restart interval of `restart_mcus` MCUs (of the
+    sampling's size; None: `default_restart(w, sampling)`).  sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0."""
     h, w = int(h), int(w)
-    r = default_restart(w) if restart_mcus is None else int(restart_mcus)
-    if not (1 <= h <= 65535 and 1 <= w <= 65535 and 1 <= r <= 32):
+    if sampling not in (0, 1, 2):
+        raise ValueError(f"jpeg_header: sampling {sampling!r} is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)")
+    r = default_restart(w, sampling) if restart_mcus is None else int(restart_mcus)
+    if not (1 <= h <= 65535 and 1 <= w <= 65535 and 1 <= r <= MAX_RESTART[sampling]):
         raise ValueError(f"jpeg_header: size {h} x {w} or restart interval {r} out of range")
     out = b"\xff\xd8"
     for t, table in enumerate(quant_tables(quality)):
         out += _segment(0xDB, bytes([t]) + bytes(table[k] for k in ZIGZAG))
-    out += _segment(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, 0x11, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    out += _segment(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, _Y_FACTORS[sampling], 0, 2, 0x11, 1, 3, 0x11, 1]))
     for key, (bits, vals) in HUFF.items():
         out += _segment(0xC4, bytes([key]) + bits + vals)
     out += _segment(0xDD, struct.pack(">H", r))

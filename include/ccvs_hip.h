@@ -489,6 +489,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_decode.h"
 /* the input stage of the video-file datasets (the reference's tensor transform chain: torch-bilinear stages in fp32), additive to ABI version 6, likewise */
 #include "ccvs_hip_video.h"
+/* the output stage with chrominance subsampling (4:2:2 and 4:2:0 scans, libjpeg-exact), additive to ABI version 6, likewise */
+#include "ccvs_hip_output_sampled.h"
 
 #ifdef __cplusplus
 }
