@@ -1075,6 +1075,69 @@ def resize_bilinear(x, size):
     return out
 
 
+# ------------------------------------------------------------------ LPIPS (include/ccvs_hip_lpips.h)
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+def lpips_prep(x, out=None, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """(x - mean[c]) / std[c] of [N, 3, H, W] fp32 images, a true fp32 division like torch's (`ccvs_lpips_prep`).  out: optional
+    contiguous fp32 [N, 3, H, W] tensor to write into (default: a new one)."""
+    _need_gpu(x, out)
+    assert x.dim() == 4 and x.shape[1] == 3 and x.dtype == torch.float32 and x.numel() > 0, (x.shape, x.dtype)
+    x = x.contiguous()
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == torch.float32 and out.is_contiguous() and out.data_ptr() != x.data_ptr(), (out.shape, x.shape)
+    m3, s3 = (C.c_float * 3)(*[float(v) for v in mean]), (C.c_float * 3)(*[float(v) for v in std])
+    _lib.check(_lib.load().ccvs_lpips_prep(_p(x), _p(out), x.shape[0] * 3, x.shape[2] * x.shape[3], m3, s3, _stream()), "ccvs_lpips_prep")
+    return out
+
+
+def relu_(x):
+    """nn.ReLU in place on a dense fp32 tensor (`ccvs_relu_`); a NaN stays a NaN.  Returns x."""
+    _need_gpu(x)
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0, (x.dtype, x.shape, x.stride())
+    _lib.check(_lib.load().ccvs_relu_(_p(x), x.numel(), _stream()), "ccvs_relu_")
+    return x
+
+
+def relu_maxpool2(x, out=None):
+    """nn.MaxPool2d(2, 2)(nn.ReLU()(x)) of [..., H, W] fp32 in one read (`ccvs_relu_maxpool2`): floor mode, a NaN in a window comes
+    out.  out: optional contiguous fp32 [..., H // 2, W // 2] tensor to write into."""
+    _need_gpu(x, out)
+    assert x.dtype == torch.float32 and x.dim() >= 2 and x.shape[-2] >= 2 and x.shape[-1] >= 2 and x.numel() > 0, (x.dtype, x.shape)
+    x = x.contiguous()
+    h, w = x.shape[-2:]
+    if out is None:
+        out = torch.empty(*x.shape[:-2], h // 2, w // 2, dtype=torch.float32, device=x.device)
+    assert out.shape == (*x.shape[:-2], h // 2, w // 2) and out.dtype == torch.float32 and out.is_contiguous(), (out.shape, x.shape)
+    _lib.check(_lib.load().ccvs_relu_maxpool2(_p(x), _p(out), x.numel() // (h * w), h, w, _stream()), "ccvs_relu_maxpool2")
+    return out
+
+
+def lpips_layer(f, w, relu=True, out=None, accumulate=False):
+    """The LPIPS distance of one tapped layer (`ccvs_lpips_layer`).  f: [2 M, C, ...] fp32, the features (relu=True: the pre-activations,
+    ReLU applied on read) of M images x followed by those of the M images y; w: the layer's linear head, C fp32 values.  Returns float64
+    [M]: per pair the mean over the positions of sum_c w[c] (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2, float64 inside, the same
+    bits on every run.  out: float64 [M] to write into; accumulate=True adds to what it holds (the sum over the layers)."""
+    _need_gpu(f, w, out)
+    assert f.dim() >= 2 and f.dtype == torch.float32 and f.shape[0] % 2 == 0 and f.numel() > 0, (f.shape, f.dtype)
+    f = f.contiguous()
+    m, c = f.shape[0] // 2, f.shape[1]
+    hw = f[0, 0].numel()
+    w = w.reshape(-1).contiguous()
+    assert w.dtype == torch.float32 and w.numel() == c, (w.shape, w.dtype, c)
+    if out is None:
+        assert not accumulate
+        out = torch.empty(m, dtype=torch.float64, device=f.device)
+    assert out.shape == (m,) and out.dtype == torch.float64 and out.is_contiguous(), (out.shape, out.dtype, m)
+    L = _lib.load()
+    ws = torch.empty(int(L.ccvs_lpips_layer_workspace_bytes(m, hw)), dtype=torch.uint8, device=f.device)   # (0 bytes for M > 65535: the call refuses)
+    _lib.check(L.ccvs_lpips_layer(_p(f), _p(w), _p(out), _p(ws), m, c, hw, int(bool(relu)), int(bool(accumulate)), _stream()), "ccvs_lpips_layer")
+    return out
+
+
 def pack_u8(vid, lo=-1.0, hi=1.0, out=None):
     """[..., 3, H, W] fp32 -> [..., H, W, 3] uint8 (helpers/generator.py:306-309).  out: optional contiguous uint8 [..., H, W, 3]
     tensor to write into (default: a new one)."""

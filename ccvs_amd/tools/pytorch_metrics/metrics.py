@@ -16,11 +16,16 @@ Same function names and argument meaning as the reference:
                       `resize` other than None raises NotImplementedError (the reference's is OpenCV INTER_AREA, not reproduced).
   get_video_files, get_folder(s), print_scores, main, and the argparse block      metrics.py:92-186:
                       python -m ccvs_amd.tools.pytorch_metrics.metrics --exp_tag TAG [--real_tag --real_folder --fake_folder
-                      --num_folds --idx --print_256] prints the reference's lines for results/*TAG/{real,fake}; the LPIPS lines say
-                      "not available (needs pretrained weights)".
-  get_lpips           NOT available: piq.LPIPS is a pretrained VGG16 plus learned linear heads whose weights are downloaded;
-                      no such file exists offline and the network is not on the synthesis path.  Raises NotImplementedError;
-                      the aggregate functions return None in its place.
+                      --num_folds --idx --print_256 --lpips_weights] prints the reference's lines for results/*TAG/{real,fake};
+                      without LPIPS weights the LPIPS lines say "not available (needs pretrained weights)".
+  get_lpips(x, y)     piq.LPIPS(reduction='mean')(x, y)                                     metrics.py:12-13 -> lpips.LPIPS
+                      piq downloads a pretrained VGG16 and learned linear heads; nothing is downloaded here and no weights are in
+                      the repository, so the user names a file: `set_lpips_weights(path | dict | None)`, the environment variable
+                      CCVS_LPIPS_WEIGHTS (read on first use), or `--lpips_weights PATH` of the command.  The file is what
+                      `python -m ccvs_amd.tools.pytorch_metrics.lpips --vgg ... --lin ... --out ...` writes (lpips.py has the
+                      algorithm).  Without weights get_lpips raises NotImplementedError, before it looks at its arguments, and the
+                      aggregate functions return None in its place.  Parity with piq itself is not pinned (piq is not installed
+                      where the tests run), as for PSNR and SSIM: the float64 mirror tests/lpips_ref.py is.
 
 x, y: [N, 3, H, W] fp32 CUDA tensors in [0, 1].  No CPU fallback: the kernels live in libccvs_hip.so.
 """
@@ -34,8 +39,36 @@ import torch
 from ccvs_amd import ops
 
 
+_LPIPS_SOURCE = None   # what `set_lpips_weights` was given; None: the environment variable, if it is set
+_LPIPS_MODEL = None    # the lpips.LPIPS built from it on first use
+
+
+def set_lpips_weights(weights):
+    """Configure LPIPS for this process: a weight file's path, the dict `lpips.load_lpips_weights` takes, or None (no weights: the
+    environment variable CCVS_LPIPS_WEIGHTS, if set, is read on the next use).  The network is built on first use."""
+    global _LPIPS_SOURCE, _LPIPS_MODEL
+    _LPIPS_SOURCE, _LPIPS_MODEL = weights, None
+
+
+def _lpips_model():
+    """The configured lpips.LPIPS, or None without weights."""
+    global _LPIPS_MODEL
+    if _LPIPS_MODEL is None:
+        source = _LPIPS_SOURCE if _LPIPS_SOURCE is not None else (os.environ.get("CCVS_LPIPS_WEIGHTS") or None)
+        if source is None:
+            return None
+        from ccvs_amd.tools.pytorch_metrics.lpips import LPIPS
+        _LPIPS_MODEL = LPIPS(source)
+    return _LPIPS_MODEL
+
+
 def get_lpips(x, y):
-    raise NotImplementedError("LPIPS needs piq's pretrained VGG16 + linear-head weights (downloaded by piq.LPIPS); not available offline")
+    """metrics.py:12-13, from the weights `set_lpips_weights` / CCVS_LPIPS_WEIGHTS name: a 0-dim fp32 device tensor."""
+    model = _lpips_model()
+    if model is None:
+        raise NotImplementedError("LPIPS needs piq's pretrained VGG16 + linear-head weights (downloaded by piq.LPIPS); none are configured: "
+                                  "name a weight file with set_lpips_weights, CCVS_LPIPS_WEIGHTS or --lpips_weights")
+    return model(x, y)
 
 
 def get_ssim(x, y):
@@ -59,49 +92,73 @@ def upscale(videos, min_size=161):
 
 
 def _scores(real_videos, generated_videos, idx, lpips, ssim, psnr):
-    """One batch of metrics.py:46-59: real_videos / generated_videos [B, T, H, W, 3] in [0, 1]."""
+    """One batch of metrics.py:46-59: real_videos / generated_videos [B, T, H, W, 3] in [0, 1].  lpips: the LPIPS lists, or None
+    without weights."""
     if len(idx) == 0:
         real = real_videos.view(-1, *real_videos.shape[2:]).permute(0, 3, 1, 2).contiguous()
         fake = generated_videos.view(-1, *generated_videos.shape[2:]).permute(0, 3, 1, 2).contiguous()
+        if lpips is not None:
+            lpips.append(get_lpips(real, fake).cpu())
         ssim.append(get_ssim(real, fake).cpu())
         psnr.append(get_psnr(real, fake).cpu())
     else:
         for k, frame_idx in enumerate(idx):
             real = upscale(real_videos[:, frame_idx].permute(0, 3, 1, 2).contiguous())
             fake = upscale(generated_videos[:, frame_idx].permute(0, 3, 1, 2).contiguous())
+            if lpips is not None:
+                lpips[k].append(get_lpips(real, fake).cpu())
             ssim[k].append(get_ssim(real, fake).cpu())
             psnr[k].append(get_psnr(real, fake).cpu())
 
 
-def _aggregate(ssim, psnr, print_256, idx, batch_size):
-    """metrics.py:61-78 (LPIPS left out)."""
+def _aggregate(ssim, psnr, print_256, idx, batch_size, lpips=None):
+    """metrics.py:61-78.  lpips: the LPIPS lists; None without weights -- LPIPS is then left out of the line and returned as None."""
+    lpips_m = None
     if print_256 and len(idx) == 0:
         ssim = torch.stack(ssim).view(-1, 256 // batch_size)
         psnr = torch.stack(psnr).view(-1, 256 // batch_size)
         ssim_m, psnr_m = ssim.mean(), psnr.mean()
-        print(f"(256) SSIM is {ssim_m} (+- {ssim.mean(1).std()}), PSNR is {psnr_m} (+- {psnr.mean(1).std()})")
+        head = ""
+        if lpips is not None:
+            lpips = torch.stack(lpips).view(-1, 256 // batch_size)
+            lpips_m = lpips.mean()
+            head = f"LPIPS is: {lpips_m} (+- {lpips.mean(1).std()}), "
+        print(f"(256) {head}SSIM is {ssim_m} (+- {ssim.mean(1).std()}), PSNR is {psnr_m} (+- {psnr.mean(1).std()})")
     elif len(idx) == 0:
         ssim_m, psnr_m = torch.stack(ssim).mean(), torch.stack(psnr).mean()
+        if lpips is not None:
+            lpips_m = torch.stack(lpips).mean()
     else:
         ssim_m = [torch.stack(e).mean() for e in ssim]
         psnr_m = [torch.stack(e).mean() for e in psnr]
-    return None, ssim_m, psnr_m
+        if lpips is not None:
+            lpips_m = [torch.stack(e).mean() for e in lpips]
+    return lpips_m, ssim_m, psnr_m
+
+
+def _lpips_lists(idx):
+    """The LPIPS lists of a run of the loop, or None without weights."""
+    if _lpips_model() is None:
+        return None
+    return [] if len(idx) == 0 else [[] for _ in idx]
 
 
 def metrics_from_videos(real_videos_u8, generated_videos_u8, print_256=False, idx=(), batch_size=16, device="cuda"):
     """The loop of `metrics_from_files` on clips already in memory: uint8 [N, T, H, W, 3] (numpy or torch), batches of 16 as in the
-    reference (a ragged tail is dropped like its `total_size // batch_size`).  Returns (None, ssim, psnr)."""
+    reference (a ragged tail is dropped like its `total_size // batch_size`).  Returns (lpips, ssim, psnr); lpips is None without
+    LPIPS weights (`set_lpips_weights`)."""
     idx = list(idx)
     total = len(real_videos_u8)
     assert len(generated_videos_u8) == total
     ssim, psnr = ([], []) if len(idx) == 0 else ([[] for _ in idx], [[] for _ in idx])
+    lpips = _lpips_lists(idx)
     with torch.no_grad():
         for i in range(total // batch_size):
             sl = slice(i * batch_size, min((i + 1) * batch_size, total))
             real = torch.as_tensor(real_videos_u8[sl]).to(device) / 255
             fake = torch.as_tensor(generated_videos_u8[sl]).to(device) / 255
-            _scores(real, fake, idx, None, ssim, psnr)
-    return _aggregate(ssim, psnr, print_256, idx, batch_size)
+            _scores(real, fake, idx, lpips, ssim, psnr)
+    return _aggregate(ssim, psnr, print_256, idx, batch_size, lpips)
 
 
 def metrics_from_files(real_video_files, generated_video_files, resize, num_workers, print_256, idx, loader=None):
@@ -116,13 +173,14 @@ def metrics_from_files(real_video_files, generated_video_files, resize, num_work
     batch_size = 16
     total = len(real_video_files)
     ssim, psnr = ([], []) if len(idx) == 0 else ([[] for _ in idx], [[] for _ in idx])
+    lpips = _lpips_lists(idx)
     with torch.no_grad():
         for i in range(total // batch_size):
             sl = slice(i * batch_size, min((i + 1) * batch_size, total))
             real = torch.as_tensor(loader(real_video_files[sl], resize)).cuda() / 255
             fake = torch.as_tensor(loader(generated_video_files[sl], resize)).cuda() / 255
-            _scores(real, fake, idx, None, ssim, psnr)
-    return _aggregate(ssim, psnr, print_256, idx, batch_size)
+            _scores(real, fake, idx, lpips, ssim, psnr)
+    return _aggregate(ssim, psnr, print_256, idx, batch_size, lpips)
 
 
 def load_video(file, resize):
@@ -185,6 +243,8 @@ def print_scores(scores, name):
 
 def main(args):
     """metrics.py:132-172."""
+    if getattr(args, "lpips_weights", None):
+        set_lpips_weights(args.lpips_weights)
     fake_folders = get_folders(args.exp_tag, args.num_folds)
     real_tag = args.exp_tag if args.real_tag is None else args.real_tag
     real_folders = get_folders(real_tag, args.num_folds)
@@ -238,6 +298,7 @@ def parse_args(argv=None):
     parser.add_argument('--num_workers', type=int, default=8)
     parser.add_argument('--print_256', action='store_true')
     parser.add_argument('--resize', type=int, nargs="+", default=None)
+    parser.add_argument('--lpips_weights', type=str, default=None, help="the LPIPS weight file (tools/pytorch_metrics/lpips.py writes it)")
     return parser.parse_args(argv)
 
 
