@@ -36,6 +36,8 @@ VIDEO_EXPORTS = ["ccvs_ingest_f32"]
 OUTPUT_SAMPLED_EXPORTS = ["ccvs_mjpeg_sampled_workspace_bytes", "ccvs_mjpeg_encode_sampled"]
 # every symbol include/ccvs_hip_lpips.h declares (the memory-bound passes of LPIPS around its convolutions; included by ccvs_hip.h too)
 LPIPS_EXPORTS = ["ccvs_lpips_prep", "ccvs_relu_", "ccvs_relu_maxpool2", "ccvs_lpips_layer_workspace_bytes", "ccvs_lpips_layer"]
+# every symbol include/ccvs_hip_fvd.h declares (the passes of the FVD embedding around its I3D convolutions; included by ccvs_hip.h too)
+FVD_EXPORTS = ["ccvs_fvd_prep", "ccvs_time_unfold", "ccvs_maxpool3d_same", "ccvs_i3d_head"]
 
 
 class ConvDesc(C.Structure):
@@ -187,6 +189,10 @@ def load():
         "ccvs_relu_": [vp, i64, vp],
         "ccvs_relu_maxpool2": [vp, vp, i64, i32, i32, vp],
         "ccvs_lpips_layer": [vp, vp, vp, vp, i64, i32, i64, i32, i32, vp],
+        "ccvs_fvd_prep": [vp, vp, i64, i32, i32, i32, i32, i32, vp],
+        "ccvs_time_unfold": [vp, i64, i64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+        "ccvs_maxpool3d_same": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
+        "ccvs_i3d_head": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
         "ccvs_ingest_f32": [vp, i32, i64, i64, i32, i32, i32, i32, i32, vp, i32, vp, vp, i64, i64, vp],
         "ccvs_ingest_u8": [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i64, i64, vp, vp],
     }

@@ -1138,6 +1138,111 @@ def lpips_layer(f, w, relu=True, out=None, accumulate=False):
     return out
 
 
+# ------------------------------------------------------------------ FVD / I3D (include/ccvs_hip_fvd.h)
+def same_pad(n, k, s):
+    """TensorFlow's SAME geometry of one axis: (out, before, after) = (ceil(n / s), total // 2, total - total // 2) with
+    total = max((out - 1) s + k - n, 0)."""
+    out = -(-n // s)
+    total = max((out - 1) * s + k - n, 0)
+    return out, total // 2, total - total // 2
+
+
+def fvd_prep(u8, size=(224, 224), flip=False, out=None):
+    """fvd.py:34-51 `preprocess` (`ccvs_fvd_prep`): uint8 [..., H, W, 3] -> fp32 [..., 3, OH, OW], TF1's resize_bilinear
+    (align_corners False, no half-pixel centres) then (2 v) / 255 - 1, each step rounded to fp32 on its own.  flip=True reverses the
+    channel order.  out: optional contiguous fp32 tensor of that shape to write into."""
+    _need_gpu(u8, out)
+    assert u8.dtype == torch.uint8 and u8.dim() >= 3 and u8.shape[-1] == 3 and u8.numel() > 0, (u8.dtype, u8.shape)
+    u8 = u8.contiguous()
+    h, w = u8.shape[-3:-1]
+    oh, ow = int(size[0]), int(size[1])
+    shape = (*u8.shape[:-3], 3, oh, ow)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=u8.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous(), (out.shape, shape)
+    _lib.check(_lib.load().ccvs_fvd_prep(_p(u8), _p(out), u8.numel() // (h * w * 3), h, w, oh, ow, int(bool(flip)), _stream()), "ccvs_fvd_prep")
+    return out
+
+
+def time_unfold(x, t, kt, st=1, pad=(0, 0, 0, 0), relu=False, phases=1, out=None):
+    """The time-stacked input of a kt-tap, stride-st 3-D convolution with SAME padding in time (`ccvs_time_unfold`).  x: [N t, C, H, W]
+    fp32, clips of t frames (a channel-slice view is read in place) -> [N To, kt C, H + pt + pb, W + pl + pr], To = ceil(t / st): channel
+    j C + c of output frame t' is channel c of the clip's frame t' st + j - before, zeros outside the clip; pad = (pt, pb, pl, pr) zero
+    border rows and columns; relu=True writes max(x, 0).  phases=2 also splits the bordered frame (even sides) into its four pixel
+    phases: [N To, 4 kt C, Hp / 2, Wp / 2], channel (j C + c) 4 + 2 py + px holding the pixels (2 y + py, 2 x + px), the input of a
+    stride-2 convolution written as a stride-1 one (`stack_conv3d_weight`).  out: optional contiguous fp32 tensor of that shape."""
+    _need_gpu(x, out)
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.numel() > 0 and x.shape[0] % t == 0, (x.shape, x.dtype, t)
+    if not (_rows_dense(x) and x.stride(1) >= x.shape[2] * x.shape[3] and x.stride(0) >= x.stride(1) * x.shape[1]):
+        x = x.contiguous()
+    nt, c, h, w = x.shape
+    pt, pb, pl, pr = (int(v) for v in pad)
+    hp, wp = h + pt + pb, w + pl + pr
+    assert phases == 1 or (phases == 2 and hp % 2 == 0 and wp % 2 == 0), (phases, hp, wp)
+    to = same_pad(t, kt, st)[0]
+    shape = (nt // t * to, kt * c * phases * phases, hp // phases, wp // phases)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous(), (out.shape, shape)
+    _lib.check(_lib.load().ccvs_time_unfold(_p(x), x.stride(0), x.stride(1), _p(out), nt // t, t, c, h, w, kt, st, pt, pb, pl, pr, phases,
+                                            int(bool(relu)), _stream()), "ccvs_time_unfold")
+    return out
+
+
+def stack_conv3d_weight(w, phases=1):
+    """[Cout, Cin, kt, k, k] -> the 2-D weight over `time_unfold`'s channels: [Cout, kt Cin, k, k], or for phases=2 (a stride-2
+    convolution as a stride-1 one over the four pixel phases) [Cout, 4 kt Cin, ceil(k / 2), ceil(k / 2)] with tap (a, b) of channel
+    (j Cin + c) 4 + 2 py + px = w[:, c, j, 2 a + py, 2 b + px], zero where that lies outside the kernel."""
+    co, ci, kt, kh, kw = w.shape
+    if phases == 1:
+        return w.permute(0, 2, 1, 3, 4).reshape(co, kt * ci, kh, kw)
+    assert phases == 2 and kh == kw, (phases, w.shape)
+    k2 = (kh + 1) // 2
+    wp = torch.zeros(co, ci, kt, 2 * k2, 2 * k2, dtype=w.dtype, device=w.device)
+    wp[:, :, :, :kh, :kw] = w
+    return wp.view(co, ci, kt, k2, 2, k2, 2).permute(0, 2, 1, 4, 6, 3, 5).reshape(co, kt * ci * 4, k2, k2)
+
+
+def maxpool3d_same(x, t, kernel, stride, relu=False, out=None):
+    """A 3-D max pool with TensorFlow's SAME geometry (`ccvs_maxpool3d_same`).  x: [N t, C, H, W] fp32, clips of t frames -> [N To, C,
+    Ho, Wo] with ceil(n / s) per axis; kernel (1,3,3), (3,3,3) or (2,2,2), stride (1,2,2), (2,2,2) or (1,1,1).  Padding never wins (a
+    window is clipped to the clip); relu=True pools max(x, 0); a NaN in a window comes out, as in torch.  out: optional contiguous
+    fp32 tensor of that shape."""
+    _need_gpu(x, out)
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.numel() > 0 and x.shape[0] % t == 0, (x.shape, x.dtype, t)
+    x = x.contiguous()
+    nt, c, h, w = x.shape
+    (kt, kh, kw), (st, sh, sw) = kernel, stride
+    shape = (nt // t * same_pad(t, kt, st)[0], c, same_pad(h, kh, sh)[0], same_pad(w, kw, sw)[0])
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    assert out.shape == shape and out.dtype == torch.float32 and out.is_contiguous(), (out.shape, shape)
+    _lib.check(_lib.load().ccvs_maxpool3d_same(_p(x), _p(out), nt // t, t, c, h, w, kt, kh, kw, st, sh, sw, int(bool(relu)), _stream()),
+               "ccvs_maxpool3d_same")
+    return out
+
+
+def i3d_head(x, t, weight, bias, relu=False, out=None):
+    """The I3D head (`ccvs_i3d_head`).  x: [N t, C, 7, 7] fp32, clips of t >= 2 frames; weight [K, C] and bias [K] fp32 -> float64 [N, K]:
+    the (2, 7, 7) average pool (stride 1, VALID: t - 1 windows), the logits `weight x + bias` and their mean over the windows, float64
+    inside, the same bits on every run.  relu=True averages max(x, 0).  out: optional float64 [N, K] to write into."""
+    _need_gpu(x, weight, bias, out)
+    assert x.dim() == 4 and x.dtype == torch.float32 and x.numel() > 0 and x.shape[0] % t == 0, (x.shape, x.dtype, t)
+    if x.shape[2:] != (7, 7):
+        raise ValueError(f"i3d_head: the map in front of the (2, 7, 7) average pool is {tuple(x.shape[2:])}, not 7 x 7 (the squeeze needs 1 x 1 behind it)")
+    x = x.contiguous()
+    nt, c = x.shape[:2]
+    weight = weight.reshape(weight.shape[0], -1).contiguous()
+    bias = bias.reshape(-1).contiguous()
+    k = weight.shape[0]
+    assert weight.dtype == torch.float32 and bias.dtype == torch.float32 and weight.shape == (k, c) and bias.shape == (k,), (weight.shape, bias.shape, c)
+    if out is None:
+        out = torch.empty(nt // t, k, dtype=torch.float64, device=x.device)
+    assert out.shape == (nt // t, k) and out.dtype == torch.float64 and out.is_contiguous(), (out.shape, out.dtype)
+    _lib.check(_lib.load().ccvs_i3d_head(_p(x), _p(weight), _p(bias), _p(out), nt // t, t, c, 49, k, int(bool(relu)), _stream()), "ccvs_i3d_head")
+    return out
+
+
 def pack_u8(vid, lo=-1.0, hi=1.0, out=None):
     """[..., 3, H, W] fp32 -> [..., H, W, 3] uint8 (helpers/generator.py:306-309).  out: optional contiguous uint8 [..., H, W, 3]
     tensor to write into (default: a new one)."""
