@@ -7,6 +7,9 @@
 // The kernel is a template over the sampling (include/ccvs_hip_output_sampled.h): 0 is the kernel above word
 // for word; 1 (4:2:2) and 2 (4:2:0) have MCUs of 16 x 8 / 16 x 16 pixels and 4 / 6 blocks, stage finished planes instead of raw RGB and
 // know dummy blocks.  An interval never has more than 96 blocks, so every buffer keeps its size.
+// It is a template over what it does with the coefficients, too (include/ccvs_hip_output_optimized.h): code them
+// with the Annex K tables (the two encoders above, unchanged), count their symbols per frame, or code them with that frame's own tables
+// -- libjpeg's optimize_coding: gather, jpeg_gen_optimal_table (jpeg_tables_kernel below), then the same two passes.
 #include "common.h"
 
 #define JP_THREADS 128
@@ -88,7 +91,14 @@ struct JpegArgs {
     int write;                     // 0: the first pass (sizes), 1: the second (bytes)
     int aligned;                   // every 4-byte group of a row that lies inside the row is dword-aligned
     unsigned short qd[2][64];      // 8 x the quantiser tables (natural order): [0] luminance, [1] chrominance
+    unsigned* counts;              // JP_GATHER: [n][4][257], how often every frame's scan emits every symbol (the tables in DHT order)
+    const unsigned* emit;          // JP_FRAME_TABLES: [n][4][256], every frame's codes as c_huff holds the constant ones
 };
+// what jpeg_interval_kernel does with the coefficients
+#define JP_STANDARD 0       // codes them with the Annex K tables
+#define JP_GATHER 1         // counts the symbols it would emit, per frame
+#define JP_FRAME_TABLES 2   // codes them with the tables of the interval's frame
+#define JP_SPEC_BYTES 272   // a table for the host: bits[16] + huffval[256]
 
 // ---- libjpeg's jfdctint.c ("islow"): one 1-D pass over d[0], d[S], ..., d[7 S].  FIRST: the row pass (results scaled up by
 // PASS1_BITS); else the column pass (that scaling and the pass's own factor of 8 removed again -- the block stays 8 x the true DCT).
@@ -155,18 +165,31 @@ __device__ __forceinline__ void put_bits(unsigned* words, int& pos, unsigned v, 
 }
 __device__ __forceinline__ int bit_length(int v) { return 32 - __clz(v); }   // of v >= 0
 
-// One block: the DC difference and the 63 AC coefficients (zigzag order, `coef[1 .. 63]`).  EMIT = false: only counts.  Returns the
-// bit position behind the block.
-template <bool EMIT>
+// One symbol of table `t` and the `cat` bits behind it.  JP_SIZE: only counts the bits; JP_EMIT: writes them; JP_COUNT: `t` is the
+// table's histogram (in LDS) and the symbol is counted.
+#define JP_SIZE 0
+#define JP_EMIT 1
+#define JP_COUNT 2
+template <int OP>
+__device__ __forceinline__ void code_symbol(const unsigned* t, int sym, unsigned bits, int cat, unsigned* words, int& pos) {
+    if (OP == JP_COUNT) {
+        atomicAdd(const_cast<unsigned*>(t) + sym, 1u);
+    } else {
+        const unsigned e = t[sym];
+        if (OP == JP_EMIT) put_bits(words, pos, ((e >> 5) << cat) | bits, (int)(e & 31u) + cat);
+        else pos += (int)(e & 31u) + cat;
+    }
+}
+
+// One block: the DC difference and the 63 AC coefficients (zigzag order, `coef[1 .. 63]`).  Returns the bit position behind the block
+// (JP_COUNT: `pos` as it came).
+template <int OP>
 __device__ __forceinline__ int code_block(const short* coef, int diff, const unsigned* dc, const unsigned* ac, unsigned* words, int pos) {
     {
         const int a = diff < 0 ? -diff : diff;
         int cat = bit_length(a);
         cat = cat > 11 ? 11 : cat;
-        const unsigned e = dc[cat];
-        const unsigned bits = (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << cat) - 1u);
-        if (EMIT) put_bits(words, pos, ((e >> 5) << cat) | bits, (int)(e & 31u) + cat);
-        else pos += (int)(e & 31u) + cat;
+        code_symbol<OP>(dc, cat, (unsigned)(diff < 0 ? diff - 1 : diff) & ((1u << cat) - 1u), cat, words, pos);
     }
     int run = 0;
     for (int k = 1; k < 64; ++k) {
@@ -176,25 +199,16 @@ __device__ __forceinline__ int code_block(const short* coef, int diff, const uns
             continue;
         }
         while (run > 15) {   // ZRL: sixteen zeros
-            const unsigned z = ac[0xF0];
-            if (EMIT) put_bits(words, pos, z >> 5, (int)(z & 31u));
-            else pos += (int)(z & 31u);
+            code_symbol<OP>(ac, 0xF0, 0u, 0, words, pos);
             run -= 16;
         }
         const int a = v < 0 ? -v : v;
         int cat = bit_length(a);
         cat = cat > 10 ? 10 : cat;
-        const unsigned e = ac[(run << 4) | cat];
-        const unsigned bits = (unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1u);
-        if (EMIT) put_bits(words, pos, ((e >> 5) << cat) | bits, (int)(e & 31u) + cat);
-        else pos += (int)(e & 31u) + cat;
+        code_symbol<OP>(ac, (run << 4) | cat, (unsigned)(v < 0 ? v - 1 : v) & ((1u << cat) - 1u), cat, words, pos);
         run = 0;
     }
-    if (run > 0) {   // EOB, only when the block ends in zeros
-        const unsigned z = ac[0x00];
-        if (EMIT) put_bits(words, pos, z >> 5, (int)(z & 31u));
-        else pos += (int)(z & 31u);
-    }
+    if (run > 0) code_symbol<OP>(ac, 0x00, 0u, 0, words, pos);   // EOB, only when the block ends in zeros
     return pos;
 }
 
@@ -231,7 +245,18 @@ __device__ __forceinline__ int dc_source(const JpegArgs& a, int first, int t) {
     return m * BPM + k;
 }
 
-template <int S>
+// JP_GATHER: the frame's histograms, kept in s_huff, go to a.counts with integer atomics (sums of integers: the same on every run).
+// The slots of s_huff are DC luminance, DC chrominance, AC luminance, AC chrominance; a.counts has the DHT order (AC luminance second).
+__device__ __forceinline__ void flush_counts(unsigned* s_huff, unsigned* counts, long frame, int tid) {
+    for (int i = tid; i < 4 * 256; i += JP_THREADS) {
+        const unsigned c = s_huff[i];
+        const int slot = i >> 8, t = slot == 1 ? 2 : (slot == 2 ? 1 : slot);
+        if (c) atomicAdd(&counts[(frame * 4 + t) * 257 + (i & 255)], c);
+        s_huff[i] = 0;
+    }
+}
+
+template <int S, int M>
 __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
     constexpr int BPM = S == 0 ? 3 : 2 * S + 2;           // blocks per MCU: Y Cb Cr, Y0 Y1 Cb Cr, Y00 Y01 Y10 Y11 Cb Cr
     constexpr int VS = S == 2 ? 2 : 1;                    // luminance rows per chrominance row
@@ -243,7 +268,11 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
     __shared__ unsigned short s_qd[2 * 64];
     __shared__ int s_dc[JP_MAXBLK], s_cnt[JP_MAXBLK], s_ff[JP_THREADS];
     const int tid = threadIdx.x;
-    for (int i = tid; i < 4 * 256; i += JP_THREADS) s_huff[i] = c_huff.t[i >> 8][i & 255];
+    if constexpr (M == JP_STANDARD)
+        for (int i = tid; i < 4 * 256; i += JP_THREADS) s_huff[i] = c_huff.t[i >> 8][i & 255];
+    if constexpr (M == JP_GATHER)
+        for (int i = tid; i < 4 * 256; i += JP_THREADS) s_huff[i] = 0;
+    long held = -1;   // JP_GATHER / JP_FRAME_TABLES: the frame whose histograms / codes s_huff holds
     if (tid < 128) s_qd[tid] = a.qd[tid >> 6][tid & 63];
     const int mcu = tid / BPM;
     const int comp = S == 0 ? tid % 3 : (tid - mcu * BPM < BPM - 2 ? 0 : tid - mcu * BPM - (BPM - 3));
@@ -254,6 +283,16 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
         const int nm = a.nmcu - first < a.R ? a.nmcu - first : a.R;   // MCUs of this interval
         const int nb = BPM * nm;                                       // its blocks, in stream order: block t = (MCU t / BPM, block t % BPM of it)
         const uint8_t* frame = a.rgb + n * a.frame_stride;
+        // (the barrier at the loop's end lies behind s_huff's last use, the one behind step 1 before its next)
+        if constexpr (M != JP_STANDARD)
+            if (n != held) {
+                if constexpr (M == JP_GATHER) {
+                    if (held >= 0) flush_counts(s_huff, a.counts, held, tid);
+                } else {
+                    for (int i = tid; i < 4 * 256; i += JP_THREADS) s_huff[i] = a.emit[n * 1024 + i];
+                }
+                held = n;
+            }
         // 1. the MCUs' pixels, a dword at a time; rows below the frame and pixels right of it replicate the last row / pixel
         if constexpr (S == 0)
         for (int it = tid; it < nm * 48; it += JP_THREADS) {
@@ -356,9 +395,11 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
                 const int prev = comp != 0 ? tid - BPM : (kb > 0 ? tid - 1 : tid - 3);
                 diff = s_dc[dc_source<S>(a, first, tid)] - (prev >= 0 ? s_dc[dc_source<S>(a, first, prev)] : 0);
             }
-            s_cnt[tid] = code_block<false>(s_coef + tid * JP_CSTRIDE, diff, dc, ac, nullptr, 0);
+            if constexpr (M == JP_GATHER) code_block<JP_COUNT>(s_coef + tid * JP_CSTRIDE, diff, dc, ac, nullptr, 0);
+            else s_cnt[tid] = code_block<JP_SIZE>(s_coef + tid * JP_CSTRIDE, diff, dc, ac, nullptr, 0);
         }
         __syncthreads();
+        if constexpr (M == JP_GATHER) continue;   // counted; the barrier above stands for the one at the loop's end
         // 4. where every block starts; clear the words the interval takes
         int start = 0, total = 0;
         for (int j = 0; j < nb; ++j) {
@@ -372,7 +413,7 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
         __syncthreads();
         // 5. the bits; the last byte is padded with ones
         if (tid < nb) {
-            int pos = code_block<true>(s_coef + tid * JP_CSTRIDE, diff, dc, ac, s_words, start);
+            int pos = code_block<JP_EMIT>(s_coef + tid * JP_CSTRIDE, diff, dc, ac, s_words, start);
             if (tid == nb - 1) put_bits(s_words, pos, (1u << (8 * nbytes - total)) - 1u, 8 * nbytes - total);
         }
         __syncthreads();
@@ -414,6 +455,8 @@ __global__ __launch_bounds__(JP_THREADS) void jpeg_interval_kernel(JpegArgs a) {
         }
         __syncthreads();   // the LDS arrays are the next interval's too
     }
+    if constexpr (M == JP_GATHER)
+        if (held >= 0) flush_counts(s_huff, a.counts, held, tid);
 }
 
 // ---- exclusive scan of the intervals' sizes by one workgroup: a lane sums a run of consecutive intervals, the runs' sums are scanned
@@ -443,6 +486,113 @@ __global__ __launch_bounds__(JP_SCAN_THREADS) void jpeg_scan_kernel(const int* s
     if (tid == 0) offsets[T / nI] = total;
 }
 
+// ---- libjpeg's jpeg_gen_optimal_table (jchuff.c) for one table of one frame: one wave per table, everything in LDS.
+//   tree     symbol 256 with frequency 1 keeps the all-ones code unused.  The two smallest nonzero frequencies are merged until one is
+//            left; among equals the LARGER symbol is taken (libjpeg scans upwards with `<=`).  libjpeg walks the two `others` chains and
+//            adds 1 to every code size on them; a chain is the set of symbols under its head, so here every symbol knows its head
+//            (s_head) and the lanes add 1 to those whose head is one of the two.
+//   limit    the code sizes (up to 32) are counted into bits[] and brought down to 16 as T.81 K.2 does; one code of the longest length
+//            goes (the pseudo-symbol's).
+//   huffval  the symbols by ascending code size BEFORE limiting, then by value: a lane finds each of its symbols' rank by counting.
+//   codes    canonical from bits[] (T.81 Annex C): the symbol at rank p has the code first[len] + p - (codes shorter than len).
+// A histogram without a symbol gives an empty table; a tree deeper than 32, where libjpeg stops with an error (it takes millions of
+// symbols in Fibonacci proportions), is counted as 32 deep.
+#define JP_TBL_THREADS 64
+#define JP_MAX_CLEN 32
+__global__ __launch_bounds__(JP_TBL_THREADS) void jpeg_tables_kernel(const unsigned* counts, uint8_t* tables, unsigned* emit) {
+    __shared__ unsigned s_freq[257];
+    __shared__ int s_size[257], s_head[257], s_bits[JP_MAX_CLEN + 1], s_before[18], s_first[18];
+    const int lane = threadIdx.x, frame = blockIdx.x >> 2, t = blockIdx.x & 3;
+    for (int i = lane; i < 257; i += JP_TBL_THREADS) {
+        s_freq[i] = i < 256 ? counts[(long)blockIdx.x * 257 + i] : 1u;
+        s_size[i] = 0;
+        s_head[i] = i;
+    }
+    if (lane <= JP_MAX_CLEN) s_bits[lane] = 0;
+    __syncthreads();
+    for (;;) {
+        // the smallest key (frequency, then 65535 - symbol) among the nonzero frequencies, and the smallest but that one
+        int c[2] = {-1, -1};
+        for (int r = 0; r < 2; ++r) {
+            unsigned long long key = ~0ull;
+            for (int i = lane; i < 257; i += JP_TBL_THREADS) {
+                const unsigned f = s_freq[i];
+                const unsigned long long k = ((unsigned long long)f << 16) | (unsigned)(0xFFFF - i);
+                if (f && i != c[0] && k < key) key = k;
+            }
+            for (int m = JP_TBL_THREADS / 2; m > 0; m >>= 1) {
+                const unsigned long long o = __shfl_xor(key, m, JP_TBL_THREADS);
+                key = o < key ? o : key;
+            }
+            if (key != ~0ull) c[r] = 0xFFFF - (int)(key & 0xFFFFu);
+        }
+        if (c[1] < 0) break;                               // (the same in every lane)
+        __syncthreads();
+        if (lane == 0) {
+            s_freq[c[0]] += s_freq[c[1]];
+            s_freq[c[1]] = 0;
+        }
+        for (int i = lane; i < 257; i += JP_TBL_THREADS) {
+            const int h = s_head[i];
+            if (h == c[0] || h == c[1]) {
+                ++s_size[i];
+                s_head[i] = c[0];
+            }
+        }
+        __syncthreads();
+    }
+    for (int i = lane; i < 257; i += JP_TBL_THREADS) {
+        const int sz = s_size[i];
+        if (sz) atomicAdd(&s_bits[sz < JP_MAX_CLEN ? sz : JP_MAX_CLEN], 1);
+    }
+    __syncthreads();
+    if (lane == 0) {
+        int i;
+        for (i = JP_MAX_CLEN; i > 16; --i)
+            while (s_bits[i] > 0) {
+                int j = i - 2;
+                while (j > 0 && s_bits[j] == 0) --j;
+                s_bits[i] -= 2;
+                s_bits[i - 1] += 1;
+                s_bits[j + 1] += 2;
+                s_bits[j] -= 1;
+            }
+        while (i > 0 && s_bits[i] == 0) --i;
+        if (i > 0) --s_bits[i];
+        int code = 0, k = 0;
+        for (int len = 1; len <= 16; ++len) {
+            s_before[len] = k;
+            s_first[len] = code;
+            k += s_bits[len];
+            code = (code + s_bits[len]) << 1;
+        }
+        s_before[17] = k;
+    }
+    __syncthreads();
+    uint8_t* spec = tables + (long)blockIdx.x * JP_SPEC_BYTES;
+    const int slot = t == 1 ? 2 : (t == 2 ? 1 : t);        // jpeg_interval_kernel's order of the four tables
+    unsigned* codes = emit + ((long)frame * 4 + slot) * 256;
+    const int total = s_before[17];
+    if (lane < 16) spec[lane] = (uint8_t)s_bits[lane + 1];
+    for (int p = total + lane; p < 256; p += JP_TBL_THREADS) spec[16 + p] = 0;
+    for (int j = lane; j < 256; j += JP_TBL_THREADS) {
+        const int sz = s_size[j];
+        unsigned e = 0;
+        if (sz) {
+            int p = 0;
+            for (int k = 0; k < 256; ++k) {
+                const int o = s_size[k];
+                p += o && (o < sz || (o == sz && k < j));
+            }
+            int len = 1;
+            while (len < 16 && p >= s_before[len + 1]) ++len;
+            spec[16 + p] = (uint8_t)j;
+            e = ((unsigned)(s_first[len] + p - s_before[len]) << 5) | (unsigned)len;
+        }
+        codes[j] = e;
+    }
+}
+
 // MCUs are 8 x 8, 16 x 8 or 16 x 16 pixels; an interval holds at most JP_MAXBLK blocks: 32, 24 or 16 MCUs
 static inline int jpeg_max_restart(int sampling) { return JP_MAXBLK / (sampling == 0 ? 3 : 2 * sampling + 2); }
 static inline long jpeg_intervals(int n, int h, int w, int sampling, int R) {
@@ -459,9 +609,21 @@ static inline size_t jpeg_workspace(int n, int h, int w, int sampling, int R) {
     return 8 * T + ((4 * T + 7) & ~(size_t)7);   // long ioff[T], then int sizes[T]
 }
 
-// `who`: the entry point's name for the messages; `sampling` has been checked by the caller.
+// The optimised form keeps, behind that, the frames' histograms (unsigned [n][4][257]) and their codes (unsigned [n][4][256]).
+static inline size_t jpeg_optimized_workspace(int n, int h, int w, int sampling, int R) {
+    const size_t base = jpeg_workspace(n, h, w, sampling, R);
+    return base ? base + (size_t)n * 4 * (257 + 256) * 4 : 0;
+}
+
+template <int M>
+static void (*jpeg_kernel(int sampling))(JpegArgs) {
+    return sampling == 0 ? jpeg_interval_kernel<0, M> : (sampling == 1 ? jpeg_interval_kernel<1, M> : jpeg_interval_kernel<2, M>);
+}
+
+// `who`: the entry point's name for the messages; `sampling` has been checked by the caller.  tables: null for the Annex K tables, else
+// where the frames' own tables go (uint8 [n][4][JP_SPEC_BYTES]).
 static int jpeg_encode(const char* who, const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int sampling, int restart_mcus,
-                       uint8_t* stream, long capacity, long* offsets, void* workspace, void* hip_stream) {
+                       uint8_t* stream, long capacity, long* offsets, uint8_t* tables, void* workspace, void* hip_stream) {
     const int maxr = jpeg_max_restart(sampling);
     CCVS_REQUIRE(quality >= 1 && quality <= 100, "%s: quality %d outside 1 .. 100", who, quality);
     CCVS_REQUIRE(restart_mcus >= 1 && restart_mcus <= maxr, "%s: restart interval %d outside 1 .. %d MCUs", who, restart_mcus, maxr);
@@ -490,7 +652,21 @@ static int jpeg_encode(const char* who, const uint8_t* rgb, long frame_stride, i
             a.qd[t][i] = (unsigned short)(q << 3);
         }
     const unsigned grid = limited_grid(a.T, hip_stream, 8);
-    void (*const kernel)(JpegArgs) = sampling == 0 ? jpeg_interval_kernel<0> : (sampling == 1 ? jpeg_interval_kernel<1> : jpeg_interval_kernel<2>);
+    void (*const kernel)(JpegArgs) = tables ? jpeg_kernel<JP_FRAME_TABLES>(sampling) : jpeg_kernel<JP_STANDARD>(sampling);
+    a.counts = nullptr; a.emit = nullptr;
+    if (tables) {
+        const size_t base = jpeg_workspace(n, h, w, sampling, restart_mcus);
+        a.counts = (unsigned*)((char*)workspace + base);
+        unsigned* emit = a.counts + (size_t)n * 4 * 257;
+        a.emit = emit;
+        if (hipMemsetAsync(a.counts, 0, (size_t)n * 4 * 257 * 4, (hipStream_t)hip_stream) != hipSuccess) {
+            ccvs_set_error("%s: clearing the histograms failed: %s", who, hipGetErrorString(hipGetLastError()));
+            return CCVS_ERR_LAUNCH;
+        }
+        a.write = 0;
+        hipLaunchKernelGGL(jpeg_kernel<JP_GATHER>(sampling), dim3(grid), dim3(JP_THREADS), 0, (hipStream_t)hip_stream, a);
+        hipLaunchKernelGGL(jpeg_tables_kernel, dim3(4 * n), dim3(JP_TBL_THREADS), 0, (hipStream_t)hip_stream, a.counts, tables, emit);
+    }
     a.write = 0;
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(JP_THREADS), 0, (hipStream_t)hip_stream, a);
     hipLaunchKernelGGL(jpeg_scan_kernel, dim3(1), dim3(JP_SCAN_THREADS), 0, (hipStream_t)hip_stream, a.sizes, ioff, offsets, a.T, a.nI);
@@ -504,7 +680,7 @@ extern "C" size_t ccvs_mjpeg_workspace_bytes(int n, int h, int w, int restart_mc
 
 extern "C" int ccvs_mjpeg_encode(const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int restart_mcus, uint8_t* stream,
                                  long capacity, long* offsets, void* workspace, void* hip_stream) {
-    return jpeg_encode("ccvs_mjpeg_encode", rgb, frame_stride, n, h, w, quality, 0, restart_mcus, stream, capacity, offsets, workspace, hip_stream);
+    return jpeg_encode("ccvs_mjpeg_encode", rgb, frame_stride, n, h, w, quality, 0, restart_mcus, stream, capacity, offsets, nullptr, workspace, hip_stream);
 }
 
 // ---- include/ccvs_hip_output_sampled.h
@@ -515,6 +691,21 @@ extern "C" size_t ccvs_mjpeg_sampled_workspace_bytes(int n, int h, int w, int sa
 extern "C" int ccvs_mjpeg_encode_sampled(const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int sampling, int restart_mcus,
                                          uint8_t* stream, long capacity, long* offsets, void* workspace, void* hip_stream) {
     CCVS_REQUIRE(sampling >= 0 && sampling <= 2, "ccvs_mjpeg_encode_sampled: sampling %d is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)", sampling);
-    return jpeg_encode("ccvs_mjpeg_encode_sampled", rgb, frame_stride, n, h, w, quality, sampling, restart_mcus, stream, capacity, offsets, workspace,
-                       hip_stream);
+    return jpeg_encode("ccvs_mjpeg_encode_sampled", rgb, frame_stride, n, h, w, quality, sampling, restart_mcus, stream, capacity, offsets, nullptr,
+                       workspace, hip_stream);
+}
+
+// ---- include/ccvs_hip_output_optimized.h
+extern "C" size_t ccvs_mjpeg_optimized_workspace_bytes(int n, int h, int w, int sampling, int restart_mcus) {
+    return jpeg_optimized_workspace(n, h, w, sampling, restart_mcus);
+}
+
+extern "C" int ccvs_mjpeg_encode_optimized(const uint8_t* rgb, long frame_stride, int n, int h, int w, int quality, int sampling, int restart_mcus,
+                                           uint8_t* stream, long capacity, long* offsets, uint8_t* tables, void* workspace, void* hip_stream) {
+    const char* who = "ccvs_mjpeg_encode_optimized";
+    CCVS_REQUIRE(sampling >= 0 && sampling <= 2, "%s: sampling %d is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)", who, sampling);
+    CCVS_REQUIRE(tables, "%s: null tables", who);
+    // libjpeg's own search for the smallest frequency stops at 10^9; a frame of 2^28 pixels emits at most 2^29 symbols per table
+    CCVS_REQUIRE((long)h * w <= (1L << 28), "%s: frame size %d x %d has more than 2^28 pixels: its symbol counts could pass libjpeg's limit of 10^9", who, h, w);
+    return jpeg_encode(who, rgb, frame_stride, n, h, w, quality, sampling, restart_mcus, stream, capacity, offsets, tables, workspace, hip_stream);
 }

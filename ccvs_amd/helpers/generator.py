@@ -597,7 +597,7 @@ class Generator:
         bs = out["real"].shape[0]
         fmt = getattr(self.opt, "video_format", "auto")
         how = dict(video_format=None if fmt == "auto" else fmt, quality=getattr(self.opt, "video_quality", 90), return_clip=False,
-                   subsampling=getattr(self.opt, "video_subsampling", "444"))
+                   subsampling=getattr(self.opt, "video_subsampling", "444"), optimize=bool(getattr(self.opt, "video_optimize", False)))
         for name in ("real", "fake", "rec", "blur"):                       # generator.py:191-212
             item = out.get(name)
             if item is None:
@@ -712,13 +712,15 @@ _SUBSAMPLING = {"444": 0, "422": 1, "420": 2}     # --video_subsampling -> the e
 
 
 def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, span, dataset, state=None, cat=None, idx=None,
-                     is_layout=False, video_format=None, quality=90, return_clip=True, subsampling="444"):
+                     is_layout=False, video_format=None, quality=90, return_clip=True, subsampling="444", optimize=False):
     """helpers/generator.py:285-333.  The clamp / rescale / uint8 / channels-last pack runs on the GPU.  video_format:
       None    mp4 when torchvision is importable, else .npy uint8 [T,H,W,3];
       "npy"   the arrays, whatever imports;
       "avi"   Motion-JPEG AVI (`ccvs_amd.tools.mjpeg`): the packed clip is JPEG-encoded on the device at `quality` (`ops.mjpeg_encode`,
               libjpeg's bytes) and the compressed scans are what is copied out for the files.  subsampling: "444" (full chrominance),
-              "422" or "420" -- the chrominance sampling of these files; the other formats do not look at it.
+              "422" or "420" -- the chrominance sampling of these files; the other formats do not look at it.  optimize: every frame
+              is coded with Huffman tables built for it and carries them in its own header (`ops.mjpeg_encode_optimized`: what libjpeg
+              writes with optimize_coding) -- the same pixels in fewer bytes; the other formats do not look at it either.
     Returns the uint8 clip on the host; `return_clip=False` lets the "avi" form skip that copy where no state marker needs it (then
     only the compressed scans cross to the host, and None is returned)."""
     if is_layout:
@@ -756,14 +758,15 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
         from ccvs_amd.tools import mjpeg
         t, (h, w) = u8.size(1), u8.shape[2:4]
         sampling = _SUBSAMPLING[subsampling]
-        scans, off = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), quality, sampling=sampling)
+        scans, off, *tables = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), quality, sampling=sampling, optimize=optimize)
         head = mjpeg.jpeg_header(h, w, quality, sampling=sampling)
+        heads = [mjpeg.jpeg_header(h, w, quality, sampling=sampling, huffman=mjpeg.huffman_from_spec(spec)) for spec in tables[0]] if optimize else None
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'
         stem = os.path.join(path, f"vid_{bs * global_iter + i:05d}{suffix}")
         if video_format == "avi":
-            mjpeg.write_avi(stem + ".avi", [head + scans[off[k]:off[k + 1]] + mjpeg.EOI for k in range(i * t, (i + 1) * t)], fps, h, w)
+            mjpeg.write_avi(stem + ".avi", [(heads[k] if optimize else head) + scans[off[k]:off[k + 1]] + mjpeg.EOI for k in range(i * t, (i + 1) * t)], fps, h, w)
         elif write_video is not None:
             write_video(stem + ".mp4", u8[i], fps)
         else:

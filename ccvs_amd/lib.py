@@ -34,6 +34,8 @@ DECODE_EXPORTS = ["ccvs_mjpeg_decode_workspace_bytes", "ccvs_mjpeg_decode"]
 VIDEO_EXPORTS = ["ccvs_ingest_f32"]
 # every symbol include/ccvs_hip_output_sampled.h declares (the output stage writing 4:2:2 and 4:2:0 as well; included by ccvs_hip.h too)
 OUTPUT_SAMPLED_EXPORTS = ["ccvs_mjpeg_sampled_workspace_bytes", "ccvs_mjpeg_encode_sampled"]
+# every symbol include/ccvs_hip_output_optimized.h declares (the output stage with per-frame optimised Huffman tables; included by ccvs_hip.h too)
+OUTPUT_OPTIMIZED_EXPORTS = ["ccvs_mjpeg_optimized_workspace_bytes", "ccvs_mjpeg_encode_optimized"]
 # every symbol include/ccvs_hip_lpips.h declares (the memory-bound passes of LPIPS around its convolutions; included by ccvs_hip.h too)
 LPIPS_EXPORTS = ["ccvs_lpips_prep", "ccvs_relu_", "ccvs_relu_maxpool2", "ccvs_lpips_layer_workspace_bytes", "ccvs_lpips_layer"]
 # every symbol include/ccvs_hip_fvd.h declares (the passes of the FVD embedding around its I3D convolutions; included by ccvs_hip.h too)
@@ -121,6 +123,8 @@ def load():
     lib.ccvs_mjpeg_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_mjpeg_sampled_workspace_bytes.restype = C.c_size_t
     lib.ccvs_mjpeg_sampled_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ccvs_mjpeg_optimized_workspace_bytes.restype = C.c_size_t
+    lib.ccvs_mjpeg_optimized_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_mjpeg_decode_workspace_bytes.restype = C.c_size_t
     lib.ccvs_mjpeg_decode_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_lpips_layer_workspace_bytes.restype = C.c_int64
@@ -184,6 +188,7 @@ def load():
         "ccvs_code_perplexity": [vp, i32, i64, vp, vp],
         "ccvs_mjpeg_encode": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_mjpeg_encode_sampled": [vp, C.c_long, i32, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
+        "ccvs_mjpeg_encode_optimized": [vp, C.c_long, i32, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp, vp],
         "ccvs_mjpeg_decode": [vp, C.c_long, vp, vp, C.c_long, vp, i32, vp, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_lpips_prep": [vp, vp, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), vp],
         "ccvs_relu_": [vp, i64, vp],

@@ -1455,6 +1455,23 @@ def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None, sam
     the offsets on the host (`mjpeg_encode_to_host` does).  out: optional uint8 stream to write into (its length is the capacity).
     `ccvs_amd.tools.mjpeg.jpeg_header(h, w, quality, restart_mcus, sampling)` + scan + EOI is a JPEG file.  Runs on the current stream; nothing
     is synchronised."""
+    frames, n, h, w, sampling, r, stream, capacity, offsets = _mjpeg_encode_args("mjpeg_encode", u8, restart_mcus, capacity, out, sampling)
+    L = _lib.load()
+    dev = u8.device
+    if sampling == 0:
+        work = torch.empty(max(int(L.ccvs_mjpeg_workspace_bytes(n, h, w, r)), 8), dtype=torch.uint8, device=dev)
+        _lib.check(L.ccvs_mjpeg_encode(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), r, _p(stream), int(capacity),
+                                       _p(offsets), _p(work), _stream()), "ccvs_mjpeg_encode")
+    else:
+        work = torch.empty(max(int(L.ccvs_mjpeg_sampled_workspace_bytes(n, h, w, sampling, r)), 8), dtype=torch.uint8, device=dev)
+        _lib.check(L.ccvs_mjpeg_encode_sampled(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), sampling, r, _p(stream),
+                                               int(capacity), _p(offsets), _p(work), _stream()), "ccvs_mjpeg_encode_sampled")
+    return stream, offsets
+
+
+def _mjpeg_encode_args(who, u8, restart_mcus, capacity, out, sampling):
+    """What the encoders share: the frames as [n, H, W, 3] with dense rows (a view where the strides allow), the sampling and restart
+    interval checked / defaulted, the stream (`out`, or `capacity` bytes) and the offsets tensor."""
     _need_gpu(u8, out)
     assert u8.dtype == torch.uint8 and u8.dim() >= 3 and u8.shape[-1] == 3, (u8.dtype, u8.shape)
     h, w = int(u8.shape[-3]), int(u8.shape[-2])
@@ -1469,7 +1486,7 @@ def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None, sam
     n = int(frames.shape[0])
     sampling = int(sampling)
     if sampling not in (0, 1, 2):
-        raise ValueError(f"mjpeg_encode: sampling {sampling} is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)")
+        raise ValueError(f"{who}: sampling {sampling} is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)")
     mw = 16 if sampling else 8
     r = min((w + mw - 1) // mw, (32, 24, 16)[sampling]) if restart_mcus is None else int(restart_mcus)
     if out is not None:
@@ -1477,31 +1494,41 @@ def mjpeg_encode(u8, quality=90, restart_mcus=None, capacity=None, out=None, sam
         capacity = out.numel()
     elif capacity is None:
         capacity = n * h * w * 3
+    stream = out if out is not None else torch.empty(int(capacity), dtype=torch.uint8, device=u8.device)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=u8.device)
+    return frames, n, h, w, sampling, r, stream, int(capacity), offsets
+
+
+def mjpeg_encode_optimized(u8, quality=90, restart_mcus=None, capacity=None, out=None, sampling=0):
+    """`mjpeg_encode` with per-frame optimised Huffman tables (`ccvs_mjpeg_encode_optimized`, include/ccvs_hip_output_optimized.h: the
+    bytes libjpeg writes with optimize_coding, bit for bit): returns (stream, offsets, tables).  stream and
+    offsets are what `mjpeg_encode` returns -- the same coefficients, coded with each frame's own tables -- and `tables` (uint8
+    [n, 4, 272], on the device) holds every frame's four tables in DHT order as bits[16] + huffval, zero-padded:
+    `tools.mjpeg.huffman_from_spec(tables[i].cpu().numpy())` is the `huffman` argument of `tools.mjpeg.jpeg_header` for frame i.  Frames,
+    strides, the default restart interval, capacity and `out` are handled as in `mjpeg_encode`.  Runs on the current stream; nothing
+    is synchronised."""
+    frames, n, h, w, sampling, r, stream, capacity, offsets = _mjpeg_encode_args("mjpeg_encode_optimized", u8, restart_mcus, capacity, out, sampling)
     L = _lib.load()
-    dev = u8.device
-    stream = out if out is not None else torch.empty(int(capacity), dtype=torch.uint8, device=dev)
-    offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
-    if sampling == 0:
-        work = torch.empty(max(int(L.ccvs_mjpeg_workspace_bytes(n, h, w, r)), 8), dtype=torch.uint8, device=dev)
-        _lib.check(L.ccvs_mjpeg_encode(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), r, _p(stream), int(capacity),
-                                       _p(offsets), _p(work), _stream()), "ccvs_mjpeg_encode")
-    else:
-        work = torch.empty(max(int(L.ccvs_mjpeg_sampled_workspace_bytes(n, h, w, sampling, r)), 8), dtype=torch.uint8, device=dev)
-        _lib.check(L.ccvs_mjpeg_encode_sampled(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), sampling, r, _p(stream),
-                                               int(capacity), _p(offsets), _p(work), _stream()), "ccvs_mjpeg_encode_sampled")
-    return stream, offsets
+    tables = torch.empty((n, 4, 272), dtype=torch.uint8, device=u8.device)
+    work = torch.empty(max(int(L.ccvs_mjpeg_optimized_workspace_bytes(n, h, w, sampling, r)), 8), dtype=torch.uint8, device=u8.device)
+    _lib.check(L.ccvs_mjpeg_encode_optimized(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, int(quality), sampling, r, _p(stream),
+                                             int(capacity), _p(offsets), _p(tables), _p(work), _stream()), "ccvs_mjpeg_encode_optimized")
+    return stream, offsets, tables
 
 
-def mjpeg_encode_to_host(u8, quality=90, restart_mcus=None, sampling=0):
+def mjpeg_encode_to_host(u8, quality=90, restart_mcus=None, sampling=0, optimize=False):
     """`mjpeg_encode` (sampling: 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0), then the scans on the host: (bytes of all scans, list of n + 1
     offsets).  The first run's stream has the
     frames' raw size; where the scans are larger than that (noise at quality 100) the offsets say by how much and a second run with
-    that capacity is exact.  What crosses to the host is the offsets and the compressed bytes, not the stream's capacity."""
-    stream, offsets = mjpeg_encode(u8, quality, restart_mcus, sampling=sampling)
-    off = offsets.cpu().tolist()
-    if off[-1] > stream.numel():
-        stream, _ = mjpeg_encode(u8, quality, restart_mcus, capacity=off[-1], sampling=sampling)
-    return stream[:off[-1]].cpu().numpy().tobytes(), off
+    that capacity is exact.  What crosses to the host is the offsets and the compressed bytes, not the stream's capacity.
+    optimize: `mjpeg_encode_optimized` instead, and a third result: the frames' tables (uint8 numpy [n, 4, 272])."""
+    encode = mjpeg_encode_optimized if optimize else mjpeg_encode
+    res = encode(u8, quality, restart_mcus, sampling=sampling)
+    off = res[1].cpu().tolist()
+    if off[-1] > res[0].numel():
+        res = encode(u8, quality, restart_mcus, capacity=off[-1], sampling=sampling)
+    scans = res[0][:off[-1]].cpu().numpy().tobytes()
+    return (scans, off, res[2].cpu().numpy()) if optimize else (scans, off)
 
 
 # ------------------------------------------------------------------ the way back (include/ccvs_hip_decode.h)

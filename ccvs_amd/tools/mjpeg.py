@@ -1,8 +1,10 @@
 """Motion-JPEG AVI files around the scans `ops.mjpeg_encode` writes.  Host only: no torch, no GPU.
 
   jpeg_header(h, w, quality, restart_mcus,   the bytes in front of a frame's scan: SOI, DQT x 2, SOF0 (8 bit, three components; luminance
-              sampling)                      sampled 1 x 1, 2 x 1 or 2 x 2 for sampling 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0, chrominance 1 x 1),
-                                             DHT x 4 (the Annex K tables), DRI, SOS.  header + scan + EOI is a JPEG file.
+              sampling, huffman)             sampled 1 x 1, 2 x 1 or 2 x 2 for sampling 0 / 1 / 2 = 4:4:4 / 4:2:2 / 4:2:0, chrominance 1 x 1),
+                                             DHT x 4 (the Annex K tables, or the frame's own: `huffman`), DRI, SOS.  header + scan + EOI is
+                                             a JPEG file.
+  huffman_from_spec(spec)                    a frame's row of `ops.mjpeg_encode_optimized`'s tables (uint8 [4, 272]) as that `huffman`.
   write_avi(path, frames, fps, h, w)         RIFF 'AVI ': hdrl (avih, one strl: strh vids/MJPG + strf BITMAPINFOHEADER), a movi list of
                                              '00dc' chunks padded to even length, idx1.
   read_avi(path) -> (fps, h, w, [jpeg])      the frames of such a file, byte for byte.
@@ -76,9 +78,25 @@ def _segment(marker, payload):
     return bytes([0xFF, marker]) + struct.pack(">H", len(payload) + 2) + payload
 
 
-def jpeg_header(h, w, quality, restart_mcus=None, sampling=0):
+def huffman_from_spec(spec):
+    """The `huffman` argument of `jpeg_header` from one frame's row of the optimised encoder's `tables` (uint8 [4, 272]: per table
+    bits[16] + huffval, zero-padded; DC luminance, AC luminance, DC chrominance, AC chrominance): four (bits, vals) of bytes."""
+    out = []
+    for row in spec:
+        row = bytes(bytearray(row))
+        if len(row) != 272 or sum(row[:16]) > 256:
+            raise ValueError("huffman_from_spec: a table is 272 bytes, bits[16] + up to 256 symbols")
+        out.append((row[:16], row[16:16 + sum(row[:16])]))
+    if len(out) != 4:
+        raise ValueError(f"huffman_from_spec: {len(out)} tables, a frame has 4")
+    return tuple(out)
+
+
+def jpeg_header(h, w, quality, restart_mcus=None, sampling=0, huffman=None):
     """Everything in front of the scan of an h x w frame encoded at `quality` with a restart interval of `restart_mcus` MCUs (of the
-    sampling's size; None: `default_restart(w, sampling)`).  sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0."""
+    sampling's size; None: `default_restart(w, sampling)`).  sampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0.  huffman: None for the Annex K
+    tables, else the frame's own four (bits, vals) -- DC luminance, AC luminance, DC chrominance, AC chrominance, the order in which
+    libjpeg writes them and `huffman_from_spec` gives them -- written as the DHT segments in the same place."""
     h, w = int(h), int(w)
     if sampling not in (0, 1, 2):
         raise ValueError(f"jpeg_header: sampling {sampling!r} is none of 0 (4:4:4), 1 (4:2:2), 2 (4:2:0)")
@@ -89,7 +107,14 @@ def jpeg_header(h, w, quality, restart_mcus=None, sampling=0):
     for t, table in enumerate(quant_tables(quality)):
         out += _segment(0xDB, bytes([t]) + bytes(table[k] for k in ZIGZAG))
     out += _segment(0xC0, struct.pack(">BHHB", 8, h, w, 3) + bytes([1, _Y_FACTORS[sampling], 0, 2, 0x11, 1, 3, 0x11, 1]))
-    for key, (bits, vals) in HUFF.items():
+    if huffman is None:
+        tables = HUFF
+    else:
+        huffman = tuple(huffman)
+        tables = {key: (bytes(bits), bytes(vals)) for key, (bits, vals) in zip(HUFF, huffman)}
+        if len(huffman) != 4 or any(len(bits) != 16 or sum(bits) != len(vals) or len(vals) > 256 for bits, vals in tables.values()):
+            raise ValueError("jpeg_header: huffman is four (bits[16], vals) with sum(bits) == len(vals) <= 256")
+    for key, (bits, vals) in tables.items():
         out += _segment(0xC4, bytes([key]) + bits + vals)
     out += _segment(0xDD, struct.pack(">H", r))
     out += _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))

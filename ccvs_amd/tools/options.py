@@ -106,9 +106,12 @@ class Options:
         # avi -- Motion-JPEG AVI, the JPEG encoder on the GPU (csrc/jpeg.hip: libjpeg's bytes at --video_quality).
         # --video_subsampling: the avi files' chrominance sampling, 444 (full chrominance: what evaluation should score), 422 or 420 (what
         # players and other tools expect, smaller files); ignored unless the files are avi
+        # --video_optimize: every avi frame carries Huffman tables built for it (libjpeg's optimize_coding; the same pixels, smaller
+        # files, a slower encode); ignored unless the files are avi
         p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi"])
         p.add_argument("--video_quality", type=_jpeg_quality, default=90)
         p.add_argument("--video_subsampling", type=str, default="444", choices=["444", "422", "420"])
+        _flag(p, "--video_optimize")
         # ---- q_: quantised video model (tools/options.py:159-264)
         p.add_argument("--q_enc_model", type=str, default="taming")
         p.add_argument("--q_dec_model", type=str, default="stylegan2")

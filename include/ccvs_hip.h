@@ -491,6 +491,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_video.h"
 /* the output stage with chrominance subsampling (4:2:2 and 4:2:0 scans, libjpeg-exact), additive to ABI version 6, likewise */
 #include "ccvs_hip_output_sampled.h"
+/* the output stage with per-frame optimised Huffman tables (libjpeg's optimize_coding, bit for bit), additive to ABI version 6, likewise */
+#include "ccvs_hip_output_optimized.h"
 /* the memory-bound passes of LPIPS around its VGG16 convolutions (normalise, ReLU, ReLU + pool, a tapped layer's distance), additive to ABI version 6, likewise */
 #include "ccvs_hip_lpips.h"
 /* the passes of the FVD embedding around its I3D convolutions (TF preprocess, time unfold, SAME max pools, the head), additive to ABI version 6, likewise */
