@@ -39,7 +39,9 @@ extern "C" int ccvs_gpt_embed(const int64_t* idx, int64_t idx_sB, const int32_t*
 }
 
 // ---------------------------------------------------------------------------------------
-// LayerNorm (eps 1e-5), one wave per row.
+// LayerNorm (eps 1e-5), one wave per row.  The row is shifted by its first element before anything is summed: the terms of
+// the mean then have the size of the row's spread, not of its mean (a row of mean 1e3 and std 1 keeps fp32 accuracy relative
+// to its std; a constant row gives exactly beta).
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, float* __restrict__ y, int rows, int C) {
@@ -47,14 +49,15 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     const float* xr = x + (long)row * C;
+    const float x0 = xr[0];
     float s = 0.f;
-    for (int c = lane; c < C; c += 64) s += xr[c];
-    const float mean = wave_sum(s) / C;
+    for (int c = lane; c < C; c += 64) s += xr[c] - x0;
+    const float mean = wave_sum(s) / C;   // of x - x0
     float v = 0.f;
-    for (int c = lane; c < C; c += 64) { const float d = xr[c] - mean; v += d * d; }
+    for (int c = lane; c < C; c += 64) { const float d = (xr[c] - x0) - mean; v += d * d; }
     const float rstd = rsqrtf(wave_sum(v) / C + 1e-5f);
     float* yr = y + (long)row * C;
-    for (int c = lane; c < C; c += 64) yr[c] = (xr[c] - mean) * rstd * g[c] + b[c];
+    for (int c = lane; c < C; c += 64) yr[c] = ((xr[c] - x0) - mean) * rstd * g[c] + b[c];
 }
 
 extern "C" int ccvs_layernorm(const float* x, const float* gamma, const float* beta, float* y, int32_t rows, int32_t C, void* stream) {

@@ -566,6 +566,85 @@ def test_gpt_embed_pack(ops):
     assert torch.equal(ops.pack_u8(vid.cuda()).cpu(), O.pack_u8(vid))
 
 
+@pytest.mark.parametrize("C", [1, 33, 1024])
+def test_gpt_embed_clamp_offsets_and_column_view(ops, C):
+    """gpt_embed_kernel, bit for bit (each element is one fp32 add of two table entries): token ids below 0 and at or above
+    `vocab` read rows 0 and vocab - 1; the positional row is pos_off[b] + pos0 + *pos_dev + t with all three present; idx as a
+    dense [B,Tq] tensor and as a [B,1] column view of a wider int64 buffer (row stride 11, as the decode step passes it)."""
+    g = torch.Generator().manual_seed(C)
+    vocab, npos, B, Tq = 50, 40, 3, 7
+    tok, pos = torch.randn(vocab, C, generator=g), torch.randn(npos, C, generator=g)
+    idx = torch.randint(0, vocab, (B, Tq), generator=g)
+    idx[0, 0], idx[0, 1], idx[1, 2], idx[2, 6], idx[2, 5] = -1, -(2 ** 40), vocab, 2 ** 40, vocab - 1
+    off = torch.tensor([0, 5, 9], dtype=torch.int32)
+    pos0, pdev = 2, 17
+    prow = (off.long().view(B, 1) + pos0 + pdev + torch.arange(Tq).view(1, Tq)).view(-1)
+    assert int(prow.max()) == npos - 6
+    want = tok[idx.clamp(0, vocab - 1).view(-1)] + pos[prow]
+    pos_dev = torch.tensor([pdev], dtype=torch.int32).cuda()
+    got = ops.gpt_embed(idx.cuda(), tok.cuda(), pos.cuda(), pos0, off.cuda(), pos_dev)
+    assert got.shape == (B * Tq, C) and torch.equal(got.cpu(), want)
+    wide = torch.randint(0, vocab, (B, 11), generator=g)
+    wide[0, 4], wide[2, 4] = -3, vocab + 3
+    wide[:, 3], wide[:, 5] = 2 ** 40, -(2 ** 40)     # the neighbouring columns would clamp to other rows
+    col = wide.cuda()[:, 4:5]
+    assert col.stride(0) == 11
+    want = tok[wide[:, 4].clamp(0, vocab - 1)] + pos[off.long() + pos0 + pdev]
+    assert torch.equal(ops.gpt_embed(col, tok.cuda(), pos.cuda(), pos0, off.cuda(), pos_dev).cpu(), want)
+
+
+def test_kv_append_strided_views_at_a_device_position(ops):
+    """kv_append_kernel: Tq = 5 rows of the K and V thirds of a [B,Tq,3*H*D] QKV buffer land at pos0 + *pos_dev of both caches
+    bit for bit, and nothing else of the sentinel-filled caches changes."""
+    g = torch.Generator().manual_seed(5)
+    B, H, D, Tq, Tmax, pos0, pdev = 2, 3, 16, 5, 23, 4, 9
+    qkv = torch.randn(B, Tq, 3 * H * D, generator=g)
+    dev = qkv.cuda()
+    k, v = dev[..., H * D:2 * H * D], dev[..., 2 * H * D:]
+    assert k.stride() == (Tq * 3 * H * D, 3 * H * D, 1)
+    kc, vc = torch.full((B, H, Tmax, D), -7.0).cuda(), torch.full((B, H, Tmax, D), -9.0).cuda()
+    ops.kv_append(k, v, kc, vc, pos0, torch.tensor([pdev], dtype=torch.int32).cuda())
+    lo, hi = pos0 + pdev, pos0 + pdev + Tq
+    for c, third, fill in ((kc.cpu(), 1, -7.0), (vc.cpu(), 2, -9.0)):
+        want = qkv[..., third * H * D:(third + 1) * H * D].view(B, Tq, H, D).transpose(1, 2)
+        assert torch.equal(c[:, :, lo:hi], want)
+        assert (c[:, :, :lo] == fill).all() and (c[:, :, hi:] == fill).all()
+
+
+@pytest.mark.parametrize("C", [1, 63, 64, 65, 1024])
+@pytest.mark.parametrize("rows", [1, 4, 5])
+def test_layernorm_vs_float64(ops, rows, C):
+    """layernorm_kernel (one wave per row, 4 rows per workgroup: rows 1 / 4 / 5 = a part-filled, a full and a second workgroup;
+    C below, on and above the 64 lanes, and 16 elements per lane) against float64, with the last row constant (y must be
+    exactly beta: every x - mean is 0) and, where there are more rows, row 0 of mean 1e3 and std 1.
+
+    Tolerance eps32 * (8 |y| + |gamma| sqrt(C) + |beta|), per element, from y = xhat gamma + beta with xhat = (x - mean) rstd:
+      * the product xhat gamma and the sum with beta round once each, and rstd (a mean of C squares, rsqrtf) and x - mean carry
+        a few ulp of relative error into xhat: a handful of eps32 relative to |xhat gamma| <= |y| + |beta|: 8 eps |y| and
+        eps |beta| (the latter only for the part of xhat gamma that beta cancels);
+      * the mean is a sum of C terms; its rounding errors add up like a random walk, sqrt(C) eps times the size of a term, and
+        reach y multiplied by rstd gamma.  With terms of the size of the row's spread (rstd x term ~ 1) that is
+        eps sqrt(C) |gamma|.  A kernel that sums the raw x instead has terms of size |mean|, not of the spread, and loses
+        |mean| / std of this: the row of mean 1e3 is here to say so (summing the raw x, the kernel reached 83 x this tolerance
+        on that row and 2.5 x on a constant row of 0.1 at C = 1024; shifted by the row's first element it stays below 0.55)."""
+    g = torch.Generator().manual_seed(100 * rows + C)
+    x = torch.randn(rows, C, generator=g)
+    if rows > 1:
+        x[0] = 1e3 + torch.randn(C, generator=g)
+    x[rows - 1] = 0.1 if rows == 1 else 1e3 / 3
+    gam, bet = torch.randn(C, generator=g) * 0.3 + 1.0, torch.randn(C, generator=g)
+    got = ops.layernorm(x.cuda(), gam.cuda(), bet.cuda()).cpu()
+    xd, gd, bd = x.double(), gam.double(), bet.double()
+    mean = xd.mean(-1, keepdim=True)
+    var = ((xd - mean) ** 2).mean(-1, keepdim=True)
+    want = (xd - mean) / torch.sqrt(var + 1e-5) * gd + bd
+    tol = 2.0 ** -24 * (8 * want.abs() + gd.abs() * C ** 0.5 + bd.abs())
+    ratio = ((got.double() - want).abs() / tol).amax(-1)
+    print(f"layernorm rows={rows} C={C}: max err/tol per row = {[round(r, 3) for r in ratio.tolist()]}")
+    assert torch.equal(got[rows - 1], bet), "a constant row must give exactly beta"
+    assert ratio.max().item() <= 1.0
+
+
 @pytest.mark.parametrize("V,n,top_k", [(1024, 4, 100), (16384, 3, 50), (200, 5, None)])
 def test_sample_topn_vs_oracle(ops, V, n, top_k):
     """ccvs_sample_topn (the n proposals of beam search + their log p, get_icode with n > 1, transformer_model.py:395-409):
@@ -755,8 +834,12 @@ def test_attention_decode_long_cache(ops, D):
     torch.manual_seed(D)
     B, H, Tmax = 2, 3, 2200
     kc, vc = torch.randn(B, H, Tmax, D).cuda(), torch.randn(B, H, Tmax, D).cuda()
-    batch = 8 * (64 // (D // 4)) * 8
-    lens = sorted({1, 2, batch - 1, batch, batch + 1, 2 * batch, 2 * batch + 7, min(3 * batch + 5, Tmax)})
+    lens = {1, 2}
+    # the kernel's register batch (4 waves x 64 / (D/4) rows x 4 in flight per lane), and four times it: the lengths this test
+    # has tried since an older kernel with that batch
+    for batch in (16 * (64 // (D // 4)), 64 * (64 // (D // 4))):
+        lens |= {batch - 1, batch, batch + 1, 2 * batch, 2 * batch + 7, min(3 * batch + 5, Tmax)}
+    lens = sorted(lens)
     for L in lens:
         q = torch.randn(B, 1, H * D).cuda()
         got = ops.attention(q, kc, vc, L - 1)   # query at position L-1 sees keys 0..L-1
