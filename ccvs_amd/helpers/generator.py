@@ -721,12 +721,15 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
               "422" or "420" -- the chrominance sampling of these files; the other formats do not look at it.  optimize: every frame
               is coded with Huffman tables built for it and carries them in its own header (`ops.mjpeg_encode_optimized`: what libjpeg
               writes with optimize_coding) -- the same pixels in fewer bytes; the other formats do not look at it either.
-    Returns the uint8 clip on the host; `return_clip=False` lets the "avi" form skip that copy where no state marker needs it (then
-    only the compressed scans cross to the host, and None is returned)."""
+      "apng"  lossless: one animated PNG `vid_XXXXX.png` per clip (`ccvs_amd.tools.apng`): the packed clip is PNG-filtered and
+              deflate-coded on the device (`ops.png_encode`) and the compressed streams are what is copied out.
+              Browsers, ffmpeg and Pillow open the files; `quality`, `subsampling` and `optimize` are not looked at.
+    Returns the uint8 clip on the host; `return_clip=False` lets the "avi" and "apng" forms skip that copy where no state marker needs
+    it (then only the compressed bytes cross to the host, and None is returned)."""
     if is_layout:
         raise NotImplementedError("layout colour maps are not on the MI355X path (SURVEY 8f)")
-    if video_format not in (None, "npy", "avi"):
-        raise ValueError(f"save_video_batch: video_format {video_format!r} is none of None, 'npy', 'avi'")
+    if video_format not in (None, "npy", "avi", "apng"):
+        raise ValueError(f"save_video_batch: video_format {video_format!r} is none of None, 'npy', 'avi', 'apng'")
     if subsampling not in _SUBSAMPLING:
         raise ValueError(f"save_video_batch: subsampling {subsampling!r} is none of '444', '422', '420'")
     if normalize and imagenet_norm:
@@ -736,7 +739,7 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
     else:
         u8 = (vid.permute(0, 1, 3, 4, 2) * 255).to(torch.uint8)
     dev_u8 = u8
-    if return_clip or video_format != "avi" or state is not None:
+    if return_clip or video_format not in ("avi", "apng") or state is not None:
         u8 = u8.cpu()
     if state is not None:  # generator.py:311-323: mark the (x, y) state on every frame
         res = {"bair": 64, "bairhd": 256}.get(dataset)
@@ -746,7 +749,7 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
                 for j in range(u8.size(1)):
                     x, y = st[i, j]
                     u8[i, j] = draw_cross(u8[i, j], min(int(res * x), res - 1), min(int(res * y), res - 1))
-            dev_u8 = None  # the marked clip is the one to write: "avi" uploads it again (rare and small)
+            dev_u8 = None  # the marked clip is the one to write: "avi" and "apng" upload it again (rare and small)
     os.makedirs(path, exist_ok=True)
     write_video = None
     if video_format is None:
@@ -761,12 +764,18 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
         scans, off, *tables = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), quality, sampling=sampling, optimize=optimize)
         head = mjpeg.jpeg_header(h, w, quality, sampling=sampling)
         heads = [mjpeg.jpeg_header(h, w, quality, sampling=sampling, huffman=mjpeg.huffman_from_spec(spec)) for spec in tables[0]] if optimize else None
+    elif video_format == "apng":
+        from ccvs_amd.tools import apng
+        t, (h, w) = u8.size(1), u8.shape[2:4]
+        zbytes, off = ops.png_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device))
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'
         stem = os.path.join(path, f"vid_{bs * global_iter + i:05d}{suffix}")
         if video_format == "avi":
             mjpeg.write_avi(stem + ".avi", [(heads[k] if optimize else head) + scans[off[k]:off[k + 1]] + mjpeg.EOI for k in range(i * t, (i + 1) * t)], fps, h, w)
+        elif video_format == "apng":
+            apng.write_apng(stem + ".png", [zbytes[off[k]:off[k + 1]] for k in range(i * t, (i + 1) * t)], fps, h, w)
         elif write_video is not None:
             write_video(stem + ".mp4", u8[i], fps)
         else:

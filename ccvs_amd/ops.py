@@ -1531,6 +1531,57 @@ def mjpeg_encode_to_host(u8, quality=90, restart_mcus=None, sampling=0, optimize
     return (scans, off, res[2].cpu().numpy()) if optimize else (scans, off)
 
 
+# ------------------------------------------------------------------ lossless output stage (include/ccvs_hip_output_lossless.h)
+def png_encode(u8, filter=-1, band_rows=0, capacity=None, out=None):
+    """One zlib stream per frame of uint8 frames [..., H, W, 3] on the device (`ccvs_apng_encode`): PNG's row
+    filters, then Huffman-only deflate with dynamic tables -- the payload of a PNG IDAT / APNG fdAT chunk (`ccvs_amd.tools.apng`
+    writes the container).  Returns (stream uint8 [capacity], offsets int64 [n + 1]), both on the device -- frame i's stream is
+    stream[offsets[i]:offsets[i + 1]].  filter: -1 = per row the type with the smallest sum of |signed byte| (libpng's heuristic),
+    0 .. 4 = None, Sub, Up, Average, Paeth for every row.  band_rows: rows per deflate block (0: about 32 KiB of filtered bytes).
+    Frames and strides are handled as in `mjpeg_encode`.  capacity: bytes of `stream` (None: 9/8 of the filtered size plus 470 bytes
+    per band, which noise does not fill); the offsets are complete also when offsets[n] > capacity, nothing at or beyond `capacity` is
+    written, and the CALLER runs again with a larger one (`png_encode_to_host` does; `ccvs_apng_stream_bound` always suffices).
+    out: optional uint8 stream to write into (its length is the capacity).  Runs on the current stream; nothing is synchronised."""
+    _need_gpu(u8, out)
+    assert u8.dtype == torch.uint8 and u8.dim() >= 3 and u8.shape[-1] == 3, (u8.dtype, u8.shape)
+    h, w = int(u8.shape[-3]), int(u8.shape[-2])
+    frames = u8.reshape(1, h, w, 3) if u8.dim() == 3 else u8
+    if frames.stride()[-3:] != (3 * w, 3, 1):
+        frames = frames.contiguous()
+    if frames.dim() > 4:
+        try:
+            frames = frames.view(-1, h, w, 3)      # leading axes of one regular stride
+        except RuntimeError:
+            frames = frames.reshape(-1, h, w, 3)
+    n, filter, band_rows = int(frames.shape[0]), int(filter), int(band_rows)
+    if n > 1 and frames.stride(0) < 3 * w * h:     # (an expanded frame axis)
+        frames = frames.contiguous()
+    L = _lib.load()
+    if out is not None:
+        assert out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous() and capacity in (None, out.numel()), (out.dtype, out.shape)
+        capacity = out.numel()
+    elif capacity is None:
+        rows = band_rows if band_rows > 0 else max(1, 32768 // (3 * w + 1))
+        capacity = n * (6 + h * (3 * w + 1) * 9 // 8 + 470 * ((h + rows - 1) // rows))
+    stream = out if out is not None else torch.empty(int(capacity), dtype=torch.uint8, device=u8.device)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=u8.device)
+    work = torch.empty(max(int(L.ccvs_apng_workspace_bytes(n, h, w, max(band_rows, 0))), 8), dtype=torch.uint8, device=u8.device)
+    _lib.check(L.ccvs_apng_encode(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, filter, band_rows, _p(stream), int(capacity),
+                                  _p(offsets), _p(work), _stream()), "ccvs_apng_encode")
+    return stream, offsets
+
+
+def png_encode_to_host(u8, filter=-1, band_rows=0):
+    """`png_encode`, then the streams on the host: (bytes of all frames' zlib streams, list of n + 1 offsets).  Where the first run's
+    stream is too small the offsets say by how much and a second run with that capacity is exact.  What crosses to the host is the
+    offsets and offsets[n] compressed bytes."""
+    stream, offsets = png_encode(u8, filter, band_rows)
+    off = offsets.cpu().tolist()
+    if off[-1] > stream.numel():
+        stream, offsets = png_encode(u8, filter, band_rows, capacity=off[-1])
+    return stream[:off[-1]].cpu().numpy().tobytes(), off
+
+
 # ------------------------------------------------------------------ the way back (include/ccvs_hip_decode.h)
 _MJPEG_STATUS = {1: "its table entry points outside the call's frames, stream, MCUs or tables", 2: "no Huffman code starts so",
                  3: "the MCUs need more bits than the unit has", 4: "a run leads past coefficient 63",

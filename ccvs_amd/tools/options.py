@@ -108,7 +108,7 @@ class Options:
         # players and other tools expect, smaller files); ignored unless the files are avi
         # --video_optimize: every avi frame carries Huffman tables built for it (libjpeg's optimize_coding; the same pixels, smaller
         # files, a slower encode); ignored unless the files are avi
-        p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi"])
+        p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi", "apng"])
         p.add_argument("--video_quality", type=_jpeg_quality, default=90)
         p.add_argument("--video_subsampling", type=str, default="444", choices=["444", "422", "420"])
         _flag(p, "--video_optimize")

@@ -12,7 +12,9 @@ Same function names and argument meaning as the reference:
                       writes) or .npy are loaded by `load_videos` below, on the GPU; for .mp4 the caller brings a `loader=` (the
                       reference's decoder is OpenCV, absent here).
   load_video(s)       metrics.py:80-97: .avi through `read_avi` and `ops.mjpeg_decode` (the JPEG decoder in HIP, DESIGN.md section
-                      4.16: libjpeg's pixels), .npy the uint8 [T, H, W, 3] arrays `run()` writes; the clips stay on the device.
+                      4.16: libjpeg's pixels), .npy the uint8 [T, H, W, 3] arrays `run()` writes, .png the lossless animated PNGs of
+                      `--video_format apng` (`tools.apng.read_apng`: inflated and un-filtered on the host, DESIGN.md section 4.22 --
+                      the exact clips, so the scores are those of the clips the model produced); the clips stay on the device.
                       `resize` other than None raises NotImplementedError (the reference's is OpenCV INTER_AREA, not reproduced).
   get_video_files, get_folder(s), print_scores, main, and the argparse block      metrics.py:92-186:
                       python -m ccvs_amd.tools.pytorch_metrics.metrics --exp_tag TAG [--real_tag --real_folder --fake_folder
@@ -166,7 +168,7 @@ def metrics_from_files(real_video_files, generated_video_files, resize, num_work
     needed for .mp4 names only -- the reference decodes those with OpenCV (metrics.py:80-97), which this image does not have, so
     without a loader they raise."""
     if loader is None:
-        if any(os.path.splitext(str(f))[1].lower() not in (".avi", ".npy") for f in list(real_video_files) + list(generated_video_files)):
+        if any(os.path.splitext(str(f))[1].lower() not in (".avi", ".npy", ".png") for f in list(real_video_files) + list(generated_video_files)):
             raise RuntimeError("metrics_from_files: no mp4 decoder here (the reference uses OpenCV); pass loader=..., or call "
                                "metrics_from_videos on the uint8 clips")
         loader = lambda files, size: load_videos(files, size, num_workers)  # noqa: E731
@@ -189,8 +191,9 @@ def load_video(file, resize):
 
 
 def get_video_files(folder):
-    """metrics.py:92-93, for the kinds of file a run writes here: the folder's *.mp4, else its *.avi, else its *.npy, sorted."""
-    for ext in ("mp4", "avi", "npy"):
+    """metrics.py:92-93, for the kinds of file a run writes here: the folder's *.mp4, else its *.avi, else its *.npy, else its *.png
+    (the animated PNGs of `--video_format apng`), sorted."""
+    for ext in ("mp4", "avi", "npy", "png"):
         files = sorted(glob(os.path.join(folder, "*." + ext)))
         if files:
             return files
@@ -211,7 +214,14 @@ def load_videos(video_files, resize, num_workers):
             if c.dtype != np.uint8 or c.ndim != 4 or c.shape[-1] != 3 or c.shape != clips[0].shape:
                 raise ValueError(f"load_videos: {f} holds {c.dtype} {c.shape}, not a uint8 [T, H, W, 3] clip of the batch's shape")
         return torch.from_numpy(np.stack(clips)).cuda()
-    raise RuntimeError(f"load_videos: files of kind(s) {sorted(kinds)}: one batch is all .avi or all .npy (no mp4 decoder here)")
+    if kinds == {".png"}:                                               # the lossless clips: inflated and un-filtered on the host, one upload
+        from ccvs_amd.tools.apng import read_apng
+        clips = [read_apng(str(f)) for f in video_files]
+        for f, c in zip(video_files, clips):
+            if c.shape != clips[0].shape:
+                raise ValueError(f"load_videos: {f} holds a clip of shape {c.shape}, not the batch's {clips[0].shape}")
+        return torch.from_numpy(np.stack(clips)).cuda()
+    raise RuntimeError(f"load_videos: files of kind(s) {sorted(kinds)}: one batch is all .avi or all .npy or all .png (no mp4 decoder here)")
 
 
 def get_folder(exp_tag, fold_i=None):

@@ -15,8 +15,8 @@ Same function names and argument meaning as the reference:
   fvd_size, fvd_full, main, parse_args    fvd.py:216-275: python -m ccvs_amd.tools.tf_fvd.fvd --exp_tag TAG [--real_tag --real_folder
                                           --fake_folder --num_folds --mode size|full|both --size 256 --fvd_weights --channel_order]
                                           prints the reference's lines for results/*TAG/{real,fake}.
-  load_videos, get_video_files, get_folder(s)   those of tools/pytorch_metrics/metrics.py: .avi (Motion-JPEG, decoded on the GPU) and
-                                          .npy clips; `--resize` raises as it does there (OpenCV's INTER_AREA is not reproduced), and
+  load_videos, get_video_files, get_folder(s)   those of tools/pytorch_metrics/metrics.py: .avi (Motion-JPEG, decoded on the GPU), .npy
+                                          and .png (lossless APNG, read on the host) clips; `--resize` raises as it does there (OpenCV's INTER_AREA is not reproduced), and
                                           .mp4 needs a `loader=`.
 
 The network's weights come from TF-Hub in the reference.  Nothing is downloaded here and no weights are in the repository, so the

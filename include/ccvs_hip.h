@@ -497,6 +497,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_lpips.h"
 /* the passes of the FVD embedding around its I3D convolutions (TF preprocess, time unfold, SAME max pools, the head), additive to ABI version 6, likewise */
 #include "ccvs_hip_fvd.h"
+/* the lossless output stage (uint8 clips -> PNG filters and Huffman-only deflate: one zlib stream per frame for an APNG), additive to ABI version 6, likewise */
+#include "ccvs_hip_output_lossless.h"
 
 #ifdef __cplusplus
 }
