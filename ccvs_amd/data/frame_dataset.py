@@ -112,8 +112,31 @@ class FrameDataset(ChainGeometry):
         with Image.open(path) as img:
             return np.asarray(img.convert("RGB"))
 
+    def compressed(self, item):
+        """`PngStreams` of a chosen item all of whose frames are single-image 8-bit RGB non-interlaced PNG files of one size, else None
+        (.npy, .jpg, palette / grey / alpha / 16-bit / interlaced or animated PNG, mixed sizes, a file the chunk walk refuses)."""
+        from ccvs_amd.tools import apng
+        streams, size = [], None
+        for p in item["paths"]:
+            if not p.lower().endswith(".png") or not apng.png_gpu_decodable(p):
+                return None
+            try:
+                h, w, zs = apng.apng_streams(p)
+            except ValueError:
+                return None
+            if len(zs) != 1 or (size or (h, w)) != (h, w):
+                return None
+            size = (h, w)
+            streams.append(zs[0])
+        return PngStreams(streams, size[0], size[1], list(item["paths"]))
+
     def decode(self, item):
-        """(uint8 [T, H, W, 3], plan) of a chosen item (T = 1 for single frames)."""
+        """(uint8 [T, H, W, 3], plan) of a chosen item (T = 1 for single frames).  With `--png_decode gpu` an item of PNG frames the GPU
+        decodes comes as (`PngStreams`, plan): the files' zlib streams, which `FrameLoader.assemble` uploads and decodes."""
+        if getattr(self.opt, "png_decode", "host") == "gpu":
+            packed = self.compressed(item)
+            if packed is not None:
+                return packed, self.plan(packed.shape[1], packed.shape[2], item["offsets"])
         frames = [self.read_frame(p) for p in item["paths"]]
         if any(f.shape != frames[0].shape for f in frames):
             raise ValueError(f"{os.path.dirname(item['paths'][0])}: frames of one clip differ in size")
@@ -122,6 +145,13 @@ class FrameDataset(ChainGeometry):
 
     def load(self, index):
         return self.decode(self.choose(index))
+
+
+class PngStreams:
+    """The frames of an item still compressed: the zlib stream of every frame, `shape` as the decoded uint8 array would have it."""
+
+    def __init__(self, streams, h, w, paths):
+        self.streams, self.paths, self.shape = streams, paths, (len(streams), h, w, 3)
 
 
 def run_plan(frames_u8, plan, out, mean, std):
@@ -144,7 +174,11 @@ class FrameLoader:
     (`FrameDataset.choose`) are made by the iterating thread in item order; its frames are decoded ahead by at most
     min(num_workers, 16) threads (none: inline).  A batch is stacked into one pinned uint8 buffer, uploaded with one non-blocking
     copy and run through `ops.ingest_u8` on the caller's current stream: no side stream, no synchronisation.  Frames of a batch that
-    differ in source size or plan are launched group by group."""
+    differ in source size or plan are launched group by group.  With `--png_decode gpu` the items that come compressed
+    (`FrameDataset.decode`) form groups of their own: a group's zlib streams go into one pinned blob, up in one non-blocking copy and
+    through one `ops.png_decode_uploaded` on the same stream, whose uint8 frames take the place of the uploaded ones; the status words
+    of a batch are read back once, after its last launch (the one synchronisation this mode adds), and a failed frame raises
+    ValueError naming its file."""
 
     def __init__(self, dataset, global_batch, lo=0, hi=None, cycle=False, ahead=2):
         self.dataset, self.global_batch = dataset, int(global_batch)
@@ -204,19 +238,36 @@ class FrameLoader:
         b, t = len(items), decoded[0][0].shape[0]
         dev = torch.device("cuda", torch.cuda.current_device())
         clip = torch.empty(b, t, 3, *ds.out_size, dtype=torch.float32, device=dev)
-        groups = {}
+        groups, checks = {}, []
         for i, (frames, plan) in enumerate(decoded):
-            groups.setdefault((frames.shape, tuple(plan)), []).append(i)
-        for (shape, plan), idxs in groups.items():
-            pinned = torch.empty(len(idxs), *shape, dtype=torch.uint8, pin_memory=True)
-            for k, i in enumerate(idxs):
-                pinned[k].copy_(torch.from_numpy(decoded[i][0]))
-            u8 = pinned.to(dev, non_blocking=True).view(len(idxs) * t, *shape[1:])
+            groups.setdefault((tuple(frames.shape), tuple(plan), isinstance(frames, PngStreams)), []).append(i)
+        for (shape, plan, packed), idxs in groups.items():
+            if packed:
+                from ccvs_amd import ops
+                meta, blob = ops.png_decode_pack([z for i in idxs for z in decoded[i][0].streams], shape[1], shape[2])
+                pinned = torch.empty(blob.size, dtype=torch.uint8, pin_memory=True)
+                pinned.copy_(torch.from_numpy(blob))
+                meta["blob"] = pinned.to(dev, non_blocking=True)
+                u8, status = ops.png_decode_uploaded(meta)
+                checks.append((status, [p for i in idxs for p in decoded[i][0].paths]))
+            else:
+                pinned = torch.empty(len(idxs), *shape, dtype=torch.uint8, pin_memory=True)
+                for k, i in enumerate(idxs):
+                    pinned[k].copy_(torch.from_numpy(decoded[i][0]))
+                u8 = pinned.to(dev, non_blocking=True).view(len(idxs) * t, *shape[1:])
             if len(groups) == 1:
                 run_plan(u8, plan, clip.view(b * t, 3, *ds.out_size), *ds.norm)
             else:
                 part = run_plan(u8, plan, torch.empty(len(idxs) * t, 3, *ds.out_size, dtype=torch.float32, device=dev), *ds.norm)
                 clip[torch.tensor(idxs, device=dev)] = part.view(len(idxs), t, 3, *ds.out_size)
+        if checks:
+            from ccvs_amd import ops
+            st = torch.cat([c[0] for c in checks]).cpu().numpy()
+            if st.any():
+                k = int(st.nonzero()[0][0])
+                word, why = ops.PD_STATUS.get(int(st[k]), ("?", "unknown"))
+                raise ValueError(f"{[p for c in checks for p in c[1]][k]}: the PNG decoder failed with status {int(st[k])} ({word}: {why}); "
+                                 f"{int((st != 0).sum())} of {st.size} frames of the batch failed")
         out = {"vid": clip} if ds.load_vid else {"img": clip[:, 0]}
         if "tgt_vid_lbl" in items[0]:
             out["tgt_vid_lbl"] = torch.stack([it["tgt_vid_lbl"] for it in items])

@@ -1688,3 +1688,145 @@ def read_avi_clips(paths):
     except ValueError as exc:
         raise ValueError(f"read_avi_clips: {exc} (frames count through the files in order, {t} per file; the first is {paths[0]})") from None
     return frames.view(len(paths), t, h, w, 3)
+
+
+# ------------------------------------------------------------------ the way back from the lossless stage (include/ccvs_hip_decode_lossless.h)
+PD_OK, PD_BAD_STREAM, PD_BAD_HEADER, PD_BAD_BLOCK, PD_BAD_TABLE, PD_BAD_CODE, PD_BAD_DISTANCE, PD_OVERRUN, PD_TOO_LONG, PD_TOO_SHORT, PD_BAD_CHECK, PD_BAD_FILTER = range(12)
+PD_STATUS = {
+    PD_OK: ("OK", "decoded"), PD_BAD_STREAM: ("BAD_STREAM", "the table row points outside the call's buffers"),
+    PD_BAD_HEADER: ("BAD_HEADER", "no zlib header of method 8 and a window of up to 32768, or it asks for a dictionary"),
+    PD_BAD_BLOCK: ("BAD_BLOCK", "block type 3, or a stored block whose LEN is not ~NLEN"),
+    PD_BAD_TABLE: ("BAD_TABLE", "a dynamic block's code lengths are no set zlib accepts"), PD_BAD_CODE: ("BAD_CODE", "no code starts so, or a symbol above the last"),
+    PD_BAD_DISTANCE: ("BAD_DISTANCE", "a match reaches before the first byte"), PD_OVERRUN: ("OVERRUN", "the input ended"),
+    PD_TOO_LONG: ("TOO_LONG", "more output than expected"), PD_TOO_SHORT: ("TOO_SHORT", "the final block ended before the expected output was there"),
+    PD_BAD_CHECK: ("BAD_CHECK", "the Adler-32 is not that of the output"), PD_BAD_FILTER: ("BAD_FILTER", "a row's filter type is above 4"),
+}
+
+
+def _pd_pack(streams, row):
+    """The table (int64 [n][len(row(0, 0, 0))]) and the streams as ONE host blob (uint8 numpy): the table first, the streams one behind
+    the other.  Returns (the table on the host, the blob, the streams' offset in it, their bytes)."""
+    import numpy as np
+    streams = [bytes(s) for s in streams]
+    rows, pos = [], 0
+    for i, s in enumerate(streams):
+        rows.append(row(i, pos, len(s)))
+        pos += len(s)
+    table = np.ascontiguousarray(rows, dtype=np.int64)
+    blob = np.zeros(table.nbytes + max(pos, 1), dtype=np.uint8)        # (the table's bytes are a multiple of 8)
+    blob[:table.nbytes] = table.view(np.uint8).reshape(-1)
+    blob[table.nbytes:table.nbytes + pos] = np.frombuffer(b"".join(streams), np.uint8)
+    return table, blob, table.nbytes, pos
+
+
+def _pd_raise(who, st, what, total=None):
+    k = int(st.nonzero()[0][0])
+    word, why = PD_STATUS.get(int(st[k]), ("?", "unknown"))
+    raise ValueError(f"{who}: {what} {k} failed with status {int(st[k])} ({word}: {why}); {int((st != 0).sum())} of {st.size if total is None else total} failed")
+
+
+def zlib_inflate(streams, sizes, check=True, out=None, offsets=None):
+    """n zlib streams (bytes each) inflated on the GPU (`ccvs_zlib_inflate`): a complete RFC 1950 / 1951 inflate
+    under zlib's acceptance rules.  sizes[i]: the bytes stream i is to hold.  Returns a uint8 tensor on the device with stream i's
+    bytes at offsets[i] (default: one behind the other); out: optional uint8 tensor to write into -- only the streams' own ranges are
+    written.  The table and the streams go up in ONE copy.  check=True reads the status words back -- the call's one synchronisation --
+    and raises ValueError naming the first failed stream and its status word; check=False returns (out, status int32 [n]) on the
+    device.  Runs on the current stream."""
+    sizes = [int(v) for v in sizes]
+    streams = list(streams)
+    if not streams or len(sizes) != len(streams) or min(sizes) < 0:
+        raise ValueError(f"zlib_inflate: {len(streams)} streams, {len(sizes)} sizes (none may be negative)")
+    if offsets is None:
+        offsets, pos = [], 0
+        for v in sizes:
+            offsets.append(pos)
+            pos += v
+    table, blob, o_data, data_bytes = _pd_pack(streams, lambda i, pos, n: (pos, n, int(offsets[i]), sizes[i]))
+    if not torch.cuda.is_available():
+        raise _lib.CcvsError("zlib_inflate needs a GPU: there is no CPU fallback")
+    up = torch.from_numpy(blob).to("cuda")
+    if out is None:
+        out = torch.empty(max(max(o + v for o, v in zip(offsets, sizes)), 1), dtype=torch.uint8, device=up.device)
+    _need_gpu(out)
+    assert out.dtype == torch.uint8 and out.is_contiguous(), (out.dtype, out.stride())
+    status = torch.empty(len(streams), dtype=torch.int32, device=up.device)
+    base = up.data_ptr()
+    _lib.check(_lib.load().ccvs_zlib_inflate(C.c_void_p(base + o_data), data_bytes, C.c_void_p(base), table.ctypes.data_as(C.c_void_p), len(streams),
+                                             _p(out), out.numel(), _p(status), _stream()), "ccvs_zlib_inflate")
+    if not check:
+        return out, status
+    st = status.cpu().numpy()
+    if st.any():
+        _pd_raise("zlib_inflate", st, "stream")
+    return out
+
+
+def png_decode_pack(streams, h, w):
+    """The zlib streams of n 8-bit RGB PNG images of h x w as ONE host blob (uint8 numpy): the table of (offset, bytes) rows, then
+    the streams.  Returns (meta, blob): `meta` with the blob on the device under "blob" (a uint8 tensor whose first byte is 8-byte
+    aligned) is what `png_decode_uploaded` takes -- callers that batch (`ccvs_amd.data.FrameLoader`) upload the blob themselves."""
+    streams = list(streams)
+    if not streams or not (1 <= int(h) <= 65535 and 1 <= int(w) <= 65535):
+        raise ValueError(f"png_decode: {len(streams)} streams of {h} x {w} (sizes are 1 .. 65535)")
+    table, blob, o_data, data_bytes = _pd_pack(streams, lambda i, pos, n: (pos, n))
+    return {"n": len(streams), "h": int(h), "w": int(w), "rows_host": table, "o_data": o_data, "data_bytes": data_bytes}, blob
+
+
+def png_decode_uploaded(up, out=None, status=None, work=None):
+    """`ccvs_png_decode` on an uploaded pack: (frames uint8 [n, H, W, 3], status int32 [n]), both on the device; status[i] == 0: frame i
+    inflated to exactly its h (3 w + 1) filtered bytes with the right Adler-32 and every row's filter type was 0 .. 4.  out: optional
+    uint8 [n, H, W, 3] to write into, frames dense, any frame stride of at least a frame; only its own bytes are written.  status /
+    work: optional buffers to reuse.  Runs on the current stream; nothing is synchronised."""
+    n, h, w = up["n"], up["h"], up["w"]
+    dev = up["blob"].device
+    if out is not None:
+        _need_gpu(out)
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (n, h, w, 3) and out.stride()[1:] == (3 * w, 3, 1) and (n == 1 or out.stride(0) >= 3 * h * w), \
+            (out.dtype, out.shape, out.stride())
+    else:
+        out = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev)
+    L = _lib.load()
+    if status is None:
+        status = torch.empty(n, dtype=torch.int32, device=dev)
+    if work is None:
+        work = torch.empty(max(int(L.ccvs_png_decode_workspace_bytes(n, h, w)), 16), dtype=torch.uint8, device=dev)
+    base = up["blob"].data_ptr()
+    _lib.check(L.ccvs_png_decode(C.c_void_p(base + up["o_data"]), up["data_bytes"], C.c_void_p(base), up["rows_host"].ctypes.data_as(C.c_void_p), n, h, w,
+                                 _p(out), out.stride(0) if n > 1 else 3 * h * w, _p(status), _p(work), _stream()), "ccvs_png_decode")
+    return out, status
+
+
+def png_decode(streams, h, w, out=None, check=True):
+    """uint8 [n, H, W, 3] on the device of the zlib streams (bytes each: a PNG's concatenated IDAT payload, `tools.apng.apng_streams`) of n
+    8-bit RGB images of h x w -- inflated and un-filtered on the GPU, the bytes `tools.apng.read_apng` gives.
+    One upload.  check=True reads the status words back -- the call's one synchronisation -- and raises ValueError naming the frame,
+    the status word and how many failed; check=False returns (frames, status) on the device (see `png_decode_uploaded`)."""
+    meta, blob = png_decode_pack(streams, h, w)
+    if not torch.cuda.is_available():
+        raise _lib.CcvsError("png_decode needs a GPU: there is no CPU fallback")
+    meta["blob"] = torch.from_numpy(blob).to("cuda")
+    frames, status = png_decode_uploaded(meta, out)
+    if not check:
+        return frames, status
+    st = status.cpu().numpy()
+    if st.any():
+        _pd_raise("png_decode", st, "frame")
+    return frames
+
+
+def read_apng_clips(paths):
+    """uint8 [N, T, H, W, 3] on the device of N PNG / APNG files of equal size and length (`tools.apng.apng_streams`), all frames of all
+    files in one decode call: only the compressed bytes cross to the device."""
+    from .tools import apng as _apng
+    clips = [_apng.apng_streams(p) for p in paths]
+    if not clips:
+        raise ValueError("read_apng_clips: no files")
+    h, w, t = clips[0][0], clips[0][1], len(clips[0][2])
+    for p, c in zip(paths, clips):
+        if (c[0], c[1], len(c[2])) != (h, w, t) or t == 0:
+            raise ValueError(f"read_apng_clips: {p} holds {len(c[2])} frames of {c[0]} x {c[1]}, {paths[0]} {t} of {h} x {w}")
+    try:
+        frames = png_decode([z for c in clips for z in c[2]], h, w)
+    except ValueError as exc:
+        raise ValueError(f"read_apng_clips: {exc} (frames count through the files in order, {t} per file; the first is {paths[0]})") from None
+    return frames.view(len(paths), t, h, w, 3)

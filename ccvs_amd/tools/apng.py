@@ -7,7 +7,9 @@
                                           player that knows nothing of APNG shows frame 0.
   read_apng(path) -> uint8 [T, H, W, 3]   walks the chunks, checks their CRCs, inflates with zlib and undoes the filters in numpy.  It
                                           reads anybody's RGB8 non-interlaced PNG or full-frame APNG and says why it refuses another.
-Nothing here touches the GPU: PNG decoding on the device is not part of the project.
+  apng_streams(data_or_path) -> (h, w, [zlib stream per frame])   the same walk without the inflate: what `ops.png_decode` takes
+                                          (DESIGN.md section 4.23); png_gpu_decodable(path) is the header probe in front of it.
+Nothing here touches the GPU.
 """
 import struct
 import zlib
@@ -104,11 +106,15 @@ def unfilter(raws, h, w):
     return out[:, 1:, 1:].astype(np.uint8)
 
 
-def read_apng(path):
-    """uint8 [T, H, W, 3] of an 8-bit RGB, non-interlaced PNG (T = 1) or APNG whose frames are all full frames with blend = source and
-    dispose = none.  ValueError names what else the file holds."""
-    with open(path, "rb") as f:
-        data = f.read()
+def apng_streams(data_or_path):
+    """(h, w, [the zlib stream of every frame, bytes]) of an 8-bit RGB, non-interlaced PNG (one frame) or APNG whose frames are all full
+    frames with blend = source and dispose = none: the chunk walk, CRC check and refusals of `read_apng`, without the inflate.  Takes
+    the file's bytes or its path."""
+    if isinstance(data_or_path, (bytes, bytearray, memoryview)):
+        data = bytes(data_or_path)
+    else:
+        with open(data_or_path, "rb") as f:
+            data = f.read()
     cs = chunks(data)
     if not cs or cs[0][0] != b"IHDR" or len(cs[0][1]) != 13:
         raise ValueError("read_apng: the first chunk is not an IHDR")
@@ -158,10 +164,31 @@ def read_apng(path):
         count = struct.unpack(">II", next(p for t, p in cs if t == b"acTL"))[0]
         if count != len(frames) or any(not f for f in frames):
             raise ValueError(f"read_apng: acTL says {count} frames, the file holds {sum(bool(f) for f in frames)}")
+    return h, w, [b"".join(parts) for parts in frames]
+
+
+def read_apng(path):
+    """uint8 [T, H, W, 3] of an 8-bit RGB, non-interlaced PNG (T = 1) or APNG whose frames are all full frames with blend = source and
+    dispose = none.  ValueError names what else the file holds."""
+    h, w, streams = apng_streams(path)
     raws = []
-    for i, parts in enumerate(frames):
+    for i, z in enumerate(streams):
         try:
-            raws.append(zlib.decompress(b"".join(parts)))
+            raws.append(zlib.decompress(z))
         except zlib.error as exc:
             raise ValueError(f"read_apng: frame {i} does not inflate: {exc}") from None
     return unfilter(raws, h, w)
+
+
+def png_gpu_decodable(path):
+    """True where the file's first 29 bytes are a PNG signature and an IHDR of colour type 2 (RGB), bit depth 8, no interlace and the
+    standard compression and filter methods: what `ccvs_amd.ops.png_decode` takes.  A cheap probe: nothing else of the file is read."""
+    try:
+        with open(path, "rb") as f:
+            head = f.read(29)
+    except OSError:
+        return False
+    if len(head) < 29 or head[:8] != SIGNATURE or head[8:16] != b"\x00\x00\x00\rIHDR":
+        return False
+    w, h, depth, colour, comp, flt, interlace = struct.unpack(">IIBBBBB", head[16:29])
+    return (depth, colour, comp, flt, interlace) == (8, 2, 0, 0, 0) and 1 <= w <= 65535 and 1 <= h <= 65535

@@ -112,6 +112,10 @@ class Options:
         p.add_argument("--video_quality", type=_jpeg_quality, default=90)
         p.add_argument("--video_subsampling", type=str, default="444", choices=["444", "422", "420"])
         _flag(p, "--video_optimize")
+        # (ccvs_amd) where the PNG frames of a frame-folder dataset are decoded: host -- Pillow in the loader's threads, the uint8 frames
+        # uploaded; gpu -- the files' zlib streams uploaded, inflated and un-filtered on the GPU (csrc/png_decode.hip; the same frames).
+        # An item that is not all 8-bit RGB non-interlaced PNGs of one size is decoded on the host either way.
+        p.add_argument("--png_decode", type=str, default="host", choices=["host", "gpu"])
         # ---- q_: quantised video model (tools/options.py:159-264)
         p.add_argument("--q_enc_model", type=str, default="taming")
         p.add_argument("--q_dec_model", type=str, default="stylegan2")

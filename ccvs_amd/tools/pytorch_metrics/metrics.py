@@ -13,8 +13,8 @@ Same function names and argument meaning as the reference:
                       reference's decoder is OpenCV, absent here).
   load_video(s)       metrics.py:80-97: .avi through `read_avi` and `ops.mjpeg_decode` (the JPEG decoder in HIP, DESIGN.md section
                       4.16: libjpeg's pixels), .npy the uint8 [T, H, W, 3] arrays `run()` writes, .png the lossless animated PNGs of
-                      `--video_format apng` (`tools.apng.read_apng`: inflated and un-filtered on the host, DESIGN.md section 4.22 --
-                      the exact clips, so the scores are those of the clips the model produced); the clips stay on the device.
+                      `--video_format apng` (`tools.apng.read_apng`: inflated and un-filtered on the host, or with png_decode="gpu" on
+                      the device by `ops.read_apng_clips`, DESIGN.md sections 4.22 and 4.23 -- the exact clips, so the scores are those of the clips the model produced); the clips stay on the device.
                       `resize` other than None raises NotImplementedError (the reference's is OpenCV INTER_AREA, not reproduced).
   get_video_files, get_folder(s), print_scores, main, and the argparse block      metrics.py:92-186:
                       python -m ccvs_amd.tools.pytorch_metrics.metrics --exp_tag TAG [--real_tag --real_folder --fake_folder
@@ -163,15 +163,15 @@ def metrics_from_videos(real_videos_u8, generated_videos_u8, print_256=False, id
     return _aggregate(ssim, psnr, print_256, idx, batch_size, lpips)
 
 
-def metrics_from_files(real_video_files, generated_video_files, resize, num_workers, print_256, idx, loader=None):
-    """metrics.py:27-78.  loader: `loader(files, resize) -> uint8 [B, T, H, W, 3]` (numpy or torch) in place of `load_videos`; it is
+def metrics_from_files(real_video_files, generated_video_files, resize, num_workers, print_256, idx, loader=None, png_decode="host"):
+    """metrics.py:27-78.  png_decode: where `load_videos` decodes .png clips ("host" or "gpu").  loader: `loader(files, resize) -> uint8 [B, T, H, W, 3]` (numpy or torch) in place of `load_videos`; it is
     needed for .mp4 names only -- the reference decodes those with OpenCV (metrics.py:80-97), which this image does not have, so
     without a loader they raise."""
     if loader is None:
         if any(os.path.splitext(str(f))[1].lower() not in (".avi", ".npy", ".png") for f in list(real_video_files) + list(generated_video_files)):
             raise RuntimeError("metrics_from_files: no mp4 decoder here (the reference uses OpenCV); pass loader=..., or call "
                                "metrics_from_videos on the uint8 clips")
-        loader = lambda files, size: load_videos(files, size, num_workers)  # noqa: E731
+        loader = lambda files, size: load_videos(files, size, num_workers, png_decode=png_decode)  # noqa: E731
     batch_size = 16
     total = len(real_video_files)
     ssim, psnr = ([], []) if len(idx) == 0 else ([[] for _ in idx], [[] for _ in idx])
@@ -200,9 +200,13 @@ def get_video_files(folder):
     return []
 
 
-def load_videos(video_files, resize, num_workers):
+def load_videos(video_files, resize, num_workers, png_decode="host"):
     """metrics.py:95-97: uint8 [B, T, H, W, 3] on the device.  The .avi files of a batch are decoded by one call; `num_workers` is
-    accepted and unused (the files are read by this process, the frames decoded by the GPU)."""
+    accepted and unused (the files are read by this process, the frames decoded by the GPU).  png_decode: "host" inflates and
+    un-filters the .png clips of a batch with zlib and numpy and uploads the frames; "gpu" uploads their zlib streams and decodes all
+    frames of the batch in one call (`ops.read_apng_clips`) -- the same bytes either way."""
+    if png_decode not in ("host", "gpu"):
+        raise ValueError(f"load_videos: png_decode is 'host' or 'gpu', not {png_decode!r}")
     if resize is not None:
         raise NotImplementedError("load_videos: resize is OpenCV's INTER_AREA in the reference, which is not reproduced here; pass resize=None")
     kinds = {os.path.splitext(str(f))[1].lower() for f in video_files}
@@ -214,6 +218,8 @@ def load_videos(video_files, resize, num_workers):
             if c.dtype != np.uint8 or c.ndim != 4 or c.shape[-1] != 3 or c.shape != clips[0].shape:
                 raise ValueError(f"load_videos: {f} holds {c.dtype} {c.shape}, not a uint8 [T, H, W, 3] clip of the batch's shape")
         return torch.from_numpy(np.stack(clips)).cuda()
+    if kinds == {".png"} and png_decode == "gpu":
+        return ops.read_apng_clips([str(f) for f in video_files])
     if kinds == {".png"}:                                               # the lossless clips: inflated and un-filtered on the host, one upload
         from ccvs_amd.tools.apng import read_apng
         clips = [read_apng(str(f)) for f in video_files]
@@ -275,7 +281,8 @@ def main(args):
         assert len(real_video_files) == len(fake_video_files)
 
         print(f"[{i}] Computing metrics")
-        lpips_i, ssim_i, psnr_i = metrics_from_files(real_video_files, fake_video_files, args.resize, args.num_workers, args.print_256, args.idx)
+        lpips_i, ssim_i, psnr_i = metrics_from_files(real_video_files, fake_video_files, args.resize, args.num_workers, args.print_256, args.idx,
+                                                      png_decode=getattr(args, "png_decode", "host"))
         if len(args.idx) == 0:
             lpips.append(lpips_i)
             ssim.append(ssim_i)
@@ -309,6 +316,8 @@ def parse_args(argv=None):
     parser.add_argument('--print_256', action='store_true')
     parser.add_argument('--resize', type=int, nargs="+", default=None)
     parser.add_argument('--lpips_weights', type=str, default=None, help="the LPIPS weight file (tools/pytorch_metrics/lpips.py writes it)")
+    parser.add_argument('--png_decode', type=str, default="host", choices=("host", "gpu"),
+                        help="where .png clips are inflated and un-filtered: host (zlib and numpy) or gpu (one decode call per batch); the same bytes")
     return parser.parse_args(argv)
 
 

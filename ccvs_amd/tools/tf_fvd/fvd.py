@@ -111,10 +111,11 @@ def emb_from_videos(real_u8, fake_u8, channel_order="bgr"):
     return _embed_batches(len(real_u8), lambda sl: real_u8[sl], lambda sl: fake_u8[sl], channel_order)
 
 
-def emb_from_files(real_video_files, fake_video_files, resize, num_workers, channel_order="bgr", loader=None):
-    """fvd.py:145-173.  loader: `loader(files, resize) -> uint8 [B, T, H, W, 3]` in place of `load_videos` (needed for .mp4 names only)."""
+def emb_from_files(real_video_files, fake_video_files, resize, num_workers, channel_order="bgr", loader=None, png_decode="host"):
+    """fvd.py:145-173.  loader: `loader(files, resize) -> uint8 [B, T, H, W, 3]` in place of `load_videos` (needed for .mp4 names only);
+    png_decode: where `load_videos` decodes .png clips ("host" or "gpu")."""
     if loader is None:
-        loader = lambda files, size: load_videos(files, size, num_workers)  # noqa: E731
+        loader = lambda files, size: load_videos(files, size, num_workers, png_decode=png_decode)  # noqa: E731
     assert len(real_video_files) == len(fake_video_files)
     return _embed_batches(len(real_video_files), lambda sl: loader(real_video_files[sl], resize), lambda sl: loader(fake_video_files[sl], resize),
                           channel_order)
@@ -169,7 +170,8 @@ def main(args):
         assert len(real_video_files) == len(fake_video_files)
 
         print(f"[{i}] Computing embeddings")
-        real_emb_i, fake_emb_i = emb_from_files(real_video_files, fake_video_files, args.resize, args.num_workers, args.channel_order)
+        real_emb_i, fake_emb_i = emb_from_files(real_video_files, fake_video_files, args.resize, args.num_workers, args.channel_order,
+                                                png_decode=getattr(args, "png_decode", "host"))
         real_emb.append(real_emb_i)
         fake_emb.append(fake_emb_i)
 
@@ -196,6 +198,8 @@ def parse_args(argv=None):
     parser.add_argument('--fvd_weights', type=str, default=None, help="the I3D weight file (tools/tf_fvd/i3d.py writes it)")
     parser.add_argument('--channel_order', type=str, default="bgr", choices=("bgr", "rgb"),
                         help="bgr: the channels reversed, as the reference feeds them (OpenCV frames, unconverted); rgb: the canonical order")
+    parser.add_argument('--png_decode', type=str, default="host", choices=("host", "gpu"),
+                        help="where .png clips are inflated and un-filtered: host (zlib and numpy) or gpu (one decode call per batch); the same bytes")
     return parser.parse_args(argv)
 
 
