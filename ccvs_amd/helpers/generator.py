@@ -597,7 +597,8 @@ class Generator:
         bs = out["real"].shape[0]
         fmt = getattr(self.opt, "video_format", "auto")
         how = dict(video_format=None if fmt == "auto" else fmt, quality=getattr(self.opt, "video_quality", 90), return_clip=False,
-                   subsampling=getattr(self.opt, "video_subsampling", "444"), optimize=bool(getattr(self.opt, "video_optimize", False)))
+                   subsampling=getattr(self.opt, "video_subsampling", "444"), optimize=bool(getattr(self.opt, "video_optimize", False)),
+                   lz77=bool(getattr(self.opt, "video_lz77", False)))
         for name in ("real", "fake", "rec", "blur"):                       # generator.py:191-212
             item = out.get(name)
             if item is None:
@@ -712,7 +713,7 @@ _SUBSAMPLING = {"444": 0, "422": 1, "420": 2}     # --video_subsampling -> the e
 
 
 def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, span, dataset, state=None, cat=None, idx=None,
-                     is_layout=False, video_format=None, quality=90, return_clip=True, subsampling="444", optimize=False):
+                     is_layout=False, video_format=None, quality=90, return_clip=True, subsampling="444", optimize=False, lz77=False):
     """helpers/generator.py:285-333.  The clamp / rescale / uint8 / channels-last pack runs on the GPU.  video_format:
       None    mp4 when torchvision is importable, else .npy uint8 [T,H,W,3];
       "npy"   the arrays, whatever imports;
@@ -723,7 +724,9 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
               writes with optimize_coding) -- the same pixels in fewer bytes; the other formats do not look at it either.
       "apng"  lossless: one animated PNG `vid_XXXXX.png` per clip (`ccvs_amd.tools.apng`): the packed clip is PNG-filtered and
               deflate-coded on the device (`ops.png_encode`) and the compressed streams are what is copied out.
-              Browsers, ffmpeg and Pillow open the files; `quality`, `subsampling` and `optimize` are not looked at.
+              Browsers, ffmpeg and Pillow open the files; `quality`, `subsampling` and `optimize` are not looked at.  lz77: the deflate
+              blocks may hold LZ77 matches, kept per block only where that is smaller: the same pixels, no file
+              larger, a slower encode; the other formats do not look at it.
     Returns the uint8 clip on the host; `return_clip=False` lets the "avi" and "apng" forms skip that copy where no state marker needs
     it (then only the compressed bytes cross to the host, and None is returned)."""
     if is_layout:
@@ -767,7 +770,7 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
     elif video_format == "apng":
         from ccvs_amd.tools import apng
         t, (h, w) = u8.size(1), u8.shape[2:4]
-        zbytes, off = ops.png_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device))
+        zbytes, off = ops.png_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), lz77=lz77)
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'

@@ -42,6 +42,8 @@ LPIPS_EXPORTS = ["ccvs_lpips_prep", "ccvs_relu_", "ccvs_relu_maxpool2", "ccvs_lp
 FVD_EXPORTS = ["ccvs_fvd_prep", "ccvs_time_unfold", "ccvs_maxpool3d_same", "ccvs_i3d_head"]
 # every symbol include/ccvs_hip_output_lossless.h declares (the lossless output stage: PNG filters and deflate, a zlib stream per frame; included by ccvs_hip.h too)
 OUTPUT_LOSSLESS_EXPORTS = ["ccvs_apng_workspace_bytes", "ccvs_apng_stream_bound", "ccvs_apng_encode"]
+# every symbol include/ccvs_hip_output_lossless_lz.h declares (the same stage with LZ77 matches, kept per deflate block only where smaller; included by ccvs_hip.h too)
+OUTPUT_LOSSLESS_LZ_EXPORTS = ["ccvs_apng_lz_workspace_bytes", "ccvs_apng_encode_lz"]
 # every symbol include/ccvs_hip_decode_lossless.h declares (the way back from it: zlib streams -> bytes, PNG streams -> uint8 frames; included by ccvs_hip.h too)
 DECODE_LOSSLESS_EXPORTS = ["ccvs_png_decode_workspace_bytes", "ccvs_zlib_inflate", "ccvs_png_decode"]
 
@@ -135,6 +137,8 @@ def load():
     lib.ccvs_apng_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_apng_stream_bound.restype = C.c_long
     lib.ccvs_apng_stream_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ccvs_apng_lz_workspace_bytes.restype = C.c_size_t
+    lib.ccvs_apng_lz_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_png_decode_workspace_bytes.restype = C.c_size_t
     lib.ccvs_png_decode_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ccvs_lpips_layer_workspace_bytes.restype = C.c_int64
@@ -201,6 +205,7 @@ def load():
         "ccvs_mjpeg_encode_optimized": [vp, C.c_long, i32, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp, vp],
         "ccvs_mjpeg_decode": [vp, C.c_long, vp, vp, C.c_long, vp, i32, vp, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_apng_encode": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
+        "ccvs_apng_encode_lz": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_zlib_inflate": [vp, C.c_long, vp, vp, i32, vp, C.c_long, vp, vp],
         "ccvs_png_decode": [vp, C.c_long, vp, vp, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_lpips_prep": [vp, vp, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), vp],

@@ -1532,7 +1532,7 @@ def mjpeg_encode_to_host(u8, quality=90, restart_mcus=None, sampling=0, optimize
 
 
 # ------------------------------------------------------------------ lossless output stage (include/ccvs_hip_output_lossless.h)
-def png_encode(u8, filter=-1, band_rows=0, capacity=None, out=None):
+def png_encode(u8, filter=-1, band_rows=0, capacity=None, out=None, lz77=False):
     """One zlib stream per frame of uint8 frames [..., H, W, 3] on the device (`ccvs_apng_encode`): PNG's row
     filters, then Huffman-only deflate with dynamic tables -- the payload of a PNG IDAT / APNG fdAT chunk (`ccvs_amd.tools.apng`
     writes the container).  Returns (stream uint8 [capacity], offsets int64 [n + 1]), both on the device -- frame i's stream is
@@ -1541,7 +1541,10 @@ def png_encode(u8, filter=-1, band_rows=0, capacity=None, out=None):
     Frames and strides are handled as in `mjpeg_encode`.  capacity: bytes of `stream` (None: 9/8 of the filtered size plus 470 bytes
     per band, which noise does not fill); the offsets are complete also when offsets[n] > capacity, nothing at or beyond `capacity` is
     written, and the CALLER runs again with a larger one (`png_encode_to_host` does; `ccvs_apng_stream_bound` always suffices).
-    out: optional uint8 stream to write into (its length is the capacity).  Runs on the current stream; nothing is synchronised."""
+    out: optional uint8 stream to write into (its length is the capacity).  Runs on the current stream; nothing is synchronised.
+    lz77: the deflate blocks may hold LZ77 matches (`ccvs_apng_encode_lz`); per block the form with fewer bits
+    is written, so no frame's stream is longer than without and the default capacity suffices as before.  Flat and structured frames
+    shrink several times; the encode takes longer."""
     _need_gpu(u8, out)
     assert u8.dtype == torch.uint8 and u8.dim() >= 3 and u8.shape[-1] == 3, (u8.dtype, u8.shape)
     h, w = int(u8.shape[-3]), int(u8.shape[-2])
@@ -1565,20 +1568,22 @@ def png_encode(u8, filter=-1, band_rows=0, capacity=None, out=None):
         capacity = n * (6 + h * (3 * w + 1) * 9 // 8 + 470 * ((h + rows - 1) // rows))
     stream = out if out is not None else torch.empty(int(capacity), dtype=torch.uint8, device=u8.device)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=u8.device)
-    work = torch.empty(max(int(L.ccvs_apng_workspace_bytes(n, h, w, max(band_rows, 0))), 8), dtype=torch.uint8, device=u8.device)
-    _lib.check(L.ccvs_apng_encode(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, filter, band_rows, _p(stream), int(capacity),
-                                  _p(offsets), _p(work), _stream()), "ccvs_apng_encode")
+    size, encode, who = ((L.ccvs_apng_lz_workspace_bytes, L.ccvs_apng_encode_lz, "ccvs_apng_encode_lz") if lz77 else
+                         (L.ccvs_apng_workspace_bytes, L.ccvs_apng_encode, "ccvs_apng_encode"))
+    work = torch.empty(max(int(size(n, h, w, max(band_rows, 0))), 8), dtype=torch.uint8, device=u8.device)
+    _lib.check(encode(_p(frames), frames.stride(0) if n > 1 else h * w * 3, n, h, w, filter, band_rows, _p(stream), int(capacity),
+                      _p(offsets), _p(work), _stream()), who)
     return stream, offsets
 
 
-def png_encode_to_host(u8, filter=-1, band_rows=0):
+def png_encode_to_host(u8, filter=-1, band_rows=0, lz77=False):
     """`png_encode`, then the streams on the host: (bytes of all frames' zlib streams, list of n + 1 offsets).  Where the first run's
     stream is too small the offsets say by how much and a second run with that capacity is exact.  What crosses to the host is the
     offsets and offsets[n] compressed bytes."""
-    stream, offsets = png_encode(u8, filter, band_rows)
+    stream, offsets = png_encode(u8, filter, band_rows, lz77=lz77)
     off = offsets.cpu().tolist()
     if off[-1] > stream.numel():
-        stream, offsets = png_encode(u8, filter, band_rows, capacity=off[-1])
+        stream, offsets = png_encode(u8, filter, band_rows, capacity=off[-1], lz77=lz77)
     return stream[:off[-1]].cpu().numpy().tobytes(), off
 
 

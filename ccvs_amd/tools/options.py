@@ -108,10 +108,14 @@ class Options:
         # players and other tools expect, smaller files); ignored unless the files are avi
         # --video_optimize: every avi frame carries Huffman tables built for it (libjpeg's optimize_coding; the same pixels, smaller
         # files, a slower encode); ignored unless the files are avi
+        # --video_lz77: the apng files' deflate blocks may hold LZ77 matches, kept per block only where that is smaller (csrc/png_lz.hip:
+        # the same pixels, never a larger file, far smaller ones for flat or structured frames, a slower encode); ignored unless the
+        # files are apng
         p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi", "apng"])
         p.add_argument("--video_quality", type=_jpeg_quality, default=90)
         p.add_argument("--video_subsampling", type=str, default="444", choices=["444", "422", "420"])
         _flag(p, "--video_optimize")
+        _flag(p, "--video_lz77")
         # (ccvs_amd) where the PNG frames of a frame-folder dataset are decoded: host -- Pillow in the loader's threads, the uint8 frames
         # uploaded; gpu -- the files' zlib streams uploaded, inflated and un-filtered on the GPU (csrc/png_decode.hip; the same frames).
         # An item that is not all 8-bit RGB non-interlaced PNGs of one size is decoded on the host either way.

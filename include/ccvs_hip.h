@@ -499,6 +499,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_fvd.h"
 /* the lossless output stage (uint8 clips -> PNG filters and Huffman-only deflate: one zlib stream per frame for an APNG), additive to ABI version 6, likewise */
 #include "ccvs_hip_output_lossless.h"
+/* the same stage with LZ77 matches in its deflate blocks, kept per block only where that is smaller, additive to ABI version 6, likewise */
+#include "ccvs_hip_output_lossless_lz.h"
 /* the way back from it (zlib streams -> bytes; the streams of 8-bit RGB PNG images -> uint8 frames), additive to ABI version 6, likewise */
 #include "ccvs_hip_decode_lossless.h"
 
