@@ -39,9 +39,11 @@ extern "C" int ccvs_gpt_embed(const int64_t* idx, int64_t idx_sB, const int32_t*
 }
 
 // ---------------------------------------------------------------------------------------
-// LayerNorm (eps 1e-5), one wave per row.  The row is shifted by its first element before anything is summed: the terms of
-// the mean then have the size of the row's spread, not of its mean (a row of mean 1e3 and std 1 keeps fp32 accuracy relative
-// to its std; a constant row gives exactly beta).
+// LayerNorm (eps 1e-5), one wave per row.  The row is shifted before anything is summed, by the mean of its first four elements
+// (its first element where it has fewer): the terms of the mean then have the size of the row's spread, not of its mean (a row of
+// mean 1e3 and std 1 keeps fp32 accuracy relative to its std; a constant row gives exactly beta).  Four elements, as the folded
+// LayerNorm of the GEMMs below (ln_shift): shifted by its first element alone, a row whose first element is its outlier (1 in
+// front of N(0, 1e-3)) sums terms of the outlier's size and missed the test's tolerance 1.1 to 2.1 times.
 // ---------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ g,
                                                         const float* __restrict__ b, float* __restrict__ y, int rows, int C) {
@@ -49,7 +51,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     const float* xr = x + (long)row * C;
-    const float x0 = xr[0];
+    const float x0 = C >= 4 ? ((xr[0] + xr[1]) + (xr[2] + xr[3])) * 0.25f : xr[0];
     float s = 0.f;
     for (int c = lane; c < C; c += 64) s += xr[c] - x0;
     const float mean = wave_sum(s) / C;   // of x - x0
@@ -81,9 +83,18 @@ extern "C" int ccvs_layernorm(const float* x, const float* gamma, const float* b
 //   * LayerNorm is folded in algebraically: with W' = W*gamma, s[n] = sum_k W'[n][k] and
 //     b' = b + W beta (packed once by the host),
 //         LN(x) @ W^T + b = rstd * (x @ W'^T - mean * s) + b'
-//     so the GEMM runs on the raw activations and the row statistics (sum x, sum x^2, which the
-//     lanes accumulate from the very x values they feed to the MFMA) are applied in the
-//     epilogue: the separate LayerNorm launch and its round trip through HBM disappear;
+//     so the GEMM needs no normalised activations and the row statistics are applied in the
+//     epilogue: the separate LayerNorm launch and its round trip through HBM disappear.
+//     LayerNorm does not change when a constant is added to a row, and the fold is run on
+//     d = x - c, c = the mean of the row's first four elements (ln_shift): what the lanes feed
+//     to the MFMA and what they sum (sum d, sum d^2, from the very values they feed) is d.  On
+//     the raw x both `sum x^2 / K - mean^2` and `x @ W'^T - mean * s` subtract two numbers of
+//     the size of mean^2 resp. |mean| |s| to get one of the size of the variance resp. of the
+//     output: the error is eps (mean / std)^2 resp. eps |mean| / std in units of the result
+//     (a residual row of mean 1e3 and std 1: 3e-3 of the output's scale).  With c within a few
+//     std of the mean both differences are between numbers of the result's own size.  Four
+//     elements and not the first alone: a row whose first element is its outlier (|x0 - mean|
+//     up to sqrt(K) std) would otherwise get the cancellation back from the shift itself;
 //   * the QKV projection can scatter its K and V column blocks straight into the KV cache at a
 //     host- or device-resident position (no separate append launch).
 // Larger M (prefill) runs the same kernel over ceil(M/16) row blocks, W then coming from L2.
@@ -103,6 +114,20 @@ __device__ __forceinline__ void ln_accum(const f32x4& v, float& sx, float& sxx) 
     sx += (v[0] + v[1]) + (v[2] + v[3]);
     sxx += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
 }
+
+// the shift of the folded LayerNorm (see above): c = the mean of the row's first four elements, a function of the row alone, and
+// d = x - c, which every form feeds to its MFMAs and to ln_accum instead of x.  One definition, contraction off, as ln_accum.
+__device__ __forceinline__ float ln_shift(const float4& h) {
+#pragma clang fp contract(off)
+    return ((h.x + h.y) + (h.z + h.w)) * 0.25f;
+}
+__device__ __forceinline__ float ln_shift(const f32x4& h) {
+#pragma clang fp contract(off)
+    return ((h[0] + h[1]) + (h[2] + h[3])) * 0.25f;
+}
+template <bool B> struct ln_on { static constexpr bool value = B; };   // a K loop's kind: with / without the folded LayerNorm
+__device__ __forceinline__ void ln_center(float4& v, float c) { v.x -= c; v.y -= c; v.z -= c; v.w -= c; }
+__device__ __forceinline__ void ln_center(f32x4& v, float c) { v[0] -= c; v[1] -= c; v[2] -= c; v[3] -= c; }
 
 // 16 bytes at descriptor `r`, per-lane byte offset `voff` + wave-uniform byte offset `soff` (buffer_load_dwordx4 ... offen)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
@@ -139,6 +164,19 @@ __device__ __forceinline__ int thread_id() {
     int t = threadIdx.x;
     if constexpr (OPAQUE) asm volatile("" : "+v"(t));
     return t;
+}
+// a wave-uniform operand of the phase table, opaque to the optimiser when OPAQUE: what the tile body derives from it for its epilogue alone
+// -- the reciprocal of a divisor, (float)K -- is loop-invariant, and hoisted in front of the phase's tile loop it holds a VECTOR register
+// (integer division and conversions run on the vector ALU) across the K loop, under the persistent step's 64-register cap.
+// These are answers to one compiler's register allocation, not to the hardware: with hipcc of ROCm 7.2.0 (AMD clang 22.0.0git,
+// roc-7.2.0 26014) and the LayerNorm shifts in the K loop, gpt_step_kernel spilled 12 to 28 bytes per lane without them -- (float)K, the
+// reciprocals of D / Tq / grp_rows, the K loops' entry tests, the barrier's poll address and target, and the lane maps of the row-major
+// body, all held in vector registers across the loop -- and none with them.  Under another compiler, build with
+// -Rpass-analysis=kernel-resource-usage and drop whichever of them no longer buys a scratch-free gpt_step_kernel.
+template <bool OPAQUE>
+__device__ __forceinline__ int opaque_if(int v) {
+    if constexpr (OPAQUE) asm volatile("" : "+s"(v));
+    return v;
 }
 // a pointer read from the persistent step's phase table (constant memory) is a GENERIC pointer to the compiler: the cast through
 // address_space(1) makes its accesses global_* instead of flat_* (COH = false: the kernel's own argument, already global)
@@ -256,7 +294,7 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
     int tid = thread_id<COH>(), lane = tid & 63, wave = tid >> 6;
     int li = lane & 15, g = lane >> 4;
     const int m0 = by_ * 16 * RB, ncol0 = bx_ * 16 * CB;
-    const int kper = K_ / (ks_ * kz_);
+    const int kper = opaque_if<COH>(K_ / (ks_ * kz_));   // (opaque: the K loops' entry tests are otherwise evaluated once per phase and parked, as booleans, in vector registers)
     const int kbase = bz_ * (K_ / kz_);
     const bool active = wave < ks_;
     // Buffer loads: a wave-uniform 128-bit descriptor per tensor in SGPRs + ONE 32-bit byte offset per lane and block (the
@@ -290,7 +328,14 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
 #pragma unroll
         for (int cb = 0; cb < CB; ++cb) acc[rb][cb] = {0.f, 0.f, 0.f, 0.f};
     }
-    if (active) {
+    // The K loop, once per kind of launch (LN: the folded LayerNorm's): the LayerNorm copy subtracts the row's shift (ln_shift, from the
+    // row's first 16 bytes) from every x it has loaded and sums the statistics of what it then feeds to the MFMAs; the plain copy is
+    // the loop without either -- no test of p.ln_s inside a batch.
+    auto k_loop = [&](auto ln_tag) {
+        constexpr bool LN = decltype(ln_tag)::value;
+        float lc[RB];
+#pragma unroll
+        for (int rb = 0; rb < RB; ++rb) lc[rb] = LN ? ln_shift(buf_load4<XAUX>(xr, xofs[rb] - koff * 4u, 0)) : 0.f;
         // full batches: U unconditional 16-byte loads per block row of W and of x in flight per lane, then the MFMAs (one
         // accumulator chain per block: the dependent MFMAs of a chain cost a few cycles each)
         int k0 = 0;
@@ -309,11 +354,12 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
             for (int u = 0; u < U; ++u) {
 #pragma unroll
                 for (int rb = 0; rb < RB; ++rb) {
+                    if constexpr (LN) ln_center(xv[rb][u], lc[rb]);
 #pragma unroll
                     for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
                         for (int t = 0; t < 4; ++t) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[rb][u][t], wv[cb][u][t], acc[rb][cb], 0, 0, 0);
-                    if (p.ln_s) ln_accum(xv[rb][u], sx[rb], sxx[rb]);
+                    if constexpr (LN) ln_accum(xv[rb][u], sx[rb], sxx[rb]);
                 }
             }
         }
@@ -325,17 +371,25 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
             for (int rb = 0; rb < RB; ++rb) x1[rb] = buf_load4<XAUX>(xr, xofs[rb], k0 * 4);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
+                if constexpr (LN) ln_center(x1[rb], lc[rb]);
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb)
 #pragma unroll
                     for (int t = 0; t < 4; ++t) acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1[rb][t], w1[cb][t], acc[rb][cb], 0, 0, 0);
-                if (p.ln_s) ln_accum(x1[rb], sx[rb], sxx[rb]);
+                if constexpr (LN) ln_accum(x1[rb], sx[rb], sxx[rb]);
             }
         }
+    };
+    if (active) {
+        // (the persistent step: tested on the pointer's own words where it is used -- as a loop-invariant boolean it is parked in a vector register)
+        const unsigned long long lnp = (unsigned long long)p.ln_s;
+        if (opaque_if<COH>((int)((unsigned)lnp | (unsigned)(lnp >> 32))) != 0) k_loop(ln_on<true>{});
+        else k_loop(ln_on<false>{});
     }
-    if constexpr (WT) {
+    if constexpr (WT || COH) {
         // the lane maps of the reduction and the epilogue, derived again from a thread index the optimiser cannot see through: ONE register
-        // live across the K loop instead of the maps themselves (with them, the tiled 2 x 2 form took 36 + 16 registers, not 32 + 16)
+        // live across the K loop instead of the maps themselves (with them, the tiled 2 x 2 form took 36 + 16 registers, not 32 + 16; the
+        // persistent step's row-major 2 x 2 body, under its 64-register cap, spilled the thread index once the LayerNorm shifts joined them)
         asm volatile("" : "+v"(tid));
         // (the launch form knows threadIdx.x's range and runs the finishing loop below at most once: say so again.  The persistent form never
         // knew -- thread_id<true> -- and with the loop unrolled its phase loop spills 52-84 bytes)
@@ -361,7 +415,7 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
         float a = 0.f, b = 0.f;
         for (int w = 0; w < GEMM_WAVES; ++w) { a += stat[((w * RB + rb) * 16 + r) * 2]; b += stat[((w * RB + rb) * 16 + r) * 2 + 1]; }
         float mean, rstd;
-        ln_finish(a, b, p.K, p.ln_eps, mean, rstd);
+        ln_finish(a, b, opaque_if<COH>(p.K), p.ln_eps, mean, rstd);
         fin[tid * 2] = mean;
         fin[tid * 2 + 1] = rstd;
     }
@@ -412,6 +466,7 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
         if (finisher && col < p.N) {
             const float bv = p.bias ? GP(p.bias)[col] : 0.f;
             const float sn = p.ln_s ? GP(p.ln_s)[col] : 0.f;
+            const int pD = opaque_if<COH>(p.D), pTq = opaque_if<COH>(p.Tq);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = mb0 + 4 * g + r;
@@ -422,10 +477,10 @@ __device__ __forceinline__ void gemm16_tile(const float* __restrict__ x_, const 
                     const int cc = col - p.C;
                     float* cache = cc >= p.C ? GP(p.vcache) : GP(p.kcache);
                     const int c2 = cc >= p.C ? cc - p.C : cc;
-                    const int h = c2 / p.D, d = c2 - h * p.D;
-                    const int b = row / p.Tq, t = row - b * p.Tq;
-                    const int pos = p.pos0 + (p.pos_dev ? GP(p.pos_dev)[p.grp_rows > 0 ? b / p.grp_rows : 0] : 0);
-                    if (pos + t < p.Tmax) st_act<COH>(cache + (((long)b * p.H + h) * p.Tmax + pos + t) * p.D + d, v);
+                    const int h = c2 / pD, d = c2 - h * pD;
+                    const int b = row / pTq, t = row - b * pTq;
+                    const int pos = p.pos0 + (p.pos_dev ? GP(p.pos_dev)[p.grp_rows > 0 ? b / opaque_if<COH>(p.grp_rows) : 0] : 0);
+                    if (pos + t < p.Tmax) st_act<COH>(cache + (((long)b * p.H + h) * p.Tmax + pos + t) * pD + d, v);
                 } else {
                     st_act<COH>(GP(p.y) + (long)row * p.ldy + col, v);
                 }
@@ -466,6 +521,10 @@ __global__ __launch_bounds__(512) void gemm16_rb_kernel(Gemm16 p) {
     float sx[RB], sxx[RB];
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb) { acc0[rb] = {0.f, 0.f, 0.f, 0.f}; acc1[rb] = {0.f, 0.f, 0.f, 0.f}; sx[rb] = 0.f; sxx[rb] = 0.f; }
+    float lc[RB];   // the folded LayerNorm's shift of this lane's rows (ln_shift)
+#pragma unroll
+    for (int rb = 0; rb < RB; ++rb)
+        lc[rb] = active && p.ln_s ? ln_shift(*reinterpret_cast<const float4*>(p.x + (long)min(m0 + 16 * rb + li, p.M - 1) * p.ldx)) : 0.f;
     if (active) {
         int k0 = 0;
         for (; k0 + 16 * GEMM_U_RB <= kper; k0 += 16 * GEMM_U_RB) {
@@ -479,11 +538,11 @@ __global__ __launch_bounds__(512) void gemm16_rb_kernel(Gemm16 p) {
                 for (int u = 0; u < GEMM_U_RB; ++u) xv[u] = *reinterpret_cast<const float4*>(xp[rb] + k0 + 16 * u);
 #pragma unroll
                 for (int u = 0; u < GEMM_U_RB; ++u) {
+                    if (p.ln_s) { ln_center(xv[u], lc[rb]); ln_accum(xv[u], sx[rb], sxx[rb]); }
                     acc0[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[u].x, wv[u].x, acc0[rb], 0, 0, 0);
                     acc1[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[u].y, wv[u].y, acc1[rb], 0, 0, 0);
                     acc0[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[u].z, wv[u].z, acc0[rb], 0, 0, 0);
                     acc1[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[u].w, wv[u].w, acc1[rb], 0, 0, 0);
-                    if (p.ln_s) ln_accum(xv[u], sx[rb], sxx[rb]);
                 }
             }
         }
@@ -491,12 +550,12 @@ __global__ __launch_bounds__(512) void gemm16_rb_kernel(Gemm16 p) {
             const float4 w1 = *reinterpret_cast<const float4*>(wp + k0);
 #pragma unroll
             for (int rb = 0; rb < RB; ++rb) {
-                const float4 x1 = *reinterpret_cast<const float4*>(xp[rb] + k0);
+                float4 x1 = *reinterpret_cast<const float4*>(xp[rb] + k0);
+                if (p.ln_s) { ln_center(x1, lc[rb]); ln_accum(x1, sx[rb], sxx[rb]); }
                 acc0[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1.x, w1.x, acc0[rb], 0, 0, 0);
                 acc1[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1.y, w1.y, acc1[rb], 0, 0, 0);
                 acc0[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1.z, w1.z, acc0[rb], 0, 0, 0);
                 acc1[rb] = __builtin_amdgcn_mfma_f32_16x16x4f32(x1.w, w1.w, acc1[rb], 0, 0, 0);
-                if (p.ln_s) ln_accum(x1, sx[rb], sxx[rb]);
             }
         }
     }
@@ -565,7 +624,9 @@ __global__ __launch_bounds__(512) void gemm16_rb_kernel(Gemm16 p) {
 //     consecutive 16-byte units per lane half: conflict-free ds_read_b128;
 //   * lane half h reads k = 8 s + 4 h .. + 3 of sub-step s for both operands, and MFMA j of the sub-step contracts the pair
 //     (8 s + j, 8 s + 4 + j): the contraction order over k is free as long as both operands agree;
-//   * the folded LayerNorm's row statistics are summed from the x stages in LDS (thread t: row t >> 1, k quads 2 (t & 1), +1);
+//   * the folded LayerNorm: the stages hold the raw x; the shifts of the lane's two fragment rows (ln_shift: read from global memory
+//     once) are subtracted from the x fragments as they leave LDS, and the row statistics are summed from those very fragments (lane
+//     half h: k quads h and 2 + h of rows 64 wr + 32 bi + l31; the two waves of a tile row hold the same fragments and sum the same bits);
 //   * epilogue as everywhere (LayerNorm fold, bias, GELU, residual, K / V scatter into the cache); a 32 x 32 block leaves as
 //     128-byte row segments.
 // A row's arithmetic depends on (N, K) only -- never on M or on the tile the row falls into -- so a batch prefilled alone and
@@ -608,7 +669,7 @@ __global__ __launch_bounds__(256, 4) void gemm_seq_kernel(Gemm16 p, int row_tile
         xoff[hf] = (unsigned)((long)min(m0 + 64 * hf + lane, p.M - 1) * p.ldx + 4 * wave) * 4u;
         woff[hf] = (unsigned)((long)min(n0 + 64 * hf + lane, p.N - 1) * p.K + 4 * wave) * 4u;
     }
-    const int wr = wave >> 1, wc = wave & 1, l31 = lane & 31, h = lane >> 5;
+    int wr = wave >> 1, wc = wave & 1, l31 = lane & 31, h = lane >> 5;
     f32x16 acc[2][2];
 #pragma unroll
     for (int bi = 0; bi < 2; ++bi)
@@ -616,7 +677,13 @@ __global__ __launch_bounds__(256, 4) void gemm_seq_kernel(Gemm16 p, int row_tile
         for (int bj = 0; bj < 2; ++bj)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[bi][bj][r] = 0.f;
-    float sx = 0.f, sxx = 0.f;
+    float sx[2] = {0.f, 0.f}, sxx[2] = {0.f, 0.f};
+    float lca[2] = {0.f, 0.f};   // ln_shift of the rows of a[..][0] and a[..][1] (LDS row r = x row min(m0 + r, M - 1)); 0 without LayerNorm
+    if (p.ln_s) {
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi)
+            lca[bi] = ln_shift(*reinterpret_cast<const float4*>(p.x + (long)min(m0 + 64 * wr + 32 * bi + l31, p.M - 1) * p.ldx));
+    }
     const int nst = p.K / 16;
 #define GS_DMA(k0, SM)                                                                                             \
     _Pragma("unroll") for (int hf = 0; hf < 2; ++hf) {                                                             \
@@ -627,28 +694,26 @@ __global__ __launch_bounds__(256, 4) void gemm_seq_kernel(Gemm16 p, int row_tile
     {                                                                                                              \
         const f32x4* xa = (SM);                                                                                    \
         const f32x4* wb = (SM) + 4 * GS_QS;                                                                        \
-        f32x4 a[2][2], b[2][2], t0, t1;                                                                            \
+        f32x4 a[2][2], b[2][2];                                                                                    \
         _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2) {                                                         \
             const int q = 2 * s2 + h;                                                                              \
             _Pragma("unroll") for (int bi = 0; bi < 2; ++bi) a[s2][bi] = xa[q * GS_QS + 64 * wr + 32 * bi + l31];  \
             _Pragma("unroll") for (int bj = 0; bj < 2; ++bj) b[s2][bj] = wb[q * GS_QS + 64 * wc + 32 * bj + l31];  \
         }                                                                                                          \
-        if (p.ln_s) {                                                                                              \
-            const int r = tid >> 1, q0 = 2 * (tid & 1);                                                            \
-            t0 = xa[q0 * GS_QS + r];                                                                               \
-            t1 = xa[(q0 + 1) * GS_QS + r];                                                                         \
-        }                                                                                                          \
         /* every LDS read of this stage is issued BEFORE the next stage's DMA: hipcc orders a ds_read behind any */ \
         /* LDS-DMA still in flight (s_waitcnt vmcnt(0)), which would serialise the stages                        */ \
         NEXT_DMA                                                                                                   \
+        /* lca is 0 in a launch without LayerNorm, and x - 0 is x, bit for bit */                                  \
+        _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2)                                                           \
+            _Pragma("unroll") for (int bi = 0; bi < 2; ++bi) ln_center(a[s2][bi], lca[bi]);                        \
         _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2)                                                           \
             _Pragma("unroll") for (int j = 0; j < 4; ++j)                                                          \
                 _Pragma("unroll") for (int bi = 0; bi < 2; ++bi)                                                   \
                     _Pragma("unroll") for (int bj = 0; bj < 2; ++bj)                                               \
                         acc[bi][bj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s2][bi][j], b[s2][bj][j], acc[bi][bj], 0, 0, 0); \
         if (p.ln_s) {                                                                                              \
-            ln_accum(t0, sx, sxx);                                                                                 \
-            ln_accum(t1, sx, sxx);                                                                                 \
+            _Pragma("unroll") for (int s2 = 0; s2 < 2; ++s2)                                                       \
+                _Pragma("unroll") for (int bi = 0; bi < 2; ++bi) ln_accum(a[s2][bi], sx[bi], sxx[bi]);             \
         }                                                                                                          \
     }
     GS_DMA(0, sm0)
@@ -661,14 +726,22 @@ __global__ __launch_bounds__(256, 4) void gemm_seq_kernel(Gemm16 p, int row_tile
     }
 #undef GS_DMA
 #undef GS_STAGE
+    {   // the epilogue's lane maps, derived again from a thread index the optimiser cannot see through: the stage loop runs at the
+        // 128-register cap of four workgroups per CU, and a map kept across it for the epilogue's sake is spilled
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        wr = t >> 7; wc = (t >> 6) & 1; l31 = t & 31; h = (t >> 5) & 1;
+    }
     if (p.ln_s) {
-        sx += __shfl_xor(sx, 1, 64);
-        sxx += __shfl_xor(sxx, 1, 64);
-        if (!(tid & 1)) {
-            float mean, rstd;
-            ln_finish(sx, sxx, p.K, p.ln_eps, mean, rstd);
-            fin[(tid >> 1) * 2] = mean;
-            fin[(tid >> 1) * 2 + 1] = rstd;
+#pragma unroll
+        for (int bi = 0; bi < 2; ++bi) {
+            const float a = sx[bi] + __shfl_xor(sx[bi], 32, 64), b = sxx[bi] + __shfl_xor(sxx[bi], 32, 64);
+            if (wc == 0 && h == 0) {
+                float mean, rstd;
+                ln_finish(a, b, p.K, p.ln_eps, mean, rstd);
+                fin[(64 * wr + 32 * bi + l31) * 2] = mean;
+                fin[(64 * wr + 32 * bi + l31) * 2 + 1] = rstd;
+            }
         }
         __syncthreads();
     }
@@ -1620,7 +1693,7 @@ __device__ __forceinline__ void step_barrier(StepBar* bar, unsigned target, int 
     __syncthreads();
     if (threadIdx.x < 64) {
         if (threadIdx.x == 0) __hip_atomic_fetch_add(&bar->shard[blockIdx.x & 7][0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned* sp = &bar->shard[threadIdx.x & 7][0];
+        const unsigned* sp = &bar->shard[thread_id<true>() & 7][0];   // (opaque: otherwise built once in front of the phase loop and held in a register pair across every phase)
         const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
         for (unsigned spins = 1;; ++spins) {
             unsigned v = __hip_atomic_load(sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1692,7 +1765,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const STEP_CONST StepPhase* prog = (const STEP_CONST StepPhase*)ap->prog;
     const int n_phases = ap->n_phases;
     const float att_scale = ap->scale;
-    unsigned target = __hip_atomic_load(&bar->base[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (a vector load of a uniform word: read into a scalar register, or the barriers' target holds a vector register across every phase)
+    unsigned target = __builtin_amdgcn_readfirstlane(__hip_atomic_load(&bar->base[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     {   // embedding of the last picked token at row pos_off + *len (gpt_embed_kernel)
         const int B = ap->B, C = ap->C, vocab = ap->vocab, grp_rows = ap->grp_rows, pos_off = ap->pos_off;
         const int64_t* tok = as_global(ap->tok);

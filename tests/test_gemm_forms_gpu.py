@@ -10,7 +10,10 @@ added (Higham, Accuracy and Stability of Numerical Algorithms, 3.1); for these z
 sqrt(k) and the errors behave as a random walk, so the observed error is ~1e-7 * A.  The check is |got - want| <= 1e-5 * A per
 element: two orders of magnitude of headroom, while a wrong tile, a stale or doubled K stage or a clamped row leaking into the
 output is an O(1) fraction of A.  The LayerNorm fold (y = rstd (x @ wg^T - mean s) + bb) is bounded the same way with
-A = rstd (|x| @ |wg|^T + |mean| |s|) + |bb|.
+A = rstd (|x| @ |wg|^T + |mean| |s|) + |bb|.  That A is the size of the fold's own intermediates on the raw activations: it
+grows with |mean| / std exactly as such a fold loses accuracy, so it says nothing about rows of large mean (and these suites draw
+mean 0.3, std 0.7).  The bound that does not depend on a row's mean, and the rows that need it, are in tests/ln_fold_ref.py and
+tests/test_ln_fold_gpu.py.
 
 The decode forms (single-position calls, no GEMM_SEQ: `gemm16_kernel<1,1,4>` up to 32 rows or under 32 columns, `gemm16_kernel<2,2,1>`
 up to 256 rows, `gemm16_rb_kernel<4>` beyond) get the same treatment below: `plan` transcribes the library's K partition (`gemm_kz`,

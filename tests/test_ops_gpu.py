@@ -616,7 +616,8 @@ def test_kv_append_strided_views_at_a_device_position(ops):
 def test_layernorm_vs_float64(ops, rows, C):
     """layernorm_kernel (one wave per row, 4 rows per workgroup: rows 1 / 4 / 5 = a part-filled, a full and a second workgroup;
     C below, on and above the 64 lanes, and 16 elements per lane) against float64, with the last row constant (y must be
-    exactly beta: every x - mean is 0) and, where there are more rows, row 0 of mean 1e3 and std 1.
+    exactly beta: every x - mean is 0) and, where there are more rows, row 0 of mean 1e3 and std 1, row 1 with its first element
+    the outlier (1 in front of N(0, 1e-3)) and row 2 the same around a large mean (-200 in front of N(100, 1)).
 
     Tolerance eps32 * (8 |y| + |gamma| sqrt(C) + |beta|), per element, from y = xhat gamma + beta with xhat = (x - mean) rstd:
       * the product xhat gamma and the sum with beta round once each, and rstd (a mean of C squares, rsqrtf) and x - mean carry
@@ -626,11 +627,19 @@ def test_layernorm_vs_float64(ops, rows, C):
         reach y multiplied by rstd gamma.  With terms of the size of the row's spread (rstd x term ~ 1) that is
         eps sqrt(C) |gamma|.  A kernel that sums the raw x instead has terms of size |mean|, not of the spread, and loses
         |mean| / std of this: the row of mean 1e3 is here to say so (summing the raw x, the kernel reached 83 x this tolerance
-        on that row and 2.5 x on a constant row of 0.1 at C = 1024; shifted by the row's first element it stays below 0.55)."""
+        on that row and 2.5 x on a constant row of 0.1 at C = 1024; shifted by the row's first element it stays below 0.55).
+        The shift must itself lie within a few std of the mean: on rows 1 and 2 the first element is |x0 - mean| ~ sqrt(C) std
+        away, and the kernel shifted by it alone reached 1.1 to 2.1 x this tolerance there (C = 64 .. 4096); it shifts by the
+        mean of the first four elements now."""
     g = torch.Generator().manual_seed(100 * rows + C)
     x = torch.randn(rows, C, generator=g)
     if rows > 1:
         x[0] = 1e3 + torch.randn(C, generator=g)
+    if rows > 3:
+        x[1] = 1e-3 * torch.randn(C, generator=g)
+        x[1, 0] = 1.0
+        x[2] = 100 + torch.randn(C, generator=g)
+        x[2, 0] = -200.0
     x[rows - 1] = 0.1 if rows == 1 else 1e3 / 3
     gam, bet = torch.randn(C, generator=g) * 0.3 + 1.0, torch.randn(C, generator=g)
     got = ops.layernorm(x.cuda(), gam.cuda(), bet.cuda()).cpu()
