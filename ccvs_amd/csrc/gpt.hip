@@ -1320,9 +1320,18 @@ extern "C" int ccvs_attention(const float* q, int64_t q_sB, int64_t ldq, const f
 // argmax(p) (greedy) or argmax(p / Exp(1) noise) (== torch.multinomial(p, 1)).
 // One workgroup per row; the k-th largest value is found by a 32-step radix descent on
 // order-preserving integer keys.
+// ZEROS: -0.0 and +0.0 share one key, as they compare equal in the reference's `out < v[-1]` mask: a k-th value of +0.0 keeps
+// every -0.0 logit and the other way round.
+// NON-FINITE ROWS: a NaN or +inf logit, or a row of -inf throughout, makes the row's total -- and with it every score -- NaN, so
+// no score compares greater than any other.  Such a row returns token 0 (vq_argmin_kernel's rule, and torch.argmax's on an all-NaN
+// row); sample_topn returns 0, 1, ..., n - 1: in any round without a winner, the lowest index not yet taken.  A stored index is
+// always inside [0, V).
+// PHILOX COUNTER: (c0, c1, c2, c3) = (element j, row0 + row inside its group, step, call), key (key0, key1), output word 0;
+// step = 0xffffffff for the eager first pick of a call, then state[0] = 0, 1, ... in the decode steps.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned fkey(float f) {
-    const unsigned u = __float_as_uint(f);
+    unsigned u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0u;   // -0.0 == +0.0
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -1427,8 +1436,9 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
     if (lane == 0) redf[wave] = lsum;
     __syncthreads();
     const float tot = ((redf[0] + redf[1]) + redf[2]) + redf[3];
-    // counter = (element, GLOBAL row = state[6] + b, step, call = state[3]): a clip's draws do not depend on which rank /
-    // batch slot it runs in, nor on how many other clips share the launch
+    // counter = (element, GLOBAL row = state[6] of the row's group + its index inside the group (mod 2^32), step, call = state[3]):
+    // a clip's draws do not depend on which rank / batch slot it runs in, nor on how many other clips share the launch
+    // (tests/pick_ref.py mirrors the draw on the host; tests/test_pick_gpu.py compares every pick with it)
     unsigned k0 = 0u, k1 = 0u, step = 0u, row0 = 0u, call = 0u;
     if (adv.rng == 2) {
         k0 = adv.imm[0]; k1 = adv.imm[1]; row0 = adv.imm[2]; step = adv.imm[3]; call = adv.imm[4];
@@ -1463,6 +1473,7 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
             if (redf[w] > best || (redf[w] == best && redj[w] < bi)) { best = redf[w]; bi = redj[w]; }
+        if (bi >= V) bi = 0;   // no score compared greater than any other (NaN throughout): token 0, never an index outside [0, V)
         out[(long)b * out_stride] = bi;
         if (adv.codes) {
             adv.codes[(long)b * adv.codes_sB + *adv.widx] = bi;
@@ -1577,6 +1588,11 @@ __global__ __launch_bounds__(256) void sample_topn_kernel(const float* __restric
         sc[j] = noise ? p / noise[(long)b * V + j] : p;
     }
     __syncthreads();
+    int free_lo = 0;   // (thread 0) no index below it is free: taken indices stay taken, so it only moves up
+    // log p = (x_i - max) - log(sum e), in double: the difference of two fp32 values is exact there, so a pick's log p carries
+    // the roundings of the sum and one rounding to fp32, not those of its own expf, division and a logf of a result far below -1
+    // (half an ulp of a log p in [-16, -8) is 2^-21; logf(p) was off by up to four times that on the least probable entries).
+    const double ltot = tid == 0 ? log((double)tot) : 0.0;
     for (int r = 0; r < n; ++r) {
         float best = -1.f;
         int bi = 0x7fffffff;
@@ -1595,9 +1611,13 @@ __global__ __launch_bounds__(256) void sample_topn_kernel(const float* __restric
         if (tid == 0) {
             for (int w = 1; w < 4; ++w)
                 if (redf[w] > best || (redf[w] == best && redj[w] < bi)) { best = redf[w]; bi = redj[w]; }
-            bi = min(bi, V - 1);
+            if (bi >= V) {   // no winner (the scores left are NaN): the lowest index not yet taken
+                while (free_lo < V - 1 && sc[free_lo] == -2.f) ++free_lo;   // (fewer than n <= V are taken: one is free)
+                bi = free_lo;
+            }
             out_idx[(long)b * n + r] = bi;
-            out_logp[(long)b * n + r] = logf(xs[bi]);
+            const float p = xs[bi];   // 0 (masked or underflowed: log p = -inf) and NaN rows keep logf's answer
+            out_logp[(long)b * n + r] = p > 0.f ? (float)(((double)(lr[bi] / temperature) - (double)gmax) - ltot) : logf(p);
             sc[bi] = -2.f;   // taken
         }
         __syncthreads();
