@@ -1328,6 +1328,17 @@ extern "C" int ccvs_attention(const float* q, int64_t q_sB, int64_t ldq, const f
 // always inside [0, V).
 // PHILOX COUNTER: (c0, c1, c2, c3) = (element j, row0 + row inside its group, step, call), key (key0, key1), output word 0;
 // step = 0xffffffff for the eager first pick of a call, then state[0] = 0, 1, ... in the decode steps.
+// NUCLEUS (the TOPP form only; include/ccvs_hip_sampling.h has the definition): on the top-k set, e_j = expf(xs_j - max) as the pick
+// itself computes it, m_j = (uint64) floor(e_j * 2^46) -- the scaling is exact, the conversion truncates: e >= 2^-22 converts exactly,
+// a smaller one loses less than 2^-46, and V < 2^16 entries of at most 2^46 cannot overflow.  T = sum m and every bin mass of the
+// radix descent are sums of these INTEGERS (64-bit LDS adds, wave shuffles): the same bits in any order, so the kept set does not
+// depend on the run, the launch form or the batch slot.  Entry j is kept iff G_j < P, G_j = sum of m_i over the top-k entries with
+// xs_i > xs_j (by key: ties share one fate, -0.0 == +0.0) and P = (uint64) ceil((double) top_p * (double) T), the ONE floating-point
+// product of the decision (for an integer G, G < P is G < top_p * T).  G is not increasing along the descending order, so the kept set
+// is {key >= c}, c = the largest key whose mass at or above it reaches P: found as kth_largest_key finds its key, with per-bin mass
+// in place of per-bin counts and expf recomputed in each pass from xs, which stays in LDS until c is known.  The most likely token
+// has G = 0 < P and is always kept.  The scores then are the top-k form's own bits -- e_j / (the fp32 total of the top-k set) / noise --
+// on the smaller set: the total is a common factor.  A non-finite row (its fp32 total is NaN) skips the descent and ends as above.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned fkey(float f) {
     unsigned u = __float_as_uint(f);
@@ -1393,12 +1404,53 @@ __device__ __forceinline__ unsigned kth_largest_key(const float* xs, int V, int 
     return prefix;
 }
 
+// The nucleus' integer mass of one entry (NUCLEUS above): floor(e * 2^46); 0 for a NaN.
+#define TOPP_MASS_SCALE 70368744177664.0f   // 2^46
+__device__ __forceinline__ unsigned long long topp_mass(float e) {
+    return e == e ? (unsigned long long)(e * TOPP_MASS_SCALE) : 0ull;
+}
+
+// The nucleus' boundary key: the largest key c such that the entries of the top-k set (key >= thr) with key >= c hold a mass of at least
+// `need` (1 <= need <= their total mass).  kth_largest_key's 4-pass radix-256 descent with per-bin mass in place of per-bin counts.
+__device__ __forceinline__ unsigned topp_boundary_key(const float* xs, int V, unsigned thr, float gmax, unsigned long long need,
+                                                      unsigned long long* mass, unsigned long long* wtot, unsigned long long* sel, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    unsigned prefix = 0u, mask = 0u;
+#pragma unroll 1
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        mass[tid] = 0ull;
+        __syncthreads();
+        for (int j = tid; j < V; j += 256) {
+            const unsigned key = fkey(xs[j]);
+            if (key >= thr && (key & mask) == prefix) atomicAdd(&mass[(key >> shift) & 255u], topp_mass(expf(xs[j] - gmax)));
+        }
+        __syncthreads();
+        const unsigned long long h = mass[tid];
+        unsigned long long s = h;  // suffix sum over bins >= tid
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long t = __shfl_down(s, o, 64);
+            if (lane + o < 64) s += t;
+        }
+        if (lane == 0) wtot[wave] = s;
+        __syncthreads();
+        for (int w = wave + 1; w < 4; ++w) s += wtot[w];
+        if (s >= need && s - h < need) { sel[0] = (unsigned long long)tid; sel[1] = need - (s - h); }
+        __syncthreads();
+        prefix |= (unsigned)sel[0] << shift;
+        mask |= 255u << shift;
+        need = sel[1];
+    }
+    return prefix;
+}
+
 // (b = the row, B_all = the rows of the launch; smem = PICK_SMEM_WORDS(V) floats.  COH: the logits were written by the head GEMM phase
-//  of the same launch -- sc1 loads.)
-template <bool COH>
+//  of the same launch -- sc1 loads.  TOPP: the nucleus form -- smem = PICK_TOPP_SMEM_WORDS(V) floats, 0 < top_p < 1; without it top_p
+//  is not read and the body is the one this function had before it took the parameter.)
+template <bool COH, bool TOPP = false>
 __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits, long ld, const float* __restrict__ noise,
                                                 int64_t* __restrict__ out, long out_stride, int V, int top_k, float temperature,
-                                                Advance adv, int b, int B_all, float* smem) {
+                                                Advance adv, int b, int B_all, float* smem, float top_p = 0.f) {
     float* xs = smem;                  // [V]
     float* redf = smem + V;            // [4]
     int* redj = (int*)(smem + V + 4);  // [4]
@@ -1426,9 +1478,11 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
     unsigned thr = 0u;  // key of the k-th largest value; 0 keeps everything
     if (top_k > 0 && top_k < V) thr = kth_largest_key(xs, V, top_k, hist, wtot, sel, tid);
     float lsum = 0.f;
+    unsigned long long msum = 0ull;   // TOPP: this thread's share of the integer total T
     for (int j = tid; j < V; j += 256) {
         const float e = (fkey(xs[j]) >= thr) ? expf(xs[j] - gmax) : 0.f;
-        xs[j] = e;
+        if constexpr (TOPP) msum += topp_mass(e);   // xs stays: the descent below needs the order of entries whose e round equal
+        else xs[j] = e;
         lsum += e;
     }
     lsum = wave_sum(lsum);
@@ -1436,6 +1490,22 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
     if (lane == 0) redf[wave] = lsum;
     __syncthreads();
     const float tot = ((redf[0] + redf[1]) + redf[2]) + redf[3];
+    if constexpr (TOPP) {
+        // the 64-bit words lie behind the top-k form's block, on an 8-byte boundary: mass bins [256], wave totals [4], the selected bin [2]
+        unsigned long long* mass = (unsigned long long*)(smem + ((V + 16 + 256 + 1) & ~1));
+        unsigned long long* wtot64 = mass + 256;
+        unsigned long long* sel64 = mass + 260;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) msum += __shfl_xor(msum, o, 64);
+        if (lane == 0) wtot64[wave] = msum;
+        __syncthreads();
+        const unsigned long long T = wtot64[0] + wtot64[1] + wtot64[2] + wtot64[3];
+        __syncthreads();   // (the descent writes wtot64 again)
+        if (tot == tot) {  // a finite row: T >= 2^46 (the maximum's own mass), 1 <= P <= T
+            const unsigned long long P = (unsigned long long)ceil((double)top_p * (double)T);
+            thr = topp_boundary_key(xs, V, thr, gmax, P, mass, wtot64, sel64, tid);
+        }
+    }
     // counter = (element, GLOBAL row = state[6] of the row's group + its index inside the group (mod 2^32), step, call = state[3]):
     // a clip's draws do not depend on which rank / batch slot it runs in, nor on how many other clips share the launch
     // (tests/pick_ref.py mirrors the draw on the host; tests/test_pick_gpu.py compares every pick with it)
@@ -1453,7 +1523,9 @@ __device__ __forceinline__ void sample_topk_row(const float* __restrict__ logits
     float best = -1.f;
     int bi = 0x7fffffff;
     for (int j = tid; j < V; j += 256) {
-        float p = xs[j] / tot;
+        float p;
+        if constexpr (TOPP) p = ((fkey(xs[j]) >= thr) ? expf(xs[j] - gmax) : 0.f) / tot;   // the e of the total's pass, on the nucleus
+        else p = xs[j] / tot;
         if (nrow) p = p / nrow[j];
         else if (adv.rng) {
             const float u = ((float)philox_first((unsigned)j, row0 + (unsigned)brow, step, call, k0, k1) + 0.5f) * 2.3283064365386963e-10f;  // (0, 1]
@@ -1537,6 +1609,69 @@ extern "C" int ccvs_sample_topk_philox(const float* logits, int64_t ld, int64_t*
                        (long)out_stride, V, top_k, temperature, adv);
     CCVS_CHECK_LAUNCH("ccvs_sample_topk_philox");
     return CCVS_OK;
+}
+
+// The nucleus form of the pick (include/ccvs_hip_sampling.h): the same row body with TOPP, in a kernel of its own -- sample_topk_kernel
+// and what reaches it stay as they are.  Its LDS: the top-k form's block, then (on an 8-byte boundary) 262 64-bit words.
+__global__ __launch_bounds__(256) void sample_topp_kernel(const float* __restrict__ logits, long ld, const float* __restrict__ noise,
+                                                          int64_t* __restrict__ out, long out_stride, int V, int top_k, float temperature,
+                                                          float top_p, Advance adv) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    sample_topk_row<false, true>(logits, ld, noise, out, out_stride, V, top_k, temperature, adv, blockIdx.x, gridDim.x, smem, top_p);
+}
+
+#define PICK_TOPP_SMEM_WORDS(V) ((((V) + 16 + 256 + 1) & ~1) + 2 * 262)
+static void pick_topp_allow_big_lds() {
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)sample_topp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr_set = true;
+    }
+}
+
+// the largest vocabulary whose PICK_TOPP_SMEM_WORDS fit the 160 KB of dynamic LDS
+extern "C" int32_t ccvs_sample_topp_max_vocab(void) {
+    int32_t v = 160 * 1024 / 4 - (16 + 256 + 1 + 2 * 262);
+    while ((size_t)PICK_TOPP_SMEM_WORDS(v + 1) * sizeof(float) <= 160 * 1024) ++v;
+    return v;
+}
+
+// 0 < top_p < 1: the nucleus is on.  1: off (the callers below then run the top-k form).  Anything else, NaN included, is refused.
+static bool topp_on(float top_p) { return top_p > 0.f && top_p < 1.f; }
+
+static int launch_sample_topp(const char* who, const float* logits, int64_t ld, const float* noise, int64_t* out, int64_t out_stride,
+                              int32_t B, int32_t V, int32_t top_k, float temperature, float top_p, const Advance& adv, hipStream_t st) {
+    CCVS_REQUIRE(logits && out, "%s: null pointer", who);
+    CCVS_REQUIRE(B > 0 && V > 0 && temperature > 0.f, "%s: bad arguments", who);
+    CCVS_REQUIRE(topp_on(top_p) || top_p == 1.f, "%s: top_p %g is neither inside (0, 1) nor 1 (off)", who, (double)top_p);
+    if (!topp_on(top_p)) {   // off: the top-k form, its own cap
+        const size_t smem = (size_t)PICK_SMEM_WORDS(V) * sizeof(float);
+        CCVS_REQUIRE(smem <= 160 * 1024, "%s: vocabulary %d too large", who, V);
+        pick_allow_big_lds();
+        hipLaunchKernelGGL(sample_topk_kernel, dim3(B), dim3(256), smem, st, logits, (long)ld, noise, out, (long)out_stride, V, top_k, temperature, adv);
+    } else {
+        const size_t smem = (size_t)PICK_TOPP_SMEM_WORDS(V) * sizeof(float);
+        CCVS_REQUIRE(smem <= 160 * 1024, "%s: vocabulary %d too large for the top_p form (at most %d)", who, V, ccvs_sample_topp_max_vocab());
+        pick_topp_allow_big_lds();
+        hipLaunchKernelGGL(sample_topp_kernel, dim3(B), dim3(256), smem, st, logits, (long)ld, noise, out, (long)out_stride, V, top_k, temperature,
+                           top_p, adv);
+    }
+    CCVS_CHECK_LAUNCH(who);
+    return CCVS_OK;
+}
+
+extern "C" int ccvs_sample_topp(const float* logits, int64_t ld, const float* noise, int64_t* out, int64_t out_stride, int32_t B, int32_t V,
+                                int32_t top_k, float temperature, float top_p, void* stream) {
+    return launch_sample_topp("ccvs_sample_topp", logits, ld, noise, out, out_stride, B, V, top_k, temperature, top_p, Advance{}, (hipStream_t)stream);
+}
+
+extern "C" int ccvs_sample_topp_philox(const float* logits, int64_t ld, int64_t* out, int64_t out_stride, int32_t B, int32_t V, int32_t top_k,
+                                       float temperature, float top_p, uint32_t key0, uint32_t key1, uint32_t row0, uint32_t step, uint32_t call,
+                                       void* stream) {
+    Advance adv = {};
+    adv.rng = 2;
+    adv.imm[0] = key0; adv.imm[1] = key1; adv.imm[2] = row0; adv.imm[3] = step; adv.imm[4] = call;
+    return launch_sample_topp("ccvs_sample_topp_philox", logits, ld, nullptr, out, out_stride, B, V, top_k, temperature, top_p, adv, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1706,6 +1841,7 @@ struct StepArgs {
     int top_k;
     float temperature;
     Advance adv;
+    float top_p;   // read by the TOPP form of the step only
 };
 
 __device__ __forceinline__ void step_barrier(StepBar* bar, unsigned target, int phase) {
@@ -1775,7 +1911,9 @@ __device__ __forceinline__ T* as_global(T* p) {
 // hipcc allocates 73 + 16 for this body although no phase needs more than the launch chain's 48: with 256 threads per workgroup it
 // sees no reason to be frugal.  64 fit beside two convolution waves of up to 216 registers per SIMD (the 3 x 3 forms that carry
 // the decoder's time: 208 / 214), not beside the 1 x 1 forms' 225 -- there the step's workgroup waits for one to retire, once per step.
-template <int D, bool T2, bool WT>   // WT: every weight matrix of the phase table is tiled (ccvs_gpt_decode.w_tiled)
+// WT: every weight matrix of the phase table is tiled (ccvs_gpt_decode.w_tiled).  TOPP: the pick phase is the nucleus form
+// (ccvs_gpt_decode.top_p inside (0, 1)) -- instantiations of their own, so that the ones without it are what they were.
+template <int D, bool T2, bool WT, bool TOPP = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void gpt_step_kernel(const StepArgs* __restrict__ ap_) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int RB = T2 ? 2 : 1, CB = T2 ? 2 : 1, U = T2 ? 1 : GEMM_U;
@@ -1838,8 +1976,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         for (int i = 0; i < 5; ++i) adv.imm[i] = 0u;
         adv.state = as_global(ap->adv.state); adv.grp_rows = ap->adv.grp_rows; adv.noise_stream = as_global(ap->adv.noise_stream);
         for (int b = blockIdx.x; b < B; b += G) {
-            sample_topk_row<true>(as_global(ap->logits), (long)V, as_global(ap->noise), const_cast<int64_t*>(as_global(ap->tok)), 1L, V, ap->top_k,
-                                  ap->temperature, adv, b, B, smem);
+            if constexpr (TOPP)
+                sample_topk_row<true, true>(as_global(ap->logits), (long)V, as_global(ap->noise), const_cast<int64_t*>(as_global(ap->tok)), 1L, V,
+                                            ap->top_k, ap->temperature, adv, b, B, smem, ap->top_p);
+            else
+                sample_topk_row<true>(as_global(ap->logits), (long)V, as_global(ap->noise), const_cast<int64_t*>(as_global(ap->tok)), 1L, V, ap->top_k,
+                                      ap->temperature, adv, b, B, smem);
             __syncthreads();
         }
     }
@@ -1957,6 +2099,7 @@ extern "C" int ccvs_gpt_decode_prepare(const ccvs_gpt_decode* d, void* stream) {
     CCVS_REQUIRE(d && d->layers && d->n_layer > 0 && d->C > 0 && d->H > 0 && d->C % d->H == 0, "ccvs_gpt_decode_prepare: bad descriptor");
     int rc = step_check(d, "ccvs_gpt_decode_prepare");
     if (rc != CCVS_OK) return rc;
+    CCVS_REQUIRE(d->top_p == 0.f || d->top_p == 1.f || topp_on(d->top_p), "ccvs_gpt_decode_prepare: top_p %g is neither inside (0, 1) nor 0 / 1 (off)", (double)d->top_p);
     const int grp_rows = step_grp_rows(d), n_ph = 5 * d->n_layer + 1;
     const size_t bytes = (size_t)ccvs_gpt_program_bytes(d->n_layer);
     char* host = (char*)calloc(1, bytes);
@@ -1969,7 +2112,7 @@ extern "C" int ccvs_gpt_decode_prepare(const ccvs_gpt_decode* d, void* stream) {
         a.bar = (StepBar*)((char*)d->workspace + GEMM_WS_BAR_OFFSET);
         a.prog = (const StepPhase*)((const char*)d->program + STEP_HEAD_BYTES);
         a.scale = 1.0f / sqrtf((float)(d->C / d->H));
-        a.noise = d->noise; a.top_k = d->top_k; a.temperature = d->temperature;
+        a.noise = d->noise; a.top_k = d->top_k; a.temperature = d->temperature; a.top_p = d->top_p;
         a.adv = step_advance(d, grp_rows);
     }
     // The kernel runs ONE tile (step_tile2) for all its GEMM phases and the table has n_ph slots: a walk or a plan that disagrees with
@@ -2004,25 +2147,28 @@ static int launch_step_persistent(const ccvs_gpt_decode* d, int D, hipStream_t s
     // room for one -- and every grid barrier then waits for 2-4 x the arrivals (profiles/r06_persistent_step.txt)
     const bool t2 = step_tile2(d);
     size_t words = t2 ? STEP_GEMM_WORDS(2, 2) : STEP_GEMM_WORDS(1, 1);
-    const size_t w_att = 16 + 4 * 256 + (size_t)d->Tmax, w_pick = PICK_SMEM_WORDS(d->V);
+    const bool topp = topp_on(d->top_p);   // (the table's top_p is the one ccvs_gpt_decode_prepare saw: a descriptor changed since is prepared again)
+    const size_t w_att = 16 + 4 * 256 + (size_t)d->Tmax, w_pick = topp ? PICK_TOPP_SMEM_WORDS(d->V) : PICK_SMEM_WORDS(d->V);
     if (w_att > words) words = w_att;
     if (w_pick > words) words = w_pick;
     const size_t smem = words * sizeof(float);
-#define STEP_LAUNCH_(Dv, T2v, WTv)                                                                                                        \
+#define STEP_LAUNCH__(Dv, T2v, WTv, TPv)                                                                                               \
     do {                                                                                                                              \
         static bool attr_set = false;                                                                                                 \
         if (!attr_set) {                                                                                                              \
-            (void)hipFuncSetAttribute((const void*)gpt_step_kernel<Dv, T2v, WTv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+            (void)hipFuncSetAttribute((const void*)gpt_step_kernel<Dv, T2v, WTv, TPv>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
             attr_set = true;                                                                                                          \
         }                                                                                                                             \
-        hipLaunchKernelGGL((gpt_step_kernel<Dv, T2v, WTv>), dim3(n_cu), dim3(256), smem, st, a);                                      \
+        hipLaunchKernelGGL((gpt_step_kernel<Dv, T2v, WTv, TPv>), dim3(n_cu), dim3(256), smem, st, a);                                 \
     } while (0)
+#define STEP_LAUNCH_(Dv, T2v, WTv) do { if (topp) STEP_LAUNCH__(Dv, T2v, WTv, true); else STEP_LAUNCH__(Dv, T2v, WTv, false); } while (0)
 #define STEP_LAUNCH(Dv, T2v) do { if (d->w_tiled) STEP_LAUNCH_(Dv, T2v, true); else STEP_LAUNCH_(Dv, T2v, false); } while (0)
     if (D == 64) { if (t2) STEP_LAUNCH(64, true); else STEP_LAUNCH(64, false); }
     else if (D == 32) { if (t2) STEP_LAUNCH(32, true); else STEP_LAUNCH(32, false); }
     else { if (t2) STEP_LAUNCH(16, true); else STEP_LAUNCH(16, false); }
 #undef STEP_LAUNCH
 #undef STEP_LAUNCH_
+#undef STEP_LAUNCH__
     CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(persistent)");
     return CCVS_OK;
 }
@@ -2046,8 +2192,12 @@ extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
     CCVS_REQUIRE(d->groups <= 1 || d->B <= GEMM_DECODE_MAX_M, "ccvs_gpt_decode_step: at most %d rows per grouped step", GEMM_DECODE_MAX_M);
     const int grp_rows = step_grp_rows(d);
     const size_t smem_att = (size_t)(16 + 4 * 256 + d->Tmax) * sizeof(float);
-    const size_t smem_pick = (size_t)PICK_SMEM_WORDS(d->V) * sizeof(float);
+    // the pick's form: top_p 0 or 1 = off (the top-k form), inside (0, 1) = the nucleus form with its own LDS size and cap
+    CCVS_REQUIRE(d->top_p == 0.f || d->top_p == 1.f || topp_on(d->top_p), "ccvs_gpt_decode_step: top_p %g is neither inside (0, 1) nor 0 / 1 (off)", (double)d->top_p);
+    const bool topp = topp_on(d->top_p);
+    const size_t smem_pick = (size_t)(topp ? PICK_TOPP_SMEM_WORDS(d->V) : PICK_SMEM_WORDS(d->V)) * sizeof(float);
     CCVS_REQUIRE(smem_att <= 64 * 1024, "ccvs_gpt_decode_step: sequence too long for the LDS score buffer");
+    if (topp) CCVS_REQUIRE(smem_pick <= 160 * 1024, "ccvs_gpt_decode_step: vocabulary %d too large for the top_p form (at most %d)", d->V, ccvs_sample_topp_max_vocab());
     CCVS_REQUIRE(smem_pick <= 160 * 1024, "ccvs_gpt_decode_step: vocabulary %d too large", d->V);
     hipStream_t st = (hipStream_t)stream;
     if (d->persistent) {   // ONE launch (gpt_step_kernel) over the phase table ccvs_gpt_decode_prepare wrote to d->program
@@ -2072,8 +2222,14 @@ extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
     });
     if (rc != CCVS_OK) return rc;
     // pick + bookkeeping
-    hipLaunchKernelGGL(sample_topk_kernel, dim3(d->B), dim3(256), smem_pick, st, d->logits, (long)d->V, d->noise, d->tok, 1L, d->V,
-                       d->top_k, d->temperature, step_advance(d, grp_rows));
+    if (topp) {
+        pick_topp_allow_big_lds();
+        hipLaunchKernelGGL(sample_topp_kernel, dim3(d->B), dim3(256), smem_pick, st, d->logits, (long)d->V, d->noise, d->tok, 1L, d->V,
+                           d->top_k, d->temperature, d->top_p, step_advance(d, grp_rows));
+    } else {
+        hipLaunchKernelGGL(sample_topk_kernel, dim3(d->B), dim3(256), smem_pick, st, d->logits, (long)d->V, d->noise, d->tok, 1L, d->V,
+                           d->top_k, d->temperature, step_advance(d, grp_rows));
+    }
     CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(pick)");
     return CCVS_OK;
 }

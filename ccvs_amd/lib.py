@@ -46,6 +46,8 @@ OUTPUT_LOSSLESS_EXPORTS = ["ccvs_apng_workspace_bytes", "ccvs_apng_stream_bound"
 OUTPUT_LOSSLESS_LZ_EXPORTS = ["ccvs_apng_lz_workspace_bytes", "ccvs_apng_encode_lz"]
 # every symbol include/ccvs_hip_decode_lossless.h declares (the way back from it: zlib streams -> bytes, PNG streams -> uint8 frames; included by ccvs_hip.h too)
 DECODE_LOSSLESS_EXPORTS = ["ccvs_png_decode_workspace_bytes", "ccvs_zlib_inflate", "ccvs_png_decode"]
+# every symbol include/ccvs_hip_sampling.h declares (nucleus sampling in the token pick; included by ccvs_hip.h too)
+SAMPLING_EXPORTS = ["ccvs_sample_topp", "ccvs_sample_topp_philox", "ccvs_sample_topp_max_vocab"]
 
 
 class ConvDesc(C.Structure):
@@ -78,7 +80,9 @@ class GptLayer(C.Structure):
 
 
 class GptDecode(C.Structure):
-    """Mirror of `ccvs_gpt_decode`."""
+    """Mirror of `ccvs_gpt_decode`.  The C struct's last field, `float top_p`, follows `w_tiled` in what is this mirror's tail padding
+    (same size either way): it is the `top_p` property below, not an entry of `_fields_`, whose last entry stays `w_tiled` as
+    tests/test_gemm_tiled_gpu.py pins it.  tests/test_nucleus_host.py checks the offset against the C compiler's."""
     _fields_ = [
         ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("F", C.c_int32), ("n_layer", C.c_int32), ("Tmax", C.c_int32),
         ("vocab", C.c_int32), ("V", C.c_int32), ("ln_eps", C.c_float),
@@ -93,6 +97,21 @@ class GptDecode(C.Structure):
         ("noise_stream", C.c_void_p),
         ("persistent", C.c_int32), ("program", C.c_void_p), ("w_tiled", C.c_int32),
     ]
+
+    def _top_p_word(self):
+        return C.c_float.from_address(C.addressof(self) + GptDecode.TOP_P_OFFSET)
+
+    @property
+    def top_p(self):
+        return self._top_p_word().value
+
+    @top_p.setter
+    def top_p(self, value):
+        self._top_p_word().value = value
+
+
+GptDecode.TOP_P_OFFSET = GptDecode.w_tiled.offset + C.sizeof(C.c_int32)
+assert GptDecode.TOP_P_OFFSET + C.sizeof(C.c_float) == C.sizeof(GptDecode)
 
 
 class CcvsError(RuntimeError):
@@ -143,6 +162,8 @@ def load():
     lib.ccvs_png_decode_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ccvs_lpips_layer_workspace_bytes.restype = C.c_int64
     lib.ccvs_lpips_layer_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.ccvs_sample_topp_max_vocab.restype = C.c_int32
+    lib.ccvs_sample_topp_max_vocab.argtypes = []
     lib.ccvs_gpt_program_bytes.restype = C.c_int64
     lib.ccvs_gpt_program_bytes.argtypes = [C.c_int32]
     lib.ccvs_conv_fetch_bytes_per_lane.restype = C.c_int
@@ -177,6 +198,8 @@ def load():
         "ccvs_kv_append": [vp, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp],
         "ccvs_sample_topk": [vp, i64, vp, vp, i64, i32, i32, i32, f32, vp],
         "ccvs_sample_topk_philox": [vp, i64, vp, i64, i32, i32, i32, f32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp],
+        "ccvs_sample_topp": [vp, i64, vp, vp, i64, i32, i32, i32, f32, f32, vp],
+        "ccvs_sample_topp_philox": [vp, i64, vp, i64, i32, i32, i32, f32, f32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp],
         "ccvs_sample_topn": [vp, i64, vp, vp, vp, i32, i32, i32, f32, i32, vp],
         "ccvs_gpt_decode_step": [C.POINTER(GptDecode), vp],
         "ccvs_gpt_decode_status": [vp, vp],

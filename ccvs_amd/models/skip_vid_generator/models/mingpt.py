@@ -255,7 +255,7 @@ class GPT(nn.Module):
         """One eager pick for all rows: `ops.sample_topk` per row group when the noise is drawn in the kernel (each group has
         its own Philox words `words[g]`; `step` = (step word, call-word mask))."""
         if words is None:
-            return ops.sample_topk(logits, sampler["top_k"], sampler["temperature"], noise=noise, out=out)
+            return ops.sample_topk(logits, sampler["top_k"], sampler["temperature"], noise=noise, out=out, top_p=sampler.get("top_p"))
         b = logits.shape[0]
         n = len(words)
         assert b % n == 0
@@ -264,7 +264,7 @@ class GPT(nn.Module):
             out = torch.empty(b, dtype=torch.int64, device=logits.device)
         for g, (k0, k1, row0, call) in enumerate(words):
             ops.sample_topk(logits[g * per:(g + 1) * per], sampler["top_k"], sampler["temperature"], out=out[g * per:(g + 1) * per],
-                            philox=(k0, k1, row0, step[0], call | step[1]))
+                            philox=(k0, k1, row0, step[0], call | step[1]), top_p=sampler.get("top_p"))
         return out
 
     def get_block_size(self):
@@ -568,7 +568,7 @@ class GPT(nn.Module):
         host_stream = bool(sampler["sample"] and not device_rng and sampler.get("stream"))   # host noise read from a pre-drawn stream
         key = (tuple(blk._folded[0] for blk in self.blocks), head_key, sampler["sample"], sampler["top_k"],
                sampler["temperature"], device_rng, host_stream, c["frame_pos0"], bool(self.persistent_step),
-               tuple(blk.tiled()[0] for blk in self.blocks) if tiled else None)
+               tuple(blk.tiled()[0] for blk in self.blocks) if tiled else None, sampler.get("top_p"))
         if c["desc"] is None or c["desc"][0] != key:
             layers = []
             for i, blk in enumerate(self.blocks):
@@ -583,7 +583,8 @@ class GPT(nn.Module):
                 x=c["x"], q=c["q"], att=c["att"], h=c["h"], logits=c["logits"],
                 noise=c["noise"] if (sampler["sample"] and not device_rng and not host_stream) else None, rng=device_rng,
                 noise_stream=c["noise_ptrs"] if host_stream else None,
-                top_k=sampler["top_k"], temperature=sampler["temperature"], state=c["state"], persistent=self.persistent_step,
+                top_k=sampler["top_k"], temperature=sampler["temperature"], top_p=sampler.get("top_p"), state=c["state"],
+                persistent=self.persistent_step,
                 tiled=([blk.tiled()[1] for blk in self.blocks], self._head_tiled()) if tiled else None)
             c["desc"] = (key, desc)
             c["graphs"] = {}   # captured graphs replay the OLD descriptor's pointers (packed weights are freed with it)
@@ -754,7 +755,7 @@ class GPT(nn.Module):
                     run += 1
                 c["len_dev"].fill_(c["len"])
                 c["widx"].fill_(n_code)
-                self._replay_steps(sampler, (sampler["sample"], sampler["top_k"], sampler["temperature"], n_cond, b, "stream"), run)
+                self._replay_steps(sampler, (sampler["sample"], sampler["top_k"], sampler["temperature"], n_cond, b, "stream", sampler.get("top_p")), run)
                 c["len"] += run          # each replay appended the previous pick, then picked the next
                 n_code += run
                 fed += run
@@ -831,8 +832,10 @@ class GPT(nn.Module):
 
     @torch.no_grad()
     def generate(self, code, add_len, cond_idx=None, delta_length_cond=None, sample=False, top_k=None, temperature=1.0,
-                 noise="device", host_noise=None, trace=None, use_graph=True, state_code=None, state_sampler=None, lbl_idx=None):
+                 noise="device", host_noise=None, trace=None, use_graph=True, state_code=None, state_sampler=None, lbl_idx=None,
+                 top_p=None):
         """code [B,t0] -> [B, t0+add_len]: one prefill, then KV-cached decode steps.
+        `top_p` inside (0, 1): nucleus sampling after the top-k mask (None or 1.0: off; `state_sampler` may carry its own "top_p").
         With an ancillary stream (`state_code` [B,ns], `state_sampler` = dict(sample, top_k, temperature, vocab)) the
         add_len new tokens are split between the two streams as the reference does and (code, state_code) is returned.
 
@@ -844,7 +847,10 @@ class GPT(nn.Module):
         b, t0 = code.shape
         use_cond = cond_idx is not None and 0 not in cond_idx.size()
         n_cond = cond_idx.shape[1] if use_cond else 0
-        sampler = {"sample": bool(sample), "top_k": top_k, "temperature": float(temperature), "noise": noise}
+        # (None and 1.0 are one setting, "off": one cache key, and the top-k entry points run)
+        sampler = {"sample": bool(sample), "top_k": top_k, "temperature": float(temperature), "noise": noise, "top_p": ops.check_top_p(top_p)}
+        if state_sampler is not None:
+            state_sampler = dict(state_sampler, top_p=ops.check_top_p(state_sampler.get("top_p")))
         n_pre = self.n_prefix()
         if state_code is not None and 0 not in state_code.size():
             if n_pre:
@@ -891,7 +897,7 @@ class GPT(nn.Module):
         if not eager:
             if self.progress is not None:
                 self.progress(t0 + 1, c["codes"])
-            self._replay_steps(sampler, (bool(sample), top_k, float(temperature), n_pre + n_cond, b), add_len - 1, known=t0 + 1)
+            self._replay_steps(sampler, (bool(sample), top_k, float(temperature), n_pre + n_cond, b, sampler["top_p"]), add_len - 1, known=t0 + 1)
         else:
             for _ in range(add_len - 1):
                 nz = None

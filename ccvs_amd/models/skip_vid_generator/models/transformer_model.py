@@ -214,6 +214,8 @@ class Transformer(torch.nn.Module):
         """transformer_model.py:331-392 on the KV-cached engine."""
         opt = self.opt
         if getattr(opt, "beam_size", None) is not None:
+            if ops.check_top_p(getattr(opt, "top_p", None)) is not None:
+                raise NotImplementedError("--x_top_p together with --x_beam_size: the n-pick kernel of beam search (ops.sample_topn) has no nucleus form")
             return self._beam_fill(code, state_code, cond_code, add_len)
         b, t0 = code.shape
         n_cond = cond_code.size(1) if 0 not in cond_code.size() else 0
@@ -229,9 +231,10 @@ class Transformer(torch.nn.Module):
         state_sampler = None
         if use_state:  # ancillary tokens: first state_num logits, their own sampling options (transformer_model.py:353-356)
             state_sampler = {"sample": bool(opt.sample_state), "top_k": opt.top_k_state, "temperature": float(opt.temperature_state),
-                             "vocab": opt.state_num}
+                             "vocab": opt.state_num, "top_p": getattr(opt, "top_p_state", None)}
         out = self.net_t.generate(code, add_len, cond_code if n_cond else None, delta_length_cond if n_cond else None,
-                                  sample=opt.sample, top_k=opt.top_k, temperature=opt.temperature, noise=self.sample_noise,
+                                  sample=opt.sample, top_k=opt.top_k, temperature=opt.temperature, top_p=getattr(opt, "top_p", None),
+                                  noise=self.sample_noise,
                                   host_noise=host_noise, trace=self.trace, use_graph=getattr(opt, "use_graph", True),
                                   state_code=state_code if use_state else None, state_sampler=state_sampler,
                                   lbl_idx=vid_lbl if getattr(opt, "cat", False) else None)

@@ -798,14 +798,48 @@ def attention(q, kcache, vcache, pos0, pos_dev=None):
     return out
 
 
-def sample_topk(logits, top_k, temperature, noise=None, out=None, philox=None):
+def check_top_p(top_p):
+    """The nucleus threshold of a sampler: None for "off" (None and 1.0), a float inside (0, 1) otherwise.  ValueError for the rest."""
+    if top_p is None:
+        return None
+    p = float(top_p)
+    if p == 1.0:
+        return None
+    if not 0.0 < p < 1.0:   # (a NaN fails both comparisons)
+        raise ValueError(f"top_p must be None, 1.0 (both: off) or inside (0, 1), got {top_p!r}")
+    return p
+
+
+def sample_topp_max_vocab():
+    """The largest vocabulary the nucleus form of the pick takes (`ccvs_sample_topp_max_vocab`; host only)."""
+    return int(_lib.load().ccvs_sample_topp_max_vocab())
+
+
+def sample_topk(logits, top_k, temperature, noise=None, out=None, philox=None, *, top_p=None):
     """logits [B,V] -> int64 [B]; noise None = greedy, else argmax(p / noise).  philox = (key0, key1, row0, step, call):
-    draw the Exp(1) noise in the kernel, keyed by the global clip index row0 + b (ccvs_sample_topk_philox)."""
+    draw the Exp(1) noise in the kernel, keyed by the global clip index row0 + b (ccvs_sample_topk_philox).
+    top_p inside (0, 1): nucleus sampling after the top-k mask (`ccvs_sample_topp` / `ccvs_sample_topp_philox`, include/ccvs_hip_sampling.h);
+    None or 1.0: off -- the calls above, as before."""
+    top_p = check_top_p(top_p)
     _need_gpu(logits, noise, out)
     b, v = logits.shape
     assert logits.stride(1) == 1
     if out is None:
         out = torch.empty(b, dtype=torch.int64, device=logits.device)
+    if top_p is not None:
+        L = _lib.load()
+        k = 0 if top_k is None else int(top_k)
+        if philox is not None:
+            assert noise is None
+            k0, k1, row0, step, call = (int(t) & 0xffffffff for t in philox)
+            _lib.check(L.ccvs_sample_topp_philox(_p(logits), logits.stride(0), _p(out), out.stride(0), b, v, k, float(temperature), top_p,
+                                                 k0, k1, row0, step, call, _stream()), "ccvs_sample_topp_philox")
+            return out
+        if noise is not None:
+            assert noise.shape == (b, v) and noise.is_contiguous()
+        _lib.check(L.ccvs_sample_topp(_p(logits), logits.stride(0), _p(noise), _p(out), out.stride(0), b, v, k, float(temperature), top_p,
+                                      _stream()), "ccvs_sample_topp")
+        return out
     if philox is not None:
         assert noise is None
         k0, k1, row0, step, call = (int(t) & 0xffffffff for t in philox)
@@ -843,8 +877,9 @@ class GptDecodeStep:
 
     def __init__(self, layers, B, C, H, Tmax, ln_eps, tok_emb, pos_table, pos_off, head, tok, codes, widx, length,
                  x, q, att, h, logits, noise, top_k, temperature, state, rng=False, groups=1, noise_stream=None, persistent=False,
-                 tiled=None):
-        """tiled: None, or ([{qkv_w, proj_w, fc_w, fc2_w} per layer], head_w) = `tile_weight` of the matrices in `layers` / `head`: the
+                 tiled=None, top_p=None):
+        """top_p: nucleus sampling in the step's pick (`ccvs_gpt_decode.top_p`; None or 1.0: off).
+        tiled: None, or ([{qkv_w, proj_w, fc_w, fc2_w} per layer], head_w) = `tile_weight` of the matrices in `layers` / `head`: the
         step then reads those (`ccvs_gpt_decode.w_tiled`); the row-major ones still give the shapes."""
         hw, hb, hs = head
         keep = [tok_emb, pos_table, hw, hb, hs, tok, codes, widx, length, x, q, att, h, logits, noise, state, noise_stream]
@@ -893,6 +928,7 @@ class GptDecodeStep:
         d.rng = 1 if (rng and noise is None and noise_stream is None) else 0
         d.noise_stream = _p(noise_stream)
         d.top_k, d.temperature = 0 if top_k is None else int(top_k), float(temperature)
+        d.top_p = check_top_p(top_p) or 0.0
         d.workspace, d.state = _p(self.ws), _p(state)
         d.groups = groups
         self.desc, self._arr, self._keep = d, arr, keep

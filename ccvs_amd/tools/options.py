@@ -160,6 +160,7 @@ class Options:
         p.add_argument("--x_head_to_n", type=int, default=0)
         p.add_argument("--x_temperature", type=float, default=1.0)
         p.add_argument("--x_top_k", type=int, default=None)
+        p.add_argument("--x_top_p", type=float, default=None, help="(ccvs_amd) nucleus sampling after top-k: inside (0, 1); None / 1.0: off")
         p.add_argument("--x_beam_size", type=int, default=None)
         p.add_argument("--x_emb_mode", type=str, default=None)
         p.add_argument("--x_z_shape", type=int, nargs="+", default=None)
@@ -167,6 +168,7 @@ class Options:
         p.add_argument("--x_state_size", type=int, default=None)
         p.add_argument("--x_temperature_state", type=float, default=1.0)
         p.add_argument("--x_top_k_state", type=int, default=None)
+        p.add_argument("--x_top_p_state", type=float, default=None, help="(ccvs_amd) --x_top_p of the ancillary token stream")
         p.add_argument("--x_blur_sigma", type=int, default=10)
         p.add_argument("--x_sample_noise", type=str, default="host", help="(ccvs_amd) 'host': reference-reproducible noise, 'device'")
         # ---- s_ / a_: ancillary token streams (declared for parity of the Namespace split)

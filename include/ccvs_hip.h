@@ -388,6 +388,12 @@ typedef struct ccvs_gpt_decode {
     /* Additive (ABI stays 6; 0 = as before).  1: the `*_w` pointers of `layers` and `head_w` hold the TILED layout of the
      * same matrices (ccvs_hip_gemm.h, included below: the layout, and an entry point that runs ONE decode GEMM on it); both forms of the step then load whole 1-KB blocks.  Tokens and every buffer stay bit-identical. */
     int32_t w_tiled;
+    /* Additive (ABI stays 6; 0 = as before).  Inside (0, 1): nucleus sampling after the top-k mask -- the pick keeps the smallest set of
+     * the most likely tokens whose mass reaches top_p (ccvs_hip_sampling.h, included below: the definition, the form's own vocabulary
+     * cap, and entry points for a single pick).  0 or 1: off.  Anything else is refused.  All three forms of the step take it (eager
+     * launches, graph replay, persistent = 1: ccvs_gpt_decode_prepare carries it into the step program, so a descriptor whose top_p
+     * changes is prepared again). */
+    float top_p;
 } ccvs_gpt_decode;
 int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream);
 /* Synchronises `stream` and returns 0 unless a grid barrier of a persistent decode step launched with this workspace gave up (a
@@ -503,6 +509,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_output_lossless_lz.h"
 /* the way back from it (zlib streams -> bytes; the streams of 8-bit RGB PNG images -> uint8 frames), additive to ABI version 6, likewise */
 #include "ccvs_hip_decode_lossless.h"
+/* nucleus (top-p) sampling in the token pick, additive to ABI version 6, likewise */
+#include "ccvs_hip_sampling.h"
 
 #ifdef __cplusplus
 }
