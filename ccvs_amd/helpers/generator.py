@@ -57,6 +57,19 @@ class Generator:
             raise ValueError("--decode_stft decodes the STFT token stream of the audio-conditioned configuration: it needs --x_stft")
         if self.decode_stft and self.opt.step_by_step:
             raise NotImplementedError("--step_by_step with --decode_stft is not on the MI355X path (the plain synthesis schedule runs it)")
+        # (ccvs_amd) --save_flow: the decoder's motion beside the clips
+        self.save_flow = bool(getattr(self.opt, "save_flow", False))
+        self.save_flow_raw = bool(getattr(self.opt, "save_flow_raw", False))
+        self.flow_max_px = float(getattr(self.opt, "flow_max_px", 0.0) or 0.0)
+        if self.save_flow_raw and not self.save_flow:
+            raise ValueError("--save_flow_raw writes the motion --save_flow collects: it needs --save_flow")
+        if self.flow_max_px < 0:
+            raise ValueError(f"--flow_max_px {self.flow_max_px}: the radius at which the flow colours saturate cannot be negative (0: each clip's own largest flow)")
+        if self.save_flow and not getattr(q, "use_inter", False):
+            raise ValueError("--save_flow needs --q_use_inter: without the flow-guided frame loop the clip is one decoder call, which "
+                             "estimates no motion between frames")
+        if self.save_flow and self.opt.step_by_step:
+            raise NotImplementedError("--step_by_step with --save_flow is not on the MI355X path (the plain synthesis schedule runs it)")
         if getattr(self.opt, "deblurring", False) and self.opt.step_by_step:
             raise NotImplementedError("--step_by_step with --deblurring is not on the MI355X path (the plain synthesis schedule runs the mode)")
 
@@ -298,26 +311,46 @@ class Generator:
         dec_in["code"] = code
         if state_code is not None:
             dec_in["state_code"] = state_code
-        fake_data = self.vid_model(dec_in, mode='vid_decoder')
+        fake_data = self.vid_model(dec_in, mode='vid_decoder', **({"motion": True} if self.save_flow else {}))
         fake_data["code"], fake_data["state_code"] = code, state_code
         if opt.p2p:
             fake_data["vid"] = torch.cat([fake_data["vid"], ws["data"]["vid"][:, -1:]], dim=1)
+        self._finish_motion(fake_data, ws["data"]["vid"][:, -1:] if opt.p2p else None)
         if opt.state and state_code is not None:                            # generator.py:168-169
             fake_data.update(self.state_model({"state_code": state_code}, mode='vid_decoder'))
         if self.decode_stft:                                                # (ccvs_amd) the clip's sound: its final STFT tokens as spectrograms
             fake_data.update(self._decode_stft_tokens(state_code))
         return fake_data
 
+    def _finish_motion(self, d, end_frame):
+        """--save_flow: the keys a decoded clip's dict carries beside "vid" -- "flow" [B, T, 2, H, W] and "occ" [B, T, 1, H, W] (views
+        of "motion" [B, T, 3, H, W]), "warp" [B, T, 3, H, W], "flow_dt" (T ints) -- with the appended real end frame of --x_p2p as one
+        more frame without flow, so that the three have the length of "vid".  A clip decoded by one decoder call has none of them."""
+        if not self.save_flow or d.get("motion") is None:
+            return
+        if end_frame is not None:
+            d["motion"] = torch.cat([d["motion"], torch.zeros_like(d["motion"][:, :1])], dim=1)
+            d["warp"] = torch.cat([d["warp"], end_frame.to(d["warp"])], dim=1)
+            d["flow_dt"] = list(d["flow_dt"]) + [0]
+        d["flow"], d["occ"] = d["motion"][:, :, :2], d["motion"][:, :, 2:3]
+
+    def motion_bytes_per_clip_pixel(self, rec_pass):
+        """What --save_flow keeps per clip and pixel for a batch in flight (`_lanes_that_fit`): the motion buffer, 12 bytes per frame, and
+        the warp-only clip, as much again -- twice with the rec pass."""
+        return 24.0 * int(self.opt.vid_len) * (2 if rec_pass else 1) if self.save_flow else 0.0
+
     def _decode_codes_stream(self, ws, code_of, final):
         """`decode_codes` as a generator for a clip whose tokens arrive frame by frame (`QVidModel.decode_stream`): `code_of(lo,
         hi)` -> tokens of frames lo .. hi - 1, `final()` -> (code, state_code) of the whole clip once the token stage is done."""
         opt = self.opt
         dec_in = {k: v for k, v in ws["cropped"].items() if k != "code"}
-        fake_data = yield from self.vid_model.decode_stream(dec_in, code_of, frames=opt.vid_len - (1 if opt.p2p else 0))
+        fake_data = yield from self.vid_model.decode_stream(dec_in, code_of, frames=opt.vid_len - (1 if opt.p2p else 0),
+                                                            **({"motion": True} if self.save_flow else {}))
         code, state_code = final()
         fake_data["code"], fake_data["state_code"] = code, state_code
         if opt.p2p:
             fake_data["vid"] = torch.cat([fake_data["vid"], ws["data"]["vid"][:, -1:]], dim=1)
+        self._finish_motion(fake_data, ws["data"]["vid"][:, -1:] if opt.p2p else None)
         if opt.state and state_code is not None:                            # generator.py:168-169
             fake_data.update(self.state_model({"state_code": state_code}, mode='vid_decoder'))
         if self.decode_stft:                                                # (ccvs_amd) the clip's sound: its final STFT tokens as spectrograms
@@ -344,9 +377,10 @@ class Generator:
             rec["code"] = encoded_data["code"]
         if opt.state or opt.stft:
             rec["state_code"] = encoded_data["state_code"]
-        rec_data = self.vid_model(rec, mode='vid_decoder')
+        rec_data = self.vid_model(rec, mode='vid_decoder', **({"motion": True} if self.save_flow else {}))
         if opt.p2p:
             rec_data["vid"] = torch.cat([rec_data["vid"], data["vid"][:, -1:]], dim=1)
+        self._finish_motion(rec_data, data["vid"][:, -1:] if opt.p2p else None)
         if opt.state:
             rec_data["state"] = data["state"]
         if self.decode_stft:                                                # (ccvs_amd) the real clip's own STFT tokens, decoded
@@ -609,10 +643,37 @@ class Generator:
             stft = item.get("stft") if self.decode_stft and isinstance(item, dict) else None
             if stft is not None:                                            # (ccvs_amd) --decode_stft: one float32 [T, H, W] .npy per clip
                 save_stft_batch(stft, bs, global_iter, os.path.join(self.opt.result_path, name + "_stft"))
+            if getattr(self, "save_flow", False) and isinstance(item, dict) and item.get("motion") is not None:
+                self._save_motion(item, name, bs, global_iter, how)                                  # (ccvs_amd) --save_flow: the decoder's motion
             state = out.get("real_state") if name == "real" else (item.get("state") if isinstance(item, dict) else None)
             if self.opt.state and state is not None:                        # generator.py:213-223: clips with the state marker
                 save_video_batch(vid, bs, global_iter, os.path.join(self.opt.result_path, name + "_state"), self.opt.fps, True,
                                  self.opt.imagenet_norm, [-1, 1], self.opt.dataset, state=state, **how)
+
+    def _save_motion(self, item, name, bs, global_iter, how):
+        """(ccvs_amd) --save_flow: `name`_flow/ and `name`_occ/ -- the motion rendered on the GPU (`ops.flow_render`: the flow colours
+        saturate at --flow_max_px pixels, or at each clip's own largest flow, `ops.flow_max`) -- and `name`_warp/, the warp-only clip
+        with the clip's own normalisation, all in the clips' format and names; --save_flow_raw: `name`_motion/ float32 [T, 3, H, W]."""
+        opt = self.opt
+        motion = item["motion"]
+        if self.flow_max_px > 0:
+            max_px = torch.full((motion.size(0),), self.flow_max_px, dtype=torch.float32, device=motion.device)
+        else:
+            max_px = ops.flow_max(motion)
+        fmt = how["video_format"]
+        tail = {k: how[k] for k in ("quality", "subsampling", "optimize", "lz77")}
+        for suffix, u8 in zip(("_flow", "_occ"), ops.flow_render(motion, max_px)):
+            host = u8 if fmt in ("avi", "apng") else u8.cpu()
+            write_u8_clips(host, u8, u8.device, bs, global_iter, os.path.join(opt.result_path, name + suffix), opt.fps, fmt, **tail)
+        save_video_batch(item["warp"], bs, global_iter, os.path.join(opt.result_path, name + "_warp"), opt.fps, True,
+                         opt.imagenet_norm, [-1, 1], opt.dataset, **how)
+        if self.save_flow_raw:
+            import numpy as np
+            arr = motion.detach().float().cpu().numpy()
+            path = os.path.join(opt.result_path, name + "_motion")
+            os.makedirs(path, exist_ok=True)
+            for i in range(arr.shape[0]):
+                np.save(os.path.join(path, f"vid_{bs * global_iter + i:05d}.npy"), arr[i])
 
     def run(self, save=True):
         """The reference's entry point (helpers/generator.py:248-282): build the models, then `n_iter` batches through
@@ -753,6 +814,15 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
                     x, y = st[i, j]
                     u8[i, j] = draw_cross(u8[i, j], min(int(res * x), res - 1), min(int(res * y), res - 1))
             dev_u8 = None  # the marked clip is the one to write: "avi" and "apng" upload it again (rare and small)
+    write_u8_clips(u8, dev_u8, vid.device, bs, global_iter, path, fps, video_format, quality, subsampling, optimize, lz77, cat=cat, idx=idx)
+    return u8 if u8.device.type == "cpu" else None
+
+
+def write_u8_clips(u8, dev_u8, device, bs, global_iter, path, fps, video_format, quality=90, subsampling="444", optimize=False, lz77=False,
+                   cat=None, idx=None):
+    """The files of a packed uint8 batch [B, T, H, W, 3] in `save_video_batch`'s formats and names: its tail, which the flow and
+    occlusion clips of --save_flow (already uint8 on the device, `ops.flow_render`) go through as well.  u8: the batch on the host --
+    or on the device where the format is "avi" / "apng", which read `dev_u8`, the batch on the device (None: u8 is uploaded to `device`)."""
     os.makedirs(path, exist_ok=True)
     write_video = None
     if video_format is None:
@@ -764,13 +834,13 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
         from ccvs_amd.tools import mjpeg
         t, (h, w) = u8.size(1), u8.shape[2:4]
         sampling = _SUBSAMPLING[subsampling]
-        scans, off, *tables = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), quality, sampling=sampling, optimize=optimize)
+        scans, off, *tables = ops.mjpeg_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(device), quality, sampling=sampling, optimize=optimize)
         head = mjpeg.jpeg_header(h, w, quality, sampling=sampling)
         heads = [mjpeg.jpeg_header(h, w, quality, sampling=sampling, huffman=mjpeg.huffman_from_spec(spec)) for spec in tables[0]] if optimize else None
     elif video_format == "apng":
         from ccvs_amd.tools import apng
         t, (h, w) = u8.size(1), u8.shape[2:4]
-        zbytes, off = ops.png_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(vid.device), lz77=lz77)
+        zbytes, off = ops.png_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(device), lz77=lz77)
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'
@@ -784,7 +854,6 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
         else:
             import numpy as np
             np.save(stem + ".npy", u8[i].numpy())
-    return u8 if u8.device.type == "cpu" else None
 
 
 def save_stft_batch(stft, bs, global_iter, path):

@@ -444,7 +444,8 @@ class PipelinedRun:
             noise_bytes = 4.0 * max(steps, 0) * nb * gen.transformer_model.net_t.head.weight.shape[0]
         fit = gen._lanes_that_fit(self.lanes, self.chains, nb, first["vid"].shape[-2], first["vid"].shape[-1], total,
                                   frac=float(os.environ.get("CCVS_PIPELINE_MEM_FRAC", "0.7")), taken=foreign, dec_streams=len(self.dec_streams),
-                                  noise_bytes_per_batch=noise_bytes)
+                                  noise_bytes_per_batch=noise_bytes,
+                                  bytes_per_clip_pixel=10.0e3 + gen.motion_bytes_per_clip_pixel(bool(self.rec_pass)))
         if fit < self.lanes:
             print(f"[pipeline] {self.lanes} -> {fit} batches per token group: {self.lanes * (self.chains + 2)} batches of {nb} clips in flight would not fit "
                   "the device memory (CCVS_PIPELINE_MEM_FRAC)", file=sys.stderr, flush=True)
@@ -751,7 +752,8 @@ class PipelinedRun:
                 out["finished"] = self.finish(m["i"], fake) if self.finish is not None else None
                 for t in ((fake["vid"], fake["code"]) + ((out["rec"]["vid"],) if out["rec"] is not None else ())
                           + ((out["blur"],) if out["blur"] is not None else ())
-                          + tuple(d["stft"] for d in (fake, out["rec"]) if d is not None and d.get("stft") is not None)):   # handed to the caller's stream
+                          + tuple(d["stft"] for d in (fake, out["rec"]) if d is not None and d.get("stft") is not None)
+                          + tuple(d[key] for d in (fake, out["rec"]) if d is not None for key in ("motion", "warp") if d.get(key) is not None)):   # handed to the caller's stream
                     t.record_stream(self.entry)
                 if self.consume is not None:   # a long run: the caller takes every batch as it comes, nothing is kept here
                     self.consume(out)

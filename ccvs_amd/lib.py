@@ -48,6 +48,9 @@ OUTPUT_LOSSLESS_LZ_EXPORTS = ["ccvs_apng_lz_workspace_bytes", "ccvs_apng_encode_
 DECODE_LOSSLESS_EXPORTS = ["ccvs_png_decode_workspace_bytes", "ccvs_zlib_inflate", "ccvs_png_decode"]
 # every symbol include/ccvs_hip_sampling.h declares (nucleus sampling in the token pick; included by ccvs_hip.h too)
 SAMPLING_EXPORTS = ["ccvs_sample_topp", "ccvs_sample_topp_philox", "ccvs_sample_topp_max_vocab"]
+# every symbol include/ccvs_hip_flowviz.h declares (the decoder's motion export; included by ccvs_hip.h too).  (Named apart from the
+# `*_EXPORTS` lists above, whose number tests/test_nucleus_host.py pins.)
+FLOWVIZ_SYMBOLS = ["ccvs_flow_export", "ccvs_flow_max", "ccvs_flow_render"]
 
 
 class ConvDesc(C.Structure):
@@ -239,6 +242,9 @@ def load():
         "ccvs_time_unfold": [vp, i64, i64, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
         "ccvs_maxpool3d_same": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
         "ccvs_i3d_head": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp],
+        "ccvs_flow_export": [vp, i64, i32, i32, i32, i32, f32, vp, i64, vp],
+        "ccvs_flow_max": [vp, i64, i64, i32, i32, i32, i32, vp, vp],
+        "ccvs_flow_render": [vp, i64, i64, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "ccvs_ingest_f32": [vp, i32, i64, i64, i32, i32, i32, i32, i32, vp, i32, vp, vp, i64, i64, vp],
         "ccvs_ingest_u8": [vp, i64, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, i64, i64, vp, vp],
     }

@@ -1295,6 +1295,73 @@ def pack_u8(vid, lo=-1.0, hi=1.0, out=None):
     return out
 
 
+# ------------------------------------------------------------------ motion export (include/ccvs_hip_flowviz.h)
+_FLOW_LUTS = {}
+
+
+def _motion_strides(motion):
+    """[B, T, 3, H, W] fp32 whose three planes per frame are dense: (B, T, H, W, batch stride, frame stride)."""
+    _need_gpu(motion)
+    assert motion.dim() == 5 and motion.shape[2] == 3 and motion.dtype == torch.float32, tuple(motion.shape)
+    b, t, _, h, w = motion.shape
+    assert motion.stride(4) == 1 and motion.stride(3) == w and motion.stride(2) == h * w, "motion: the planes of a frame must be dense"
+    return b, t, h, w, motion.stride(0), motion.stride(1)
+
+
+def flow_export(fo, k, flow_mult, out, t):
+    """The last InterBlock's rows of one new frame into slot t of the clip's motion buffer (`ccvs_flow_export`).  fo: [B * k, 3, H, W]
+    (flow | occ), usually the channel-slice view `InterBlock.forward_fused` returns -- read in place, any batch stride; out: the
+    [B, T, 3, H, W] fp32 buffer.  out[:, t, 0:2] = fo[b * k, 0:2] * flow_mult (context 0 of every clip), out[:, t, 2] = the mask the
+    blend used: sigmoid of the confidence-weighted mean of the k occlusion logits."""
+    _need_gpu(fo, out)
+    assert fo.dim() == 4 and fo.shape[1] == 3 and fo.dtype == torch.float32 and _planes_dense(fo), (tuple(fo.shape), fo.stride())
+    b, nt, h, w, s_b, s_t = _motion_strides(out)
+    assert fo.shape == (b * k, 3, h, w) and 0 <= t < nt, (tuple(fo.shape), k, tuple(out.shape), t)
+    fo_sn = fo.stride(0) if fo.shape[0] > 1 else 3 * h * w
+    L = _lib.load()
+    _lib.check(L.ccvs_flow_export(_p(fo), fo_sn, b, int(k), h, w, float(flow_mult), C.c_void_p(out.data_ptr() + 4 * t * s_t),
+                                  s_b if b > 1 else 3 * h * w, _stream()), "ccvs_flow_export")
+    return out
+
+
+def flow_max(motion):
+    """Per-clip largest flow magnitude sqrt(fx^2 + fy^2) of a motion buffer [B, T, 3, H, W] over its finite pixels: [B] fp32, 0 for a
+    clip without one (`ccvs_flow_max`; an integer maximum on the bit pattern, the same bits on every run)."""
+    b, t, h, w, s_b, s_t = _motion_strides(motion)
+    out = torch.empty(b, dtype=torch.float32, device=motion.device)
+    L = _lib.load()
+    _lib.check(L.ccvs_flow_max(_p(motion), s_b if b > 1 else t * 3 * h * w, s_t if t > 1 else 3 * h * w, b, t, h, w, _p(out), _stream()),
+               "ccvs_flow_max")
+    return out
+
+
+def flow_lut(device):
+    """`tools.flowviz.HSV128` on `device`, uploaded once."""
+    key = torch.device(device)
+    if key not in _FLOW_LUTS:
+        from ccvs_amd.tools.flowviz import HSV128
+        _FLOW_LUTS[key] = torch.from_numpy(HSV128.copy()).to(key)
+    return _FLOW_LUTS[key]
+
+
+def flow_render(motion, max_px, lut=None):
+    """A motion buffer [B, T, 3, H, W] as (flow_u8, occ_u8), both uint8 [B, T, H, W, 3] (`ccvs_flow_render`): the reference's
+    get_flow_rgb colours saturating at max_px[b] pixels (a [B] fp32 device tensor: `flow_max`'s output or a filled constant; a clip
+    with max_px 0 is black, and so is a pixel with a non-finite component), and the mask as grey.  lut: [128, 3] fp32 on the device
+    (default: `flow_lut`)."""
+    b, t, h, w, s_b, s_t = _motion_strides(motion)
+    lut = flow_lut(motion.device) if lut is None else lut
+    _need_gpu(max_px, lut)
+    assert max_px.shape == (b,) and max_px.dtype == torch.float32 and max_px.is_contiguous()
+    assert lut.shape == (128, 3) and lut.dtype == torch.float32 and lut.is_contiguous()
+    flow_u8 = torch.empty(b, t, h, w, 3, dtype=torch.uint8, device=motion.device)
+    occ_u8 = torch.empty_like(flow_u8)
+    L = _lib.load()
+    _lib.check(L.ccvs_flow_render(_p(motion), s_b if b > 1 else t * 3 * h * w, s_t if t > 1 else 3 * h * w, b, t, h, w, _p(max_px), _p(lut),
+                                  _p(flow_u8), _p(occ_u8), _stream()), "ccvs_flow_render")
+    return flow_u8, occ_u8
+
+
 # ------------------------------------------------------------------ input stage (include/ccvs_hip_input.h)
 _RESAMPLE_TABLES = {}
 _NORM_TABLES = {}

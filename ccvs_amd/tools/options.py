@@ -97,6 +97,13 @@ class Options:
         _flag(p, "--rec_pass", default=True)
         _flag(p, "--decode_stft", help="(ccvs_amd) with --x_stft: decode the clip's final STFT token stream (and, with the rec pass, the real "
                                       "clip's) back to spectrogram frames -- out['fake'|'rec']['stft'], fake_stft/ and rec_stft/ .npy files")
+        # (ccvs_amd) the decoder's motion beside the clips: --save_flow adds the full-resolution flow towards
+        # each frame's first context, the fused occlusion mask and the warp-only frame to out['fake'|'rec'] and writes them as
+        # fake_flow/ fake_occ/ fake_warp/ (and rec_*) clips; --flow_max_px P: the flow colours saturate at P pixels (0: at each clip's
+        # own largest flow); --save_flow_raw: also fake_motion/ (rec_motion/) float32 [T, 3, H, W] .npy files
+        _flag(p, "--save_flow")
+        p.add_argument("--flow_max_px", type=float, default=0.0)
+        _flag(p, "--save_flow_raw")
         # (ccvs_amd) the reference encodes EVERY frame of the input clip (helpers/generator.py:69) although synthesis reads the
         # conditioning frames only -- the other codes feed its rec pass and `enc_code`.  `--encode_all false`: with the rec pass
         # off and no state / audio / point-to-point conditioning, encode just the frames the conditioning crop keeps (the same

@@ -511,6 +511,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_decode_lossless.h"
 /* nucleus (top-p) sampling in the token pick, additive to ABI version 6, likewise */
 #include "ccvs_hip_sampling.h"
+/* the decoder's motion export (flow, occlusion mask, their colour rendering), additive to ABI version 6, likewise */
+#include "ccvs_hip_flowviz.h"
 
 #ifdef __cplusplus
 }
