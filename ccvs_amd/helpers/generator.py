@@ -663,7 +663,7 @@ class Generator:
         fmt = how["video_format"]
         tail = {k: how[k] for k in ("quality", "subsampling", "optimize", "lz77")}
         for suffix, u8 in zip(("_flow", "_occ"), ops.flow_render(motion, max_px)):
-            host = u8 if fmt in ("avi", "apng") else u8.cpu()
+            host = u8 if fmt in ("avi", "apng", "gif") else u8.cpu()
             write_u8_clips(host, u8, u8.device, bs, global_iter, os.path.join(opt.result_path, name + suffix), opt.fps, fmt, **tail)
         save_video_batch(item["warp"], bs, global_iter, os.path.join(opt.result_path, name + "_warp"), opt.fps, True,
                          opt.imagenet_norm, [-1, 1], opt.dataset, **how)
@@ -788,12 +788,17 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
               Browsers, ffmpeg and Pillow open the files; `quality`, `subsampling` and `optimize` are not looked at.  lz77: the deflate
               blocks may hold LZ77 matches, kept per block only where that is smaller: the same pixels, no file
               larger, a slower encode; the other formats do not look at it.
-    Returns the uint8 clip on the host; `return_clip=False` lets the "avi" and "apng" forms skip that copy where no state marker needs
+      "gif"   for showing: one animated GIF `vid_XXXXX.gif` per clip (`ccvs_amd.tools.gif`), looping, in 256 colours chosen from that
+              clip's own pixels: histogram, median cut, index mapping and LZW coding run on the device (`ops.gif_encode`, DESIGN.md
+              section 4.27) and the palettes and the coded bytes are what is copied out.  The frames are quantised (clips of at most 256
+              colours in distinct 5-bit bins, as the flow and occlusion clips of --save_flow mostly are, are stored exactly), so the
+              metrics and FVD commands do not read these files; `quality`, `subsampling`, `optimize` and `lz77` are not looked at.
+    Returns the uint8 clip on the host; `return_clip=False` lets the "avi", "apng" and "gif" forms skip that copy where no state marker needs
     it (then only the compressed bytes cross to the host, and None is returned)."""
     if is_layout:
         raise NotImplementedError("layout colour maps are not on the MI355X path (SURVEY 8f)")
-    if video_format not in (None, "npy", "avi", "apng"):
-        raise ValueError(f"save_video_batch: video_format {video_format!r} is none of None, 'npy', 'avi', 'apng'")
+    if video_format not in (None, "npy", "avi", "apng", "gif"):
+        raise ValueError(f"save_video_batch: video_format {video_format!r} is none of None, 'npy', 'avi', 'apng', 'gif'")
     if subsampling not in _SUBSAMPLING:
         raise ValueError(f"save_video_batch: subsampling {subsampling!r} is none of '444', '422', '420'")
     if normalize and imagenet_norm:
@@ -803,7 +808,7 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
     else:
         u8 = (vid.permute(0, 1, 3, 4, 2) * 255).to(torch.uint8)
     dev_u8 = u8
-    if return_clip or video_format not in ("avi", "apng") or state is not None:
+    if return_clip or video_format not in ("avi", "apng", "gif") or state is not None:
         u8 = u8.cpu()
     if state is not None:  # generator.py:311-323: mark the (x, y) state on every frame
         res = {"bair": 64, "bairhd": 256}.get(dataset)
@@ -813,7 +818,7 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
                 for j in range(u8.size(1)):
                     x, y = st[i, j]
                     u8[i, j] = draw_cross(u8[i, j], min(int(res * x), res - 1), min(int(res * y), res - 1))
-            dev_u8 = None  # the marked clip is the one to write: "avi" and "apng" upload it again (rare and small)
+            dev_u8 = None  # the marked clip is the one to write: "avi", "apng" and "gif" upload it again (rare and small)
     write_u8_clips(u8, dev_u8, vid.device, bs, global_iter, path, fps, video_format, quality, subsampling, optimize, lz77, cat=cat, idx=idx)
     return u8 if u8.device.type == "cpu" else None
 
@@ -822,7 +827,10 @@ def write_u8_clips(u8, dev_u8, device, bs, global_iter, path, fps, video_format,
                    cat=None, idx=None):
     """The files of a packed uint8 batch [B, T, H, W, 3] in `save_video_batch`'s formats and names: its tail, which the flow and
     occlusion clips of --save_flow (already uint8 on the device, `ops.flow_render`) go through as well.  u8: the batch on the host --
-    or on the device where the format is "avi" / "apng", which read `dev_u8`, the batch on the device (None: u8 is uploaded to `device`)."""
+    or on the device where the format is "avi" / "apng" / "gif", which read `dev_u8`, the batch on the device (None: u8 is uploaded to
+    `device`)."""
+    if video_format not in (None, "npy", "avi", "apng", "gif"):
+        raise ValueError(f"write_u8_clips: video_format {video_format!r} is none of None, 'npy', 'avi', 'apng', 'gif'")
     os.makedirs(path, exist_ok=True)
     write_video = None
     if video_format is None:
@@ -841,6 +849,10 @@ def write_u8_clips(u8, dev_u8, device, bs, global_iter, path, fps, video_format,
         from ccvs_amd.tools import apng
         t, (h, w) = u8.size(1), u8.shape[2:4]
         zbytes, off = ops.png_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(device), lz77=lz77)
+    elif video_format == "gif":
+        from ccvs_amd.tools import gif
+        t, (h, w) = u8.size(1), u8.shape[2:4]
+        gbytes, off, palettes = ops.gif_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(device))
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'
@@ -849,6 +861,8 @@ def write_u8_clips(u8, dev_u8, device, bs, global_iter, path, fps, video_format,
             mjpeg.write_avi(stem + ".avi", [(heads[k] if optimize else head) + scans[off[k]:off[k + 1]] + mjpeg.EOI for k in range(i * t, (i + 1) * t)], fps, h, w)
         elif video_format == "apng":
             apng.write_apng(stem + ".png", [zbytes[off[k]:off[k + 1]] for k in range(i * t, (i + 1) * t)], fps, h, w)
+        elif video_format == "gif":
+            gif.write_gif(stem + ".gif", [gbytes[off[k]:off[k + 1]] for k in range(i * t, (i + 1) * t)], palettes[i], fps, h, w)
         elif write_video is not None:
             write_video(stem + ".mp4", u8[i], fps)
         else:

@@ -51,6 +51,9 @@ SAMPLING_EXPORTS = ["ccvs_sample_topp", "ccvs_sample_topp_philox", "ccvs_sample_
 # every symbol include/ccvs_hip_flowviz.h declares (the decoder's motion export; included by ccvs_hip.h too).  (Named apart from the
 # `*_EXPORTS` lists above, whose number tests/test_nucleus_host.py pins.)
 FLOWVIZ_SYMBOLS = ["ccvs_flow_export", "ccvs_flow_max", "ccvs_flow_render"]
+# every symbol include/ccvs_hip_output_gif.h declares (the GIF output stage: a palette per clip, LZW-coded frames; included by ccvs_hip.h
+# too; named apart from the `*_EXPORTS` lists for the same reason)
+GIF_SYMBOLS = ["ccvs_gif_workspace_bytes", "ccvs_gif_stream_bound", "ccvs_gif_palette", "ccvs_gif_encode"]
 
 
 class ConvDesc(C.Structure):
@@ -161,6 +164,10 @@ def load():
     lib.ccvs_apng_stream_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_apng_lz_workspace_bytes.restype = C.c_size_t
     lib.ccvs_apng_lz_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ccvs_gif_workspace_bytes.restype = C.c_size_t
+    lib.ccvs_gif_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ccvs_gif_stream_bound.restype = C.c_long
+    lib.ccvs_gif_stream_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_png_decode_workspace_bytes.restype = C.c_size_t
     lib.ccvs_png_decode_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.ccvs_lpips_layer_workspace_bytes.restype = C.c_int64
@@ -232,6 +239,8 @@ def load():
         "ccvs_mjpeg_decode": [vp, C.c_long, vp, vp, C.c_long, vp, i32, vp, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_apng_encode": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_apng_encode_lz": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
+        "ccvs_gif_palette": [vp, C.c_long, C.c_long, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+        "ccvs_gif_encode": [vp, C.c_long, C.c_long, i32, i32, i32, i32, i32, vp, vp, C.c_long, vp, vp, vp],
         "ccvs_zlib_inflate": [vp, C.c_long, vp, vp, i32, vp, C.c_long, vp, vp],
         "ccvs_png_decode": [vp, C.c_long, vp, vp, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_lpips_prep": [vp, vp, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), vp],

@@ -1690,6 +1690,85 @@ def png_encode_to_host(u8, filter=-1, band_rows=0, lz77=False):
     return stream[:off[-1]].cpu().numpy().tobytes(), off
 
 
+# ------------------------------------------------------------------ GIF output stage (include/ccvs_hip_output_gif.h)
+def _gif_clips(who, u8):
+    """The clips [B, T, H, W, 3] (or one clip [T, H, W, 3]) as the C calls take them: (clips, b, t, h, w, clip stride, frame stride)."""
+    assert u8.dtype == torch.uint8 and u8.dim() in (4, 5) and u8.shape[-1] == 3, (who, u8.dtype, u8.shape)
+    clips = u8.unsqueeze(0) if u8.dim() == 4 else u8
+    b, t, h, w = (int(v) for v in clips.shape[:4])
+    frame = 3 * w * h
+    if clips.stride()[-3:] != (3 * w, 3, 1):
+        clips = clips.contiguous()
+    fs = clips.stride(1) if t > 1 else frame
+    cs = clips.stride(0) if b > 1 else (t - 1) * fs + frame
+    if fs < frame or cs < (t - 1) * fs + frame:       # (an expanded or interleaved axis)
+        clips = clips.contiguous()
+        fs, cs = frame, t * frame
+    return clips, b, t, h, w, cs, fs
+
+
+def _gif_palette(L, clips, b, t, h, w, cs, fs, work):
+    dev = clips.device
+    palette = torch.empty((b, 256, 3), dtype=torch.uint8, device=dev)
+    table = torch.empty((b, 32768), dtype=torch.uint8, device=dev)
+    used = torch.empty(b, dtype=torch.int32, device=dev)
+    _lib.check(L.ccvs_gif_palette(_p(clips), cs, fs, b, t, h, w, _p(palette), _p(table), _p(used), _p(work), _stream()), "ccvs_gif_palette")
+    return palette, table, used
+
+
+def gif_palette(u8_clips):
+    """The colour tables of uint8 clips [B, T, H, W, 3] on the device (`ccvs_gif_palette`), one per clip from that
+    clip's own pixels: (palette uint8 [B, 256, 3], table uint8 [B, 32768], used int32 [B]), all on the device.  The pixels are counted
+    in 32768 bins of 5 bits per channel, median cut makes up to 256 boxes of the occupied bins, a box's mean colour is its palette
+    entry (`used` of them; the rest are 0) and `table` gives every bin's entry: a pixel's index is table[(R >> 3) << 10 | (G >> 3) << 5 |
+    B >> 3].  A [T, H, W, 3] input is one clip.  Views whose rows are dense and whose frame and clip strides hold a frame / a clip are
+    read in place.  Runs on the current stream; nothing is synchronised."""
+    _need_gpu(u8_clips)
+    clips, b, t, h, w, cs, fs = _gif_clips("gif_palette", u8_clips)
+    L = _lib.load()
+    work = torch.empty(max(int(L.ccvs_gif_workspace_bytes(b, t, h, w, 0)), 8), dtype=torch.uint8, device=clips.device)
+    return _gif_palette(L, clips, b, t, h, w, cs, fs, work)
+
+
+def gif_encode(u8_clips, band_rows=0, capacity=None, out=None):
+    """The GIF image data of uint8 clips [B, T, H, W, 3] on the device (`ccvs_gif_palette`, then `ccvs_gif_encode`, DESIGN.md section
+    4.27): every clip's pixels are mapped to its own 256 colours (`gif_palette`) and every frame's indices are LZW-coded on the GPU and
+    framed in sub-blocks -- what follows an image descriptor in a GIF file (`ccvs_amd.tools.gif` writes the container).  Returns
+    (stream uint8 [capacity], offsets int64 [B T + 1], palette uint8 [B, 256, 3]), all on the device -- frame j of clip i is
+    stream[offsets[i T + j]:offsets[i T + j + 1]].  band_rows: rows per independently coded band (0: about 4096 pixels).  Clips and
+    strides are handled as in `gif_palette`.  capacity: bytes of `stream` (None: a byte per pixel, which noise overflows); the offsets
+    are complete also when offsets[n] > capacity, nothing at or beyond `capacity` is written, and the CALLER runs again with a larger one
+    (`gif_encode_to_host` does; `ccvs_gif_stream_bound` always suffices).  out: optional uint8 stream to write into (its length is the
+    capacity).  Runs on the current stream; nothing is synchronised."""
+    _need_gpu(u8_clips, out)
+    clips, b, t, h, w, cs, fs = _gif_clips("gif_encode", u8_clips)
+    n, band_rows = b * t, int(band_rows)
+    L = _lib.load()
+    if out is not None:
+        assert out.dtype == torch.uint8 and out.dim() == 1 and out.is_contiguous() and capacity in (None, out.numel()), (out.dtype, out.shape)
+        capacity = out.numel()
+    elif capacity is None:
+        capacity = n * (2 + h * w + (h * w + 254) // 255)
+    stream = out if out is not None else torch.empty(int(capacity), dtype=torch.uint8, device=clips.device)
+    offsets = torch.empty(n + 1, dtype=torch.int64, device=clips.device)
+    work = torch.empty(max(int(L.ccvs_gif_workspace_bytes(b, t, h, w, max(band_rows, 0))), 8), dtype=torch.uint8, device=clips.device)
+    palette, table, _ = _gif_palette(L, clips, b, t, h, w, cs, fs, work)
+    _lib.check(L.ccvs_gif_encode(_p(clips), cs, fs, b, t, h, w, band_rows, _p(table), _p(stream), int(capacity), _p(offsets), _p(work),
+                                 _stream()), "ccvs_gif_encode")
+    return stream, offsets, palette
+
+
+def gif_encode_to_host(u8_clips, band_rows=0):
+    """`gif_encode`, then its results on the host: (bytes of all frames' payloads, list of B T + 1 offsets, palettes uint8 numpy
+    [B, 256, 3]).  Where the first run's stream is too small the offsets say by how much and a second run with that capacity is exact.
+    What crosses to the host is the offsets, offsets[n] coded bytes and 768 palette bytes per clip."""
+    stream, offsets, palette = gif_encode(u8_clips, band_rows)
+    off = offsets.cpu().tolist()
+    if off[-1] > stream.numel():
+        stream, offsets, palette = gif_encode(u8_clips, band_rows, capacity=off[-1])
+    return stream[:off[-1]].cpu().numpy().tobytes(), off, palette.cpu().numpy()
+
+
 # ------------------------------------------------------------------ the way back (include/ccvs_hip_decode.h)
 _MJPEG_STATUS = {1: "its table entry points outside the call's frames, stream, MCUs or tables", 2: "no Huffman code starts so",
                  3: "the MCUs need more bits than the unit has", 4: "a run leads past coefficient 63",

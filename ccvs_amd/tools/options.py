@@ -118,7 +118,9 @@ class Options:
         # --video_lz77: the apng files' deflate blocks may hold LZ77 matches, kept per block only where that is smaller (csrc/png_lz.hip:
         # the same pixels, never a larger file, far smaller ones for flat or structured frames, a slower encode); ignored unless the
         # files are apng
-        p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi", "apng"])
+        # gif -- animated GIF in 256 colours per clip, palette and LZW coding on the GPU (csrc/gif.hip); for showing: the frames are
+        # quantised, and the metrics and FVD commands do not read these files; the four --video_* options below are ignored
+        p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi", "apng", "gif"])
         p.add_argument("--video_quality", type=_jpeg_quality, default=90)
         p.add_argument("--video_subsampling", type=str, default="444", choices=["444", "422", "420"])
         _flag(p, "--video_optimize")
