@@ -2,6 +2,7 @@
 // KV-cached causal attention and the top-k / softmax / pick of the sampling loop.
 // Reference: models/skip_vid_generator/models/mingpt.py:33-117,186-305 and
 // models/skip_vid_generator/models/transformer_model.py:256-260,395-409.
+#include "attention_kv16.h"
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------
@@ -2053,8 +2054,10 @@ static bool step_tile2(const ccvs_gpt_decode* d) {
 // ccvs_gpt_decode_prepare plans it (gemm16_plan) and stores it in the persistent step's table.  visit(kind, g, name): `g` the phase's
 // descriptor (STEP_ATTENTION: x = q, y = att, kcache / vcache, H, Tmax, M = rows), `name` its launch name in error texts; a result
 // other than CCVS_OK ends the walk and is returned.  `who` names the caller in the layers' null-pointer check.
+// kv16 (ccvs_gpt_decode_step_bf16kv, launch chain only): the caches are bf16 -- ln1 + QKV is the plain GEMM into d->q with row stride 3C
+// (no scatter), and the attention phase carries q_sB = ldx = 3C; its K / V rows are the two upper thirds of that buffer.
 template <typename Visit>
-static int step_phases(const ccvs_gpt_decode* d, const char* who, Visit visit) {
+static int step_phases(const ccvs_gpt_decode* d, const char* who, Visit visit, bool kv16 = false) {
     const int D = d->C / d->H, grp_rows = step_grp_rows(d), wt = d->w_tiled ? 1 : 0;
     float* ws_slabs = (float*)d->workspace;
     int* ws_count = d->workspace ? (int*)((char*)d->workspace + GEMM_WS_SLAB_BYTES) : nullptr;
@@ -2068,29 +2071,30 @@ static int step_phases(const ccvs_gpt_decode* d, const char* who, Visit visit) {
         g.ln_s = L.qkv_s; g.ln_eps = d->ln_eps;
         g.kcache = L.kcache; g.vcache = L.vcache; g.C = d->C; g.H = d->H; g.D = D; g.Tq = 1; g.Tmax = d->Tmax; g.pos0 = 0; g.pos_dev = d->len; g.grp_rows = grp_rows;
         g.wt = wt;
-        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(qkv)")) != CCVS_OK) return rc;
+        if (kv16) { g.ldy = 3 * d->C; g.kcache = g.vcache = nullptr; g.C = g.H = g.D = g.Tq = g.Tmax = 0; g.pos_dev = nullptr; g.grp_rows = 0; }
+        if ((rc = visit(STEP_GEMM, g, kv16 ? "ccvs_gpt_decode_step_bf16kv(qkv)" : "ccvs_gpt_decode_step(qkv)")) != CCVS_OK) return rc;
         g = Gemm16{};  // attention over the cache
-        g.x = d->q; g.ldx = d->C; g.y = d->att; g.kcache = L.kcache; g.vcache = L.vcache; g.H = d->H; g.M = d->B; g.Tmax = d->Tmax;
+        g.x = d->q; g.ldx = kv16 ? 3 * d->C : d->C; g.y = d->att; g.kcache = L.kcache; g.vcache = L.vcache; g.H = d->H; g.M = d->B; g.Tmax = d->Tmax;
         g.pos_dev = d->len; g.grp_rows = grp_rows;
-        if ((rc = visit(STEP_ATTENTION, g, "ccvs_gpt_decode_step(attention)")) != CCVS_OK) return rc;
+        if ((rc = visit(STEP_ATTENTION, g, kv16 ? "ccvs_gpt_decode_step_bf16kv(attention)" : "ccvs_gpt_decode_step(attention)")) != CCVS_OK) return rc;
         g = Gemm16{};  // proj + residual (in place on x)
         g.x = d->att; g.ldx = d->C; g.w = L.proj_w; g.bias = L.proj_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->C; g.epi = 2;
         g.ws_slabs = ws_slabs; g.ws_count = ws_count;
         g.wt = wt;
-        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(proj)")) != CCVS_OK) return rc;
+        if ((rc = visit(STEP_GEMM, g, kv16 ? "ccvs_gpt_decode_step_bf16kv(proj)" : "ccvs_gpt_decode_step(proj)")) != CCVS_OK) return rc;
         g = Gemm16{};  // ln2 + fc + GELU
         g.x = d->x; g.ldx = d->C; g.w = L.fc_w; g.bias = L.fc_b; g.y = d->h; g.ldy = d->F; g.M = d->B; g.N = d->F; g.K = d->C; g.epi = 1;
         g.ln_s = L.fc_s; g.ln_eps = d->ln_eps;
         g.wt = wt;
-        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(fc)")) != CCVS_OK) return rc;
+        if ((rc = visit(STEP_GEMM, g, kv16 ? "ccvs_gpt_decode_step_bf16kv(fc)" : "ccvs_gpt_decode_step(fc)")) != CCVS_OK) return rc;
         g = Gemm16{};  // fc2 + residual (in place on x)
         g.x = d->h; g.ldx = d->F; g.w = L.fc2_w; g.bias = L.fc2_b; g.res = d->x; g.y = d->x; g.ldy = d->C; g.M = d->B; g.N = d->C; g.K = d->F; g.epi = 2;
         g.ws_slabs = ws_slabs; g.ws_count = ws_count;
         g.wt = wt;
-        if ((rc = visit(STEP_GEMM, g, "ccvs_gpt_decode_step(fc2)")) != CCVS_OK) return rc;
+        if ((rc = visit(STEP_GEMM, g, kv16 ? "ccvs_gpt_decode_step_bf16kv(fc2)" : "ccvs_gpt_decode_step(fc2)")) != CCVS_OK) return rc;
     }
     Gemm16 g = step_head_gemm(d);
-    return visit(STEP_GEMM, g, "ccvs_gpt_decode_step(head)");
+    return visit(STEP_GEMM, g, kv16 ? "ccvs_gpt_decode_step_bf16kv(head)" : "ccvs_gpt_decode_step(head)");
 }
 
 // The phase table of d's persistent step, written to d->program (device memory): the phases of step_phases, each GEMM planned by
@@ -2178,30 +2182,33 @@ static int launch_step_persistent(const ccvs_gpt_decode* d, int D, hipStream_t s
 // ccvs_gemm_nt / ccvs_gemm_ln / ccvs_sample_topk for a single new position, 5 * n_layer + 3 launches
 // on one stream, every per-step quantity device-resident (hipGraph-capturable).
 // ---------------------------------------------------------------------------------------
-extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
-    CCVS_REQUIRE(d && d->layers && d->tok_emb && d->pos_table && d->head_w && d->head_b && d->head_s, "ccvs_gpt_decode_step: null pointer");
+static int decode_step(const ccvs_gpt_decode* d, void* stream, bool kv16) {
+    const char* who = kv16 ? "ccvs_gpt_decode_step_bf16kv" : "ccvs_gpt_decode_step";   // the entry the caller came through, in every error text
+    CCVS_REQUIRE(d && d->layers && d->tok_emb && d->pos_table && d->head_w && d->head_b && d->head_s, "%s: null pointer", who);
     CCVS_REQUIRE(d->tok && d->codes && d->widx && d->len && d->x && d->q && d->att && d->h && d->logits && d->state,
-                 "ccvs_gpt_decode_step: null state pointer");
+                 "%s: null state pointer", who);
     CCVS_REQUIRE(d->B > 0 && d->C > 0 && d->H > 0 && d->C % d->H == 0 && d->F > 0 && d->n_layer > 0 && d->Tmax > 0 && d->vocab > 0 && d->V > 0,
-                 "ccvs_gpt_decode_step: bad shape");
+                 "%s: bad shape", who);
     const int D = d->C / d->H;
-    CCVS_REQUIRE(D == 64 || D == 32 || D == 16, "ccvs_gpt_decode_step: head dim %d unsupported (16, 32, 64)", D);
-    CCVS_REQUIRE(d->temperature > 0.f, "ccvs_gpt_decode_step: bad temperature");
-    CCVS_REQUIRE(d->groups >= 0 && (d->groups <= 1 || d->B % d->groups == 0), "ccvs_gpt_decode_step: %d rows do not split into %d groups", d->B, d->groups);
+    CCVS_REQUIRE(D == 64 || D == 32 || D == 16, "%s: head dim %d unsupported (16, 32, 64)", who, D);
+    CCVS_REQUIRE(d->temperature > 0.f, "%s: bad temperature", who);
+    CCVS_REQUIRE(d->groups >= 0 && (d->groups <= 1 || d->B % d->groups == 0), "%s: %d rows do not split into %d groups", who, d->B, d->groups);
     // (more rows than the weight-stream form takes run the row-blocked form inside launch_gemm16; row groups cannot)
-    CCVS_REQUIRE(d->groups <= 1 || d->B <= GEMM_DECODE_MAX_M, "ccvs_gpt_decode_step: at most %d rows per grouped step", GEMM_DECODE_MAX_M);
+    CCVS_REQUIRE(d->groups <= 1 || d->B <= GEMM_DECODE_MAX_M, "%s: at most %d rows per grouped step", who, GEMM_DECODE_MAX_M);
     const int grp_rows = step_grp_rows(d);
     const size_t smem_att = (size_t)(16 + 4 * 256 + d->Tmax) * sizeof(float);
     // the pick's form: top_p 0 or 1 = off (the top-k form), inside (0, 1) = the nucleus form with its own LDS size and cap
-    CCVS_REQUIRE(d->top_p == 0.f || d->top_p == 1.f || topp_on(d->top_p), "ccvs_gpt_decode_step: top_p %g is neither inside (0, 1) nor 0 / 1 (off)", (double)d->top_p);
+    CCVS_REQUIRE(d->top_p == 0.f || d->top_p == 1.f || topp_on(d->top_p), "%s: top_p %g is neither inside (0, 1) nor 0 / 1 (off)", who, (double)d->top_p);
     const bool topp = topp_on(d->top_p);
     const size_t smem_pick = (size_t)(topp ? PICK_TOPP_SMEM_WORDS(d->V) : PICK_SMEM_WORDS(d->V)) * sizeof(float);
-    CCVS_REQUIRE(smem_att <= 64 * 1024, "ccvs_gpt_decode_step: sequence too long for the LDS score buffer");
-    if (topp) CCVS_REQUIRE(smem_pick <= 160 * 1024, "ccvs_gpt_decode_step: vocabulary %d too large for the top_p form (at most %d)", d->V, ccvs_sample_topp_max_vocab());
-    CCVS_REQUIRE(smem_pick <= 160 * 1024, "ccvs_gpt_decode_step: vocabulary %d too large", d->V);
+    CCVS_REQUIRE(smem_att <= 64 * 1024, "%s: sequence too long for the LDS score buffer", who);
+    if (topp) CCVS_REQUIRE(smem_pick <= 160 * 1024, "%s: vocabulary %d too large for the top_p form (at most %d)", who, d->V, ccvs_sample_topp_max_vocab());
+    CCVS_REQUIRE(smem_pick <= 160 * 1024, "%s: vocabulary %d too large", who, d->V);
     hipStream_t st = (hipStream_t)stream;
+    // (bf16 caches: gpt_step_kernel's attention phase and its QKV scatter read and write fp32 cache rows)
+    CCVS_REQUIRE(!(kv16 && d->persistent), "ccvs_gpt_decode_step_bf16kv: persistent = 1 is refused: the persistent step (gpt_step_kernel) runs on fp32 KV caches only");
     if (d->persistent) {   // ONE launch (gpt_step_kernel) over the phase table ccvs_gpt_decode_prepare wrote to d->program
-        int rc_ = step_check(d, "ccvs_gpt_decode_step");
+        int rc_ = step_check(d, who);
         if (rc_ != CCVS_OK) return rc_;
         return launch_step_persistent(d, D, st);
     }
@@ -2211,15 +2218,19 @@ extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
         const long total = (long)d->B * d->C;
         hipLaunchKernelGGL(gpt_embed_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, st, d->tok, 1L, (const int32_t*)nullptr, d->pos_off,
                            (const int32_t*)d->len, grp_rows, 1, d->tok_emb, d->pos_table, d->x, total, d->C, d->vocab);
-        CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(embed)");
+        CCVS_CHECK_LAUNCH(kv16 ? "ccvs_gpt_decode_step_bf16kv(embed)" : "ccvs_gpt_decode_step(embed)");
     }
     const float scale = 1.0f / sqrtf((float)D);
-    const int rc = step_phases(d, "ccvs_gpt_decode_step", [&](int kind, Gemm16& g, const char* name) -> int {
+    const int rc = step_phases(d, who, [&](int kind, Gemm16& g, const char* name) -> int {
         if (kind == STEP_GEMM) return launch_gemm16(g, st, name);
-        launch_attention_decode(D, g.M * g.H, smem_att, st, g.x, g.ldx, g.kcache, g.vcache, g.y, g.H, 0, g.pos_dev, g.grp_rows, g.Tmax, scale);
+        if (kv16)   // the appending form: K and V of this position are columns C.. and 2C.. of the QKV output
+            ccvs_kv16_launch_attention_decode(D, g.M * g.H, smem_att, st, g.x, g.ldx, g.x + d->C, g.x + 2 * d->C, g.ldx, (uint16_t*)g.kcache,
+                                              (uint16_t*)g.vcache, g.y, g.H, 0, g.pos_dev, g.grp_rows, g.Tmax, scale);
+        else
+            launch_attention_decode(D, g.M * g.H, smem_att, st, g.x, g.ldx, g.kcache, g.vcache, g.y, g.H, 0, g.pos_dev, g.grp_rows, g.Tmax, scale);
         CCVS_CHECK_LAUNCH(name);
         return CCVS_OK;
-    });
+    }, kv16);
     if (rc != CCVS_OK) return rc;
     // pick + bookkeeping
     if (topp) {
@@ -2230,6 +2241,11 @@ extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) {
         hipLaunchKernelGGL(sample_topk_kernel, dim3(d->B), dim3(256), smem_pick, st, d->logits, (long)d->V, d->noise, d->tok, 1L, d->V,
                            d->top_k, d->temperature, step_advance(d, grp_rows));
     }
-    CCVS_CHECK_LAUNCH("ccvs_gpt_decode_step(pick)");
+    CCVS_CHECK_LAUNCH(kv16 ? "ccvs_gpt_decode_step_bf16kv(pick)" : "ccvs_gpt_decode_step(pick)");
     return CCVS_OK;
 }
+
+extern "C" int ccvs_gpt_decode_step(const ccvs_gpt_decode* d, void* stream) { return decode_step(d, stream, false); }
+
+// The same chain on bf16 KV caches (include/ccvs_hip_kv16.h): layers[i].kcache / vcache point to bf16, d->q holds 3C floats per row.
+extern "C" int ccvs_gpt_decode_step_bf16kv(const ccvs_gpt_decode* d, void* stream) { return decode_step(d, stream, true); }

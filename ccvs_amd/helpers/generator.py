@@ -687,6 +687,11 @@ class Generator:
             self.engine = engine
             self.valid_data_info = self.get_data_info("valid", "img" if opt.gen_from_img else "vid")
             self.build_models(is_main=True)
+            if self.transformer_model is not None and engine.rank == 0:   # once per run, not once per rank
+                net_t = self.transformer_model.net_t
+                rows = int(self.valid_data_info["batch_size_per_gpu"])
+                print(f"KV cache ({net_t.kv_dtype}): {net_t.kv_cache_bytes(rows, net_t.block_size) / 2 ** 20:.1f} MiB per batch of "
+                      f"{rows} x {net_t.block_size} positions")
             rec = not opt.gen_from_img and (getattr(opt, "rec_pass", True) or opt.rec_only)
             writer = _ResultWriter(self) if save else None
 

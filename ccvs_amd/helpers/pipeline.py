@@ -372,7 +372,7 @@ class PipelinedRun:
         tr = self.chain_list[chain][0]
         ver = sum(p_._version for p_ in tr.net_t.parameters())
         return (chain, rows, groups, opt.vid_len, opt.z_len, opt.cond_len, bool(opt.p2p), bool(opt.sample), opt.top_k, float(opt.temperature),
-                tr.sample_noise, ver, ops.check_top_p(getattr(opt, "top_p", None)))
+                tr.sample_noise, ver, ops.check_top_p(getattr(opt, "top_p", None)), tr.net_t.kv_dtype)
 
     def _is_cold(self, c, nb, g):
         # the captured steps live in the engine's cache of that row count: ask the engine, not only the side set (a serial

@@ -54,6 +54,9 @@ FLOWVIZ_SYMBOLS = ["ccvs_flow_export", "ccvs_flow_max", "ccvs_flow_render"]
 # every symbol include/ccvs_hip_output_gif.h declares (the GIF output stage: a palette per clip, LZW-coded frames; included by ccvs_hip.h
 # too; named apart from the `*_EXPORTS` lists for the same reason)
 GIF_SYMBOLS = ["ccvs_gif_workspace_bytes", "ccvs_gif_stream_bound", "ccvs_gif_palette", "ccvs_gif_encode"]
+# every symbol include/ccvs_hip_kv16.h declares (the token loop on a bf16 KV cache: append, attention, the step's launch chain; included by
+# ccvs_hip.h too; named apart from the `*_EXPORTS` lists for the same reason)
+KV16_SYMBOLS = ["ccvs_kv_append_bf16", "ccvs_attention_bf16", "ccvs_gpt_decode_step_bf16kv"]
 
 
 class ConvDesc(C.Structure):
@@ -212,6 +215,9 @@ def load():
         "ccvs_sample_topp_philox": [vp, i64, vp, i64, i32, i32, i32, f32, f32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp],
         "ccvs_sample_topn": [vp, i64, vp, vp, vp, i32, i32, i32, f32, i32, vp],
         "ccvs_gpt_decode_step": [C.POINTER(GptDecode), vp],
+        "ccvs_gpt_decode_step_bf16kv": [C.POINTER(GptDecode), vp],
+        "ccvs_kv_append_bf16": [vp, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp],
+        "ccvs_attention_bf16": [vp, i64, i64, vp, vp, i64, vp, vp, vp, i32, i32, i32, i32, vp, i32, i32, i32, vp],
         "ccvs_gpt_decode_status": [vp, vp],
         "ccvs_gpt_decode_prepare": [C.POINTER(GptDecode), vp],
         "ccvs_pack_u8": [vp, vp, i64, i32, i32, f32, f32, vp],

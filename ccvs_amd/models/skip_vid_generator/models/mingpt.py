@@ -215,6 +215,11 @@ class GPT(nn.Module):
         # include/ccvs_hip_gemm.h, ccvs_gemm_tiled): every wave load is 1 KB of whole 128-byte lines.  Same bits (tests/test_gemm_tiled_gpu.py);
         # costs a second copy of the weights (prefill and the eager forward keep the row-major ones).  Steps of more than 256 rows keep the row-major weights.  CCVS_DECODE_TILED_W=0 / 1.
         self.tiled_weights = os.environ.get("CCVS_DECODE_TILED_W", "1") == "1"
+        # kv_dtype: "fp32" (default: today's bits) or "bf16" (`--x_kv_dtype bf16`) -- every key / value row is rounded to bfloat16 when it
+        # is appended to the cache and every attention product reads the stored values, widened exactly (include/ccvs_hip_kv16.h has
+        # the definition).  Half the cache bytes; sampled tokens differ from the fp32 mode's.  Read by `begin()`: a cache
+        # of the other type is dropped with its descriptor and graphs.  Not with the persistent step (fp32 caches only).
+        self.kv_dtype = "fp32"
 
     @property
     def _graphs(self):
@@ -227,6 +232,12 @@ class GPT(nn.Module):
     def drop_engine_state(self):
         """Free every KV cache / captured decode step (they are rebuilt on the next call)."""
         self._cache, self._caches = None, {}
+
+    def kv_cache_bytes(self, batch, max_len):
+        """Bytes of the KV cache of `batch` sequences of `max_len` positions in the current `kv_dtype`: layers x heads x positions x
+        head dim x 2 (K and V) x element size -- arithmetic from the shapes, nothing is allocated."""
+        cfg = self.config
+        return 2 * cfg.n_layer * batch * max_len * cfg.n_embd * ops.check_kv_dtype(self.kv_dtype).itemsize
 
     def _philox_words(self):
         """[(key0, key1, row0, call)] of this generate() call, one tuple per row group."""
@@ -391,23 +402,28 @@ class GPT(nn.Module):
         d = cfg.n_embd // cfg.n_head
         groups = self.n_groups()
         assert batch % groups == 0, f"{batch} rows do not split into {groups} row groups"
+        kvd = ops.check_kv_dtype(self.kv_dtype)
+        kv16 = kvd == torch.bfloat16
+        if kv16 and self.persistent_step:
+            raise ValueError("CCVS_DECODE_PERSISTENT=1 together with a bf16 KV cache (--x_kv_dtype bf16): the persistent decode step "
+                             "(gpt_step_kernel) reads and writes fp32 caches only")
         c = self._caches.get(batch)
-        if c is None or c["T"] < max_len or c["dev"] != dev or c["G"] != groups:
+        if c is None or c["T"] < max_len or c["dev"] != dev or c["G"] != groups or c["kv_dtype"] != kvd:
             # (captured graphs live in the cache dict: they go with the buffers they hold)
             if c is None and len(self._caches) >= 8:
                 self._caches.pop(next(iter(self._caches)))   # a handful of batch sizes at most: drop the oldest
             C, V = cfg.n_embd, self.head.weight.shape[0]
             f32 = dict(dtype=torch.float32, device=dev)
-            kc = [torch.empty(batch, cfg.n_head, max_len, d, **f32) for _ in range(cfg.n_layer)]
-            vc = [torch.empty(batch, cfg.n_head, max_len, d, **f32) for _ in range(cfg.n_layer)]
+            kc = [torch.empty(batch, cfg.n_head, max_len, d, dtype=kvd, device=dev) for _ in range(cfg.n_layer)]
+            vc = [torch.empty(batch, cfg.n_head, max_len, d, dtype=kvd, device=dev) for _ in range(cfg.n_layer)]
             c = self._caches[batch] = {
-                "B": batch, "G": groups, "T": max_len, "dev": dev, "k": kc, "v": vc,
+                "B": batch, "G": groups, "T": max_len, "dev": dev, "k": kc, "v": vc, "kv_dtype": kvd,
                 "len_dev": torch.zeros(groups, dtype=torch.int32, device=dev),  # cache positions filled, per row group (they advance together)
                 "widx": torch.zeros(groups, dtype=torch.int32, device=dev),     # column of `codes` the next token goes to
                 "tok": torch.zeros(batch, 1, dtype=torch.int64, device=dev),   # last sampled token
                 "codes": torch.zeros(batch, max_len, dtype=torch.int64, device=dev),
-                # scratch of ccvs_gpt_decode_step
-                "x": torch.empty(batch, C, **f32), "q": torch.empty(batch, C, **f32), "att": torch.empty(batch, C, **f32),
+                # scratch of ccvs_gpt_decode_step (bf16 caches: q is the step's whole QKV output, [B,3C] -- ccvs_gpt_decode_step_bf16kv)
+                "x": torch.empty(batch, C, **f32), "q": torch.empty(batch, 3 * C if kv16 else C, **f32), "att": torch.empty(batch, C, **f32),
                 "h": torch.empty(batch, 4 * C, **f32), "logits": torch.empty(batch, V, **f32), "noise": torch.empty(batch, V, **f32),
                 "state": torch.zeros(groups, 8, dtype=torch.int32, device=dev),    # per group: [0] steps done, [4..5] Philox key (ccvs_hip.h)
                 "noise_ptrs": torch.zeros(groups, dtype=torch.int64, device=dev),  # per group: its pre-drawn noise stream (ccvs_gpt_decode.noise_stream)
@@ -439,12 +455,35 @@ class GPT(nn.Module):
         # whole-sequence calls always run the row-blocked GEMM form, single-position calls the weight-stream form: a row's
         # bits must not depend on how many rows share the launch (include/ccvs_hip.h, CCVS_GEMM_SEQ)
         seq = ops.GEMM_SEQ if tq > 1 else 0
+        if c["kv_dtype"] == torch.bfloat16:
+            return self._layers_bf16kv(x, b, tq, pos0, pos_dev, seq)
         for i, blk in enumerate(self.blocks):
             # 5 launches per layer: [ln1 + QKV + cache scatter] [attention] [proj + residual]
             #                       [ln2 + fc + GELU] [fc2 + residual]
             qkv_w, fc_w = blk.folded()
             q = ops.gemm_ln_qkv(x, *qkv_w, c["k"][i], c["v"][i], b, tq, pos0, pos_dev, eps=blk.ln1.eps).view(b, tq, C)
             att = ops.attention(q, c["k"][i], c["v"][i], pos0, pos_dev)
+            ops.gemm_nt(att.view(b * tq, C), blk.attn.proj.weight, blk.attn.proj.bias, ops.EPI_RESIDUAL | seq, residual=x, out=x)
+            h = ops.gemm_ln(x, *fc_w, eps=blk.ln2.eps, epilogue=ops.EPI_GELU | seq)
+            ops.gemm_nt(h, blk.mlp[3].weight, blk.mlp[3].bias, ops.EPI_RESIDUAL | seq, residual=x, out=x)
+        if pos_dev is None:
+            c["len"] = pos0 + tq
+        return x
+
+    def _layers_bf16kv(self, x, b, tq, pos0, pos_dev, seq):
+        """`_layers` on a bf16 KV cache: ln1 + QKV is the plain folded GEMM to [b*tq, 3C] (the bits the fp32 mode scatters); whole
+        sequences then append (round) and attend to the stored rows, a single position runs the appending decode form."""
+        c = self._cache
+        C = self.config.n_embd
+        for i, blk in enumerate(self.blocks):
+            qkv_w, fc_w = blk.folded()
+            qkv = ops.gemm_ln(x, *qkv_w, eps=blk.ln1.eps, epilogue=seq).view(b, tq, 3 * C)
+            q, k, v = qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:]
+            if tq > 1:
+                ops.kv_append_bf16(k, v, c["k"][i], c["v"][i], pos0, pos_dev)
+                att = ops.attention_bf16(q, c["k"][i], c["v"][i], pos0, pos_dev)
+            else:
+                att = ops.attention_bf16(q, c["k"][i], c["v"][i], pos0, pos_dev, kv_new=(k, v))
             ops.gemm_nt(att.view(b * tq, C), blk.attn.proj.weight, blk.attn.proj.bias, ops.EPI_RESIDUAL | seq, residual=x, out=x)
             h = ops.gemm_ln(x, *fc_w, eps=blk.ln2.eps, epilogue=ops.EPI_GELU | seq)
             ops.gemm_nt(h, blk.mlp[3].weight, blk.mlp[3].bias, ops.EPI_RESIDUAL | seq, residual=x, out=x)
@@ -568,7 +607,7 @@ class GPT(nn.Module):
         host_stream = bool(sampler["sample"] and not device_rng and sampler.get("stream"))   # host noise read from a pre-drawn stream
         key = (tuple(blk._folded[0] for blk in self.blocks), head_key, sampler["sample"], sampler["top_k"],
                sampler["temperature"], device_rng, host_stream, c["frame_pos0"], bool(self.persistent_step),
-               tuple(blk.tiled()[0] for blk in self.blocks) if tiled else None, sampler.get("top_p"))
+               tuple(blk.tiled()[0] for blk in self.blocks) if tiled else None, sampler.get("top_p"), c["kv_dtype"])
         if c["desc"] is None or c["desc"][0] != key:
             layers = []
             for i, blk in enumerate(self.blocks):
@@ -584,7 +623,7 @@ class GPT(nn.Module):
                 noise=c["noise"] if (sampler["sample"] and not device_rng and not host_stream) else None, rng=device_rng,
                 noise_stream=c["noise_ptrs"] if host_stream else None,
                 top_k=sampler["top_k"], temperature=sampler["temperature"], top_p=sampler.get("top_p"), state=c["state"],
-                persistent=self.persistent_step,
+                persistent=self.persistent_step, kv_dtype=c["kv_dtype"],
                 tiled=([blk.tiled()[1] for blk in self.blocks], self._head_tiled()) if tiled else None)
             c["desc"] = (key, desc)
             c["graphs"] = {}   # captured graphs replay the OLD descriptor's pointers (packed weights are freed with it)
@@ -755,7 +794,7 @@ class GPT(nn.Module):
                     run += 1
                 c["len_dev"].fill_(c["len"])
                 c["widx"].fill_(n_code)
-                self._replay_steps(sampler, (sampler["sample"], sampler["top_k"], sampler["temperature"], n_cond, b, "stream", sampler.get("top_p")), run)
+                self._replay_steps(sampler, (sampler["sample"], sampler["top_k"], sampler["temperature"], n_cond, b, "stream", sampler.get("top_p"), c["kv_dtype"]), run)
                 c["len"] += run          # each replay appended the previous pick, then picked the next
                 n_code += run
                 fed += run
@@ -798,6 +837,9 @@ class GPT(nn.Module):
         is read at the last FRAME position either way.  Every pick is a full forward over the merged prefix -- what the
         reference does for every token of every configuration."""
         cfg = self.config
+        if ops.check_kv_dtype(self.kv_dtype) != torch.float32:
+            raise NotImplementedError("--x_state_front together with --x_kv_dtype bf16: that path runs a full forward per pick and keeps no "
+                                      "KV cache between picks, so there is nothing for the mode to save")
         size, ss = cfg.shape[0] * cfg.shape[1], cfg.state_size
         tot, cap = size + ss, cfg.num_blocks * ss
         b = code.shape[0]
@@ -897,7 +939,7 @@ class GPT(nn.Module):
         if not eager:
             if self.progress is not None:
                 self.progress(t0 + 1, c["codes"])
-            self._replay_steps(sampler, (bool(sample), top_k, float(temperature), n_pre + n_cond, b, sampler["top_p"]), add_len - 1, known=t0 + 1)
+            self._replay_steps(sampler, (bool(sample), top_k, float(temperature), n_pre + n_cond, b, sampler["top_p"], c["kv_dtype"]), add_len - 1, known=t0 + 1)
         else:
             for _ in range(add_len - 1):
                 nz = None

@@ -91,6 +91,15 @@ class Transformer(torch.nn.Module):
                     state_front=opt.state_front).cuda()
         if self.is_main:
             net_t = load_network(net_t, "transformer_t", opt, head_to_n=getattr(opt, "head_to_n", 0))
+        kv_dtype = getattr(opt, "kv_dtype", None) or "fp32"   # --x_kv_dtype
+        ops.check_kv_dtype(kv_dtype)
+        if kv_dtype != "fp32" and opt.state_front:
+            raise NotImplementedError("--x_state_front together with --x_kv_dtype bf16: that path runs a full forward per pick and keeps no "
+                                      "KV cache between picks")
+        if kv_dtype != "fp32" and net_t.persistent_step:
+            raise ValueError("CCVS_DECODE_PERSISTENT=1 together with --x_kv_dtype bf16: the persistent decode step reads and writes fp32 "
+                             "KV caches only")
+        net_t.kv_dtype = kv_dtype
         return net_t
 
     # ------------------------------------------------------------------ teacher-forced loss

@@ -724,6 +724,7 @@ def gemm_ln(x, wg, bb, s, eps=1e-5, epilogue=EPI_NONE, out=None):
 def gemm_ln_qkv(x, wg, bb, s, kcache, vcache, b, tq, pos0, pos_dev=None, eps=1e-5, out=None):
     """ln1 + fused QKV projection: returns q [b*tq, C] (`out`, dense, when given); K / V go straight into the caches."""
     _need_gpu(x, wg, bb, s, kcache, vcache, pos_dev, out)
+    _need_cache_dtype("gemm_ln_qkv", torch.float32, kcache, vcache)
     c = x.shape[1]
     _, h, tmax, d = kcache.shape
     assert x.shape[0] == b * tq and x.stride(1) == 1 and wg.shape == (3 * c, c) and h * d == c
@@ -778,6 +779,7 @@ def gemm_tiled(x, wt, n, bias=None, epilogue=EPI_NONE, residual=None, out=None, 
 
 def kv_append(k, v, kcache, vcache, pos0, pos_dev=None):
     """k, v [B,Tq,H*D] views (row stride shared) -> caches [B,H,Tmax,D] at pos0 (+ *pos_dev).."""
+    _need_cache_dtype("kv_append", torch.float32, kcache, vcache)
     b, tq, hd = k.shape
     _, h, tmax, d = kcache.shape
     assert k.stride(2) == 1 and v.stride() == k.stride()
@@ -788,6 +790,7 @@ def kv_append(k, v, kcache, vcache, pos0, pos_dev=None):
 
 def attention(q, kcache, vcache, pos0, pos_dev=None):
     """q [B,Tq,H*D] view -> out [B,Tq,H*D]; query t sees cache positions 0..pos0(+*pos_dev)+t."""
+    _need_cache_dtype("attention", torch.float32, kcache, vcache)
     b, tq, hd = q.shape
     _, h, tmax, d = kcache.shape
     assert q.stride(2) == 1
@@ -795,6 +798,75 @@ def attention(q, kcache, vcache, pos0, pos_dev=None):
     L = _lib.load()
     _lib.check(L.ccvs_attention(_p(q), q.stride(0), q.stride(1), _p(kcache), _p(vcache), _p(out), b, h, tq, pos0, _p(pos_dev), tmax, d,
                                 _stream()), "ccvs_attention")
+    return out
+
+
+KV_DTYPES = {"fp32": torch.float32, "bf16": torch.bfloat16}
+
+
+def check_kv_dtype(kv_dtype):
+    """The KV cache's element type as torch names it, from "fp32" / "bf16" (`--x_kv_dtype`) or a torch dtype.  ValueError for the rest."""
+    if kv_dtype in KV_DTYPES:
+        return KV_DTYPES[kv_dtype]
+    if kv_dtype in KV_DTYPES.values():
+        return kv_dtype
+    raise ValueError(f"kv_dtype must be one of {sorted(KV_DTYPES)}, got {kv_dtype!r}")
+
+
+def _need_cache_dtype(name, want, *caches):
+    """An op never reinterprets a cache: the fp32 ops take fp32 caches, the `*_bf16` ops bf16 caches."""
+    for c in caches:
+        if c.dtype != want:
+            raise ValueError(f"{name}: the KV cache is {c.dtype}, this op reads and writes {want} caches")
+        if not c.is_contiguous():
+            raise ValueError(f"{name}: the KV cache must be contiguous")
+
+
+def kv_append_bf16(k, v, kcache, vcache, pos0, pos_dev=None):
+    """`kv_append` on bf16 caches (`ccvs_kv_append_bf16`, include/ccvs_hip_kv16.h): k, v fp32 [B,Tq,H*D] views (strides shared) are
+    rounded to bf16 (round to nearest even: `.to(torch.bfloat16)`) into the caches [B,H,Tmax,D] at pos0 (+ *pos_dev)..; a position at or
+    beyond Tmax is skipped."""
+    _need_cache_dtype("kv_append_bf16", torch.bfloat16, kcache, vcache)
+    _need_gpu(k, v, kcache, vcache, pos_dev)
+    if k.dtype != torch.float32 or v.dtype != torch.float32:
+        raise ValueError("kv_append_bf16: k and v are the fp32 rows of the QKV GEMM")
+    b, tq, hd = k.shape
+    _, h, tmax, d = kcache.shape
+    assert k.stride(2) == 1 and v.stride() == k.stride() and h * d == hd and kcache.shape == vcache.shape and kcache.shape[0] == b
+    L = _lib.load()
+    _lib.check(L.ccvs_kv_append_bf16(_p(k), _p(v), k.stride(0), k.stride(1), _p(kcache), _p(vcache), b, h, tq, pos0, _p(pos_dev), tmax, d,
+                                     _stream()), "ccvs_kv_append_bf16")
+
+
+def attention_bf16(q, kcache, vcache, pos0, pos_dev=None, kv_new=None, grp_rows=0):
+    """`attention` over bf16 caches (`ccvs_attention_bf16`): q fp32 [B,Tq,H*D] view -> out fp32 [B,Tq,H*D]; every stored value is widened
+    exactly and the arithmetic is fp32.  kv_new = (k, v), fp32 [B,1,H*D] views of one stride (Tq = 1 only): the APPENDING decode form --
+    the call rounds those rows into the caches at pos0 (+ *pos_dev) and attends to the rounded values; None: the caches hold that position.
+    grp_rows > 0 (Tq = 1): row groups of a grouped decode step -- pos_dev is int32 [B / grp_rows], one cache length per group."""
+    _need_cache_dtype("attention_bf16", torch.bfloat16, kcache, vcache)
+    _need_gpu(q, kcache, vcache, pos_dev)
+    if q.dtype != torch.float32:
+        raise ValueError("attention_bf16: q is fp32")
+    b, tq, hd = q.shape
+    _, h, tmax, d = kcache.shape
+    assert q.stride(2) == 1 and h * d == hd and kcache.shape == vcache.shape and kcache.shape[0] == b
+    kn = vn = None
+    kv_sb = 0
+    if kv_new is not None:
+        kn, vn = kv_new
+        _need_gpu(kn, vn)
+        if kn.dtype != torch.float32 or vn.dtype != torch.float32:
+            raise ValueError("attention_bf16: kv_new holds the fp32 rows of the QKV GEMM")
+        if tq != 1:
+            raise ValueError("attention_bf16: kv_new is for the decode form (Tq = 1)")
+        assert kn.shape == (b, 1, hd) and vn.shape == kn.shape and kn.stride(2) == 1 and vn.stride() == kn.stride()
+        kv_sb = kn.stride(0)
+    if grp_rows:
+        assert pos_dev is not None and pos_dev.dtype == torch.int32 and pos_dev.is_contiguous() and pos_dev.numel() * grp_rows == b
+    out = torch.empty(b, tq, hd, dtype=torch.float32, device=q.device)
+    L = _lib.load()
+    _lib.check(L.ccvs_attention_bf16(_p(q), q.stride(0), q.stride(1), _p(kn), _p(vn), kv_sb, _p(kcache), _p(vcache), _p(out), b, h, tq, pos0,
+                                     _p(pos_dev), int(grp_rows), tmax, d, _stream()), "ccvs_attention_bf16")
     return out
 
 
@@ -877,11 +949,18 @@ class GptDecodeStep:
 
     def __init__(self, layers, B, C, H, Tmax, ln_eps, tok_emb, pos_table, pos_off, head, tok, codes, widx, length,
                  x, q, att, h, logits, noise, top_k, temperature, state, rng=False, groups=1, noise_stream=None, persistent=False,
-                 tiled=None, top_p=None):
+                 tiled=None, top_p=None, kv_dtype=torch.float32):
         """top_p: nucleus sampling in the step's pick (`ccvs_gpt_decode.top_p`; None or 1.0: off).
+        kv_dtype: the type of every layer's kcache / vcache.  bf16: `launch()` calls `ccvs_gpt_decode_step_bf16kv` (include/ccvs_hip_kv16.h),
+        `q` is [B,3C] (the whole QKV output of a step), and `persistent` is refused.
         tiled: None, or ([{qkv_w, proj_w, fc_w, fc2_w} per layer], head_w) = `tile_weight` of the matrices in `layers` / `head`: the
         step then reads those (`ccvs_gpt_decode.w_tiled`); the row-major ones still give the shapes."""
         hw, hb, hs = head
+        self.kv_dtype = check_kv_dtype(kv_dtype)
+        kv16 = self.kv_dtype == torch.bfloat16
+        if kv16 and persistent:
+            raise ValueError("the persistent decode step (CCVS_DECODE_PERSISTENT=1, `ccvs_gpt_decode.persistent`) reads fp32 KV caches only: "
+                             "not together with a bf16 KV cache (--x_kv_dtype bf16)")
         keep = [tok_emb, pos_table, hw, hb, hs, tok, codes, widx, length, x, q, att, h, logits, noise, state, noise_stream]
         for t in keep:
             if t is not None:
@@ -899,7 +978,11 @@ class GptDecodeStep:
             for name, t in lay.items():
                 t = t.detach()
                 _need_gpu(t)
-                assert t.dtype == torch.float32 and t.is_contiguous(), name
+                if name in ("kcache", "vcache"):
+                    _need_cache_dtype("GptDecodeStep", self.kv_dtype, t)
+                    assert t.shape == (B, H, Tmax, C // H), (name, t.shape)
+                else:
+                    assert t.dtype == torch.float32 and t.is_contiguous(), name
                 if tiled is not None and name in tiled[0][i]:
                     n_k, t = t.shape, tiled[0][i][name]
                     _need_gpu(t)
@@ -908,6 +991,7 @@ class GptDecodeStep:
                 setattr(arr[i], name, _p(t))
         F = layers[0]["fc_w"].shape[0]
         assert x.shape == (B, C) and h.shape == (B, F) and logits.shape == (B, hw.shape[0])
+        assert q.shape == (B, 3 * C if kv16 else C) and att.shape == (B, C), (q.shape, att.shape)
         self.ws = _gemm_workspace(x.device)
         d = _lib.GptDecode()
         d.B, d.C, d.H, d.F, d.n_layer, d.Tmax, d.vocab, d.V = B, C, H, F, len(layers), Tmax, tok_emb.shape[0], hw.shape[0]
@@ -944,7 +1028,10 @@ class GptDecodeStep:
 
     def launch(self):
         L = _lib.load()
-        _lib.check(L.ccvs_gpt_decode_step(C.byref(self.desc), _stream()), "ccvs_gpt_decode_step")
+        if self.kv_dtype == torch.bfloat16:
+            _lib.check(L.ccvs_gpt_decode_step_bf16kv(C.byref(self.desc), _stream()), "ccvs_gpt_decode_step_bf16kv")
+        else:
+            _lib.check(L.ccvs_gpt_decode_step(C.byref(self.desc), _stream()), "ccvs_gpt_decode_step")
 
     def status(self):
         """Persistent step: synchronise the current stream and raise if a grid barrier of any step launched with this workspace gave

@@ -170,6 +170,9 @@ class Options:
         p.add_argument("--x_temperature", type=float, default=1.0)
         p.add_argument("--x_top_k", type=int, default=None)
         p.add_argument("--x_top_p", type=float, default=None, help="(ccvs_amd) nucleus sampling after top-k: inside (0, 1); None / 1.0: off")
+        p.add_argument("--x_kv_dtype", type=str, default="fp32", choices=("fp32", "bf16"),
+                       help="(ccvs_amd) element type of the token loop's KV cache; bf16 rounds keys / values when they are stored: half the "
+                            "cache bytes, sampled tokens differ from fp32's")
         p.add_argument("--x_beam_size", type=int, default=None)
         p.add_argument("--x_emb_mode", type=str, default=None)
         p.add_argument("--x_z_shape", type=int, nargs="+", default=None)
