@@ -1,8 +1,10 @@
 // Transformer kernels: embedding, LayerNorm, nn.Linear GEMM on the fp32 matrix cores,
-// KV-cached causal attention and the top-k / softmax / pick of the sampling loop.
+// the top-k / softmax / pick of the sampling loop and the decode step (KV-cached causal attention: attention.hip).
 // Reference: models/skip_vid_generator/models/mingpt.py:33-117,186-305 and
 // models/skip_vid_generator/models/transformer_model.py:256-260,395-409.
-#include "attention_kv16.h"
+#include "act_access.h"
+#include "attention.h"
+#include "attention_core.h"   // attention_decode_item, the attention phase of gpt_step_kernel
 #include "common.h"
 
 // ---------------------------------------------------------------------------------------
@@ -132,40 +134,12 @@ __device__ __forceinline__ void ln_center(f32x4& v, float c) { v[0] -= c; v[1] -
 
 // 16 bytes at descriptor `r`, per-lane byte offset `voff` + wave-uniform byte offset `soff` (buffer_load_dwordx4 ... offen)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-template <int AUX = 0>   // AUX = 16: sc1 (see below)
+template <int AUX = 0>   // AUX = 16: sc1 (see act_access.h)
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX);
     return __builtin_bit_cast(f32x4, v);
 }
 
-// ---------------------------------------------------------------------------------------
-// Agent-scope ("sc1") accesses for data that one workgroup hands to another INSIDE a launch (the persistent decode step below; the
-// split-K slabs since round 2).  Per-XCD L2s are not coherent and a CU's L1 is never refreshed by another CU's stores
-// (MI355X_MICROARCH.md, "Workgroup dispatch, XCD placement & inter-workgroup visibility"): the producer stores sc1 (write-through)
-// and drains (s_waitcnt vmcnt(0)) before its workgroup signals; EVERY consumer load of those bytes is an sc1 load (it bypasses
-// L1) issued after the consumer's poll has matched and its workgroup has passed a barrier.  COH = false: the plain access (a
-// kernel boundary orders it), so that one body serves the launch chain and the persistent kernel with identical arithmetic.
-// ---------------------------------------------------------------------------------------
-template <bool COH>
-__device__ __forceinline__ float ld_act(const float* p) {
-    if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-template <bool COH>
-__device__ __forceinline__ void st_act(float* p, float v) {
-    if constexpr (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-// threadIdx.x, opaque to the optimiser when OPAQUE: inside the persistent step's phase loop every lane-derived constant of every
-// phase body (LDS offsets, row / column maps, masks -- dozens of registers) is loop-invariant and gets hoisted in front of the loop,
-// where it stays live across all the other phases (with a 64-register cap: 19 spills, all of them such values); behind an asm
-// statement the optimiser cannot move, each body recomputes its handful of shifts and masks where it runs.
-template <bool OPAQUE>
-__device__ __forceinline__ int thread_id() {
-    int t = threadIdx.x;
-    if constexpr (OPAQUE) asm volatile("" : "+v"(t));
-    return t;
-}
 // a wave-uniform operand of the phase table, opaque to the optimiser when OPAQUE: what the tile body derives from it for its epilogue alone
 // -- the reciprocal of a divisor, (float)K -- is loop-invariant, and hoisted in front of the phase's tile loop it holds a VECTOR register
 // (integer division and conversions run on the vector ALU) across the K loop, under the persistent step's 64-register cap.
@@ -185,13 +159,6 @@ template <bool COH, typename T>
 __device__ __forceinline__ T* gp_(T* p) {
     if constexpr (COH) return (T*)(__attribute__((address_space(1))) T*)p;
     else return p;
-}
-// 16 bytes, sc1 (global_load_dwordx4 ... sc1 through a one-off buffer descriptor: aux bit 4)
-__device__ __forceinline__ f32x4 ld_act4_sc1(const float* p) {
-    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, 16, 0x00020000);
-    typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
-    const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(r, 0, 0, 16);
-    return __builtin_bit_cast(f32x4, v);
 }
 
 struct Gemm16 {
@@ -935,388 +902,6 @@ extern "C" int ccvs_gemm_tiled(const float* x, int64_t ldx, const float* w_tiled
 }
 
 // ---------------------------------------------------------------------------------------
-// KV cache append and causal attention over the cache (head dim 16 / 32 / 64).
-// Positions may come from a device-resident int32 (`pos_dev`, added to pos0) so that a decode
-// step captured in a hipGraph replays at advancing positions without re-capture.
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void kv_append_kernel(const float* __restrict__ k, const float* __restrict__ v, long sB, long ld,
-                                                        float* __restrict__ kc, float* __restrict__ vc, long total, int H, int Tq,
-                                                        int pos0, const int32_t* __restrict__ pos_dev, int Tmax, int D) {
-    if (pos_dev) pos0 += *pos_dev;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-        const int d = (int)(i % D);
-        long t = i / D;
-        const int h = (int)(t % H);
-        t /= H;
-        const int tq = (int)(t % Tq);
-        const long b = t / Tq;
-        if (pos0 + tq >= Tmax) continue;
-        const long src = b * sB + tq * ld + h * D + d;
-        const long dst = ((b * H + h) * Tmax + pos0 + tq) * D + d;
-        kc[dst] = k[src];
-        vc[dst] = v[src];
-    }
-}
-
-extern "C" int ccvs_kv_append(const float* k, const float* v, int64_t sB, int64_t ld, float* kcache, float* vcache, int32_t B, int32_t H,
-                              int32_t Tq, int32_t pos0, const int32_t* pos_dev, int32_t Tmax, int32_t D, void* stream) {
-    CCVS_REQUIRE(k && v && kcache && vcache, "ccvs_kv_append: null pointer");
-    CCVS_REQUIRE(B > 0 && H > 0 && Tq > 0 && D > 0 && pos0 >= 0 && pos0 + Tq <= Tmax, "ccvs_kv_append: positions %d..%d exceed cache %d",
-                 pos0, pos0 + Tq, Tmax);
-    const long total = (long)B * Tq * H * D;
-    hipLaunchKernelGGL(kv_append_kernel, dim3((unsigned)cdiv64(total, 256)), dim3(256), 0, (hipStream_t)stream, k, v, (long)sB, (long)ld, kcache,
-                       vcache, total, H, Tq, pos0, pos_dev, Tmax, D);
-    CCVS_CHECK_LAUNCH("ccvs_kv_append");
-    return CCVS_OK;
-}
-
-// Prefill form (Tq > 1): flash-style attention on the fp32 matrix cores (v_mfma_f32_32x32x2_f32), exact fp32 products.
-//
-// A workgroup = 4 waves = 4 blocks of 32 queries of one (batch, head); the K / V rows of the cache are walked in tiles of
-// 32 keys staged ONCE per workgroup in LDS (K transposed to [d][key], V as [key][d]) and shared by its 128 queries.
-// Per wave and key tile:
-//   S^T = K . Q^T   (A = K tile from LDS, B = the wave's Q block held in registers, pre-scaled by 1/sqrt(D)): the 32x32
-//         accumulator layout gives every lane ONE query (column lane%32) and 16 of the 32 keys, so the causal mask, the
-//         running max / sum of the online softmax and the exponentials are per-lane register work plus one xor-32 shuffle;
-//   O^T += V^T . P^T   the probabilities are used as the B operand straight from the S accumulator registers: MFMA step
-//         j contracts over the key that accumulator register j holds in each lane half (the contraction order over keys
-//         is free), and the A operand reads the matching V row from LDS -- P never moves;
-//   O is rescaled by exp(m_old - m_new) when the running max moves.
-// Query t (position pos0 + t) sees keys 0 .. pos0 + t; tiles beyond a wave's last query are skipped by that wave.  Two
-// tile buffers: tile i+1 is fetched into registers before tile i is consumed and stored after it, one barrier per tile.
-// The result goes through LDS so that it is written with lanes along the head dimension (coalesced rows of `out`).
-// Replaces the softmax(QK^T / sqrt(d) masked) V of mingpt.py:67-77 for whole sequences (prefill, teacher-forced forward,
-// the re-prefill of a slid token window).
-template <int D>
-__global__ __launch_bounds__(256) void attention_prefill_kernel(const float* __restrict__ q, long q_sB, long ldq, const float* __restrict__ kc,
-                                                                const float* __restrict__ vc, float* __restrict__ out, int H, int Tq, int pos0,
-                                                                const int32_t* __restrict__ pos_dev, int Tmax, float scale) {
-    constexpr int MT = (D + 31) / 32;   // 32-row tiles of the head dimension in O^T
-    constexpr int DP = MT * 32;         // head dimension padded to the tile (zero columns of V)
-    constexpr int DK = D / 2;           // MFMA steps of S (K = 2 per step)
-    constexpr int KS = 33;              // row stride of the transposed K tile
-    constexpr int F4 = D / 4;           // float4 per cache row
-    constexpr int NLD = (32 * F4 + 255) / 256;  // float4 per thread and tile
-    constexpr int TILE_WORDS = D * KS + 32 * DP;
-    constexpr int OUT_WORDS = 128 * (D + 1);
-    constexpr int SMEM_WORDS = 2 * TILE_WORDS > OUT_WORDS ? 2 * TILE_WORDS : OUT_WORDS;
-    __shared__ __attribute__((aligned(16))) float smem[SMEM_WORDS];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int qi = lane & 31, half = lane >> 5;
-    // grid = (batch x head, query block): blocks are dispatched x-fastest, so ALL (batch, head) pairs of the last query block
-    // -- the one with the most visible keys under the causal mask -- start first and the short blocks fill the tail
-    const int bh = blockIdx.x, b = bh / H, h = bh - b * H;
-    if (pos_dev) pos0 += *pos_dev;
-    const int q0 = (gridDim.y - 1 - blockIdx.y) * 128;     // first query of the workgroup
-    const int qw = q0 + wave * 32;                         // first query of the wave
-    const int qidx = qw + qi;                              // this lane's query
-    const int q_last_wg = min(q0 + 127, Tq - 1), q_last_w = min(qw + 31, Tq - 1);
-    const int ntiles = (min(pos0 + q_last_wg + 1, Tmax) + 31) >> 5;
-    const float* kbase = kc + (long)bh * Tmax * D;
-    const float* vbase = vc + (long)bh * Tmax * D;
-
-    // Q block of the wave: lane holds Q[qidx][2i + half], i = 0 .. DK-1 (B operand of step i)
-    float qreg[DK];
-    {
-        const float* qp = q + (long)b * q_sB + (long)min(qidx, Tq - 1) * ldq + h * D + half;
-#pragma unroll
-        // scores are kept in the log2 domain (scale * log2(e) folded into Q): the softmax then needs v_exp_f32 only
-        for (int i = 0; i < DK; ++i) qreg[i] = (qidx < Tq) ? qp[2 * i] * (scale * 1.44269504088896340736f) : 0.f;
-    }
-    if (MT * 32 > D) {  // zero the padding columns of both V buffers once (D = 16)
-        for (int e = tid; e < 2 * 32 * (DP - D); e += 256) {
-            const int bsel = e / (32 * (DP - D)), r = e - bsel * 32 * (DP - D);
-            smem[bsel * TILE_WORDS + D * KS + (r / (DP - D)) * DP + D + r % (DP - D)] = 0.f;
-        }
-    }
-
-    float4 kreg[NLD], vreg[NLD];
-    auto fetch = [&](int kt) {
-#pragma unroll
-        for (int r = 0; r < NLD; ++r) {
-            const int e = min(tid + 256 * r, 32 * F4 - 1);
-            const int key = e / F4, d4 = e - key * F4;
-            // cache rows >= pos0 + Tq have never been written: their scores are masked (select) but a 0 x NaN in the PV
-            // product would still poison the sum, so such rows are staged as zeros (and never read: the address is clamped)
-            const bool written = kt * 32 + key < pos0 + Tq;
-            const long row = min(kt * 32 + key, pos0 + Tq - 1);
-            const float4 kv = *reinterpret_cast<const float4*>(kbase + row * D + 4 * d4);
-            const float4 vv = *reinterpret_cast<const float4*>(vbase + row * D + 4 * d4);
-            kreg[r] = written ? kv : make_float4(0.f, 0.f, 0.f, 0.f);
-            vreg[r] = written ? vv : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stash = [&](int buf) {
-        float* kt_s = smem + buf * TILE_WORDS;
-        float* v_s = kt_s + D * KS;
-#pragma unroll
-        for (int r = 0; r < NLD; ++r) {
-            const int e = tid + 256 * r;
-            if (e < 32 * F4) {
-                const int key = e / F4, d4 = e - key * F4;
-                kt_s[(4 * d4 + 0) * KS + key] = kreg[r].x;
-                kt_s[(4 * d4 + 1) * KS + key] = kreg[r].y;
-                kt_s[(4 * d4 + 2) * KS + key] = kreg[r].z;
-                kt_s[(4 * d4 + 3) * KS + key] = kreg[r].w;
-                *reinterpret_cast<float4*>(v_s + key * DP + 4 * d4) = vreg[r];
-            }
-        }
-    };
-
-    f32x16 acc_o[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc_o[mt][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;
-
-    fetch(0);
-    __syncthreads();   // padding columns zeroed
-    stash(0);
-    __syncthreads();
-    for (int kt = 0; kt < ntiles; ++kt) {
-        const int buf = kt & 1;
-        if (kt + 1 < ntiles) fetch(kt + 1);
-        const int key0 = kt * 32;
-        if (key0 <= pos0 + q_last_w && qw < Tq) {   // wave-uniform: this tile holds keys visible to the wave
-            const float* kt_s = smem + buf * TILE_WORDS;
-            const float* v_s = kt_s + D * KS;
-            f32x16 s;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s[r] = 0.f;
-#pragma unroll
-            for (int i = 0; i < DK; ++i) s = __builtin_amdgcn_mfma_f32_32x32x2f32(kt_s[(2 * i + half) * KS + qi], qreg[i], s, 0, 0, 0);
-            // s[r] = S[query qidx][key key0 + 8*(r/4) + 4*half + r%4]
-            const int lim = pos0 + qidx - key0;   // keys with index <= lim are visible
-            float m_t = -INFINITY;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int kk = 8 * (r >> 2) + 4 * half + (r & 3);
-                s[r] = (kk <= lim && qidx < Tq) ? s[r] : -INFINITY;
-                m_t = fmaxf(m_t, s[r]);
-            }
-            m_t = fmaxf(m_t, __shfl_xor(m_t, 32, 64));
-            const float m_new = fmaxf(m_run, m_t);
-            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;   // nothing visible yet: every p below is 2^-inf = 0
-            const float alpha = __builtin_amdgcn_exp2f(m_run - m_use);  // m_run = -inf -> 0
-            float l_t = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                s[r] = __builtin_amdgcn_exp2f(s[r] - m_use);
-                l_t += s[r];
-            }
-            l_t += __shfl_xor(l_t, 32, 64);
-            l_run = l_run * alpha + l_t;
-            m_run = m_new;
-            const bool rescale = __any(alpha != 1.f);   // wave-uniform: the running max of no lane moved -> O keeps its scale
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                if (rescale) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc_o[mt][r] *= alpha;
-                }
-#pragma unroll
-                for (int j = 0; j < 16; ++j) {
-                    const int kk = 8 * (j >> 2) + 4 * half + (j & 3);
-                    acc_o[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(v_s[kk * DP + mt * 32 + qi], s[j], acc_o[mt], 0, 0, 0);
-                }
-            }
-        }
-        if (kt + 1 < ntiles) stash(buf ^ 1);   // the other buffer: its last readers passed the barrier of the previous tile
-        __syncthreads();
-    }
-    // O[d][query] / l  ->  LDS [query][d]  ->  out rows (lanes along d)
-    float* o_s = smem;
-    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int d = mt * 32 + 8 * (r >> 2) + 4 * half + (r & 3);
-            if (d < D) o_s[(wave * 32 + qi) * (D + 1) + d] = acc_o[mt][r] * inv;
-        }
-    __syncthreads();
-    for (int e = tid; e < 128 * D; e += 256) {
-        const int ql = e / D, d = e - ql * D;
-        if (q0 + ql < Tq) out[((long)b * Tq + q0 + ql) * (H * D) + h * D + d] = o_s[ql * (D + 1) + d];
-    }
-}
-
-// 16 bytes with the non-temporal policy (a stream read once: keys / values of a decode step)
-__device__ __forceinline__ f32x4 ld_f4_nt(const float* p) {
-    return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p));
-}
-
-// Decode form (Tq = 1): one workgroup per (batch, head) streams that head's K and V rows once.
-// A key row of D floats is read by D/4 consecutive lanes as float4 (a wave-instruction covers
-// 64/(D/4) whole rows: 1 KiB, fully coalesced); the partial dots are summed across those lanes
-// with xor shuffles.  PV uses the same lane map (lane owns 4 head dims of one key slot); the
-// key slots of a wave and the 4 waves are reduced through LDS in a fixed order.
-// Footprint (see gemm16_kernel): 256 threads, <= 48 VGPRs, LDS = scores + 4 KB -- the workgroup is dispatched next to a
-// convolution workgroup of the frame decoder instead of waiting for one to retire; a stream of this shape keeps 3.5 TB/s
-// beside the decoder (5.5 alone; tools/chain_probe.py).  Four key rows per lane are requested together (16 KB in flight
-// per workgroup); the first V batch is requested before the softmax reduction starts.
-// (bh = the (batch row, head) pair; smem = 16 + 1024 + Tmax floats.  COH: the persistent decode step -- q, the cache row of the
-//  CURRENT position (written by the QKV phase of the same launch) and the output are handed between workgroups of one launch:
-//  sc1 accesses; the older cache rows were written by earlier launches and stay on the plain / non-temporal stream.)
-template <int D, bool COH>
-__device__ __forceinline__ void attention_decode_item(const float* __restrict__ q, long q_sB, const float* __restrict__ kc,
-                                                      const float* __restrict__ vc, float* __restrict__ out, int H, int pos0,
-                                                      const int32_t* __restrict__ pos_dev, int grp_rows, int Tmax, float scale, int bh,
-                                                      float* smem) {
-    constexpr int LPK = D / 4;     // lanes per key row
-    constexpr int KPI = 64 / LPK;  // key rows per wave-instruction
-    constexpr int NW = 4;
-    constexpr int AU = 4;          // key rows per lane whose loads are issued together
-    constexpr int BATCH = NW * KPI * AU;
-    float* red = smem;                    // [16]
-    float* pv = smem + 16;                // [NW][64][4]
-    float* ps = smem + 16 + NW * 256;     // [Tmax]
-    const int tid = thread_id<COH>(), lane = tid & 63, wave = tid >> 6;
-    const int b = bh / H, h = bh - b * H;
-    if (pos_dev) {   // row groups of a decode step: one cache length per group
-        // (COH: the length words are constant for the whole launch until the pick's last row moves them on, after every other reader:
-        //  a SCALAR load through the constant address space -- as a vector load of a uniform address the value, and with it the
-        //  loop bounds and row addresses, is per-lane data to the compiler)
-        if constexpr (COH) pos0 += ((const __attribute__((address_space(4))) int32_t*)pos_dev)[grp_rows > 0 ? b / grp_rows : 0];
-        else pos0 += pos_dev[grp_rows > 0 ? b / grp_rows : 0];
-    }
-    const int L = min(pos0 + 1, Tmax);
-    const int kk = lane / LPK, d4 = lane - kk * LPK;
-    const float* kbase = kc + (long)bh * Tmax * D + 4 * d4;
-    const float* vbase = vc + (long)bh * Tmax * D + 4 * d4;
-    const int jw = wave * KPI + kk;  // this lane's row within a batch, + u * NW * KPI
-    const int nbatch = (L + BATCH - 1) / BATCH;
-
-    // unconditional loads from clamped rows (predicated loads would serialise)
-    // COH: rows >= L - 1 (the position this step appends, and the clamped tail of the last batch) take the row fetched by ONE sc1
-    // load instead of whatever the streaming load of that address returned -- same values, same arithmetic, no stale line
-    f32x4 k_new = {0.f, 0.f, 0.f, 0.f}, v_new = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (COH) {
-        k_new = ld_act4_sc1(kbase + (long)(L - 1) * D);
-        v_new = ld_act4_sc1(vbase + (long)(L - 1) * D);
-    }
-#define ATT_LOAD(dst, base, bi, fresh)                                                                                   \
-    _Pragma("unroll") for (int u = 0; u < AU; ++u) {                                                                     \
-        dst[u] = ld_f4_nt(base + (long)min((bi) * BATCH + jw + u * NW * KPI, L - 1) * D);                                \
-        if constexpr (COH) { if ((bi) * BATCH + jw + u * NW * KPI >= L - 1) dst[u] = fresh; }                            \
-    }
-
-    float4 qv;
-    if constexpr (COH) {
-        const f32x4 q4 = ld_act4_sc1(q + (long)b * q_sB + h * D + 4 * d4);
-        qv = make_float4(q4[0], q4[1], q4[2], q4[3]);
-    } else {
-        qv = *reinterpret_cast<const float4*>(q + (long)b * q_sB + h * D + 4 * d4);
-    }
-    float lmax = -INFINITY;
-#pragma unroll 1   // (one batch of AU rows in flight per lane: the 48-register budget; hipcc unrolls this loop by two once the body is an inlined function)
-    for (int bi = 0; bi < nbatch; ++bi) {
-        f32x4 kv[AU];
-        ATT_LOAD(kv, kbase, bi, k_new);
-#pragma unroll
-        for (int u = 0; u < AU; ++u) {
-            const int j = bi * BATCH + jw + u * NW * KPI;
-            float s = kv[u][0] * qv.x + kv[u][1] * qv.y + kv[u][2] * qv.z + kv[u][3] * qv.w;
-#pragma unroll
-            for (int o = 1; o < LPK; o <<= 1) s += __shfl_xor(s, o, 64);
-            s *= scale;
-            if (j < L) {
-                if (d4 == 0) ps[j] = s;
-                lmax = fmaxf(lmax, s);
-            }
-        }
-    }
-    f32x4 vv[AU];
-    ATT_LOAD(vv, vbase, 0, v_new);  // in flight during the softmax reductions
-
-    lmax = wave_max(lmax);
-    if (lane == 0) red[wave] = lmax;
-    __syncthreads();
-    float gmax = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) gmax = fmaxf(gmax, red[w]);
-    float lsum = 0.f;
-    for (int j = tid; j < L; j += NW * 64) {
-        const float e = expf(ps[j] - gmax);
-        ps[j] = e;
-        lsum += e;
-    }
-    lsum = wave_sum(lsum);
-    __syncthreads();
-    if (lane == 0) red[wave] = lsum;
-    __syncthreads();
-    float tot = red[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) tot += red[w];
-
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 1
-    for (int bi = 0; bi < nbatch; ++bi) {
-        if (bi > 0) ATT_LOAD(vv, vbase, bi, v_new);
-#pragma unroll
-        for (int u = 0; u < AU; ++u) {
-            const int j = bi * BATCH + jw + u * NW * KPI;
-            const float p = (j < L) ? ps[min(j, L - 1)] : 0.f;
-            acc.x += p * vv[u][0]; acc.y += p * vv[u][1]; acc.z += p * vv[u][2]; acc.w += p * vv[u][3];
-        }
-    }
-#undef ATT_LOAD
-    *reinterpret_cast<float4*>(pv + (wave * 64 + lane) * 4) = acc;
-    __syncthreads();
-    if (tid < D) {
-        const int dd4 = tid >> 2, comp = tid & 3;
-        float o = 0.f;
-        for (int w = 0; w < NW; ++w)
-            for (int s2 = 0; s2 < KPI; ++s2) o += pv[(w * 64 + s2 * LPK + dd4) * 4 + comp];
-        st_act<COH>(out + (long)b * (H * D) + h * D + tid, o / tot);
-    }
-}
-
-template <int D>
-__global__ __launch_bounds__(256) void attention_decode_kernel(const float* __restrict__ q, long q_sB, const float* __restrict__ kc,
-                                                               const float* __restrict__ vc, float* __restrict__ out, int H, int pos0,
-                                                               const int32_t* __restrict__ pos_dev, int grp_rows, int Tmax, float scale) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    attention_decode_item<D, false>(q, q_sB, kc, vc, out, H, pos0, pos_dev, grp_rows, Tmax, scale, blockIdx.x, smem);
-}
-
-// one workgroup per (batch row, head), `smem` bytes of LDS for the scores; the caller checks the launch under its own name
-static void launch_attention_decode(int D, int n_bh, size_t smem, hipStream_t st, const float* q, long q_sB, const float* kc, const float* vc,
-                                    float* out, int H, int pos0, const int32_t* pos_dev, int grp_rows, int Tmax, float scale) {
-#define ATT_DECODE_LAUNCH(Dv) \
-    hipLaunchKernelGGL((attention_decode_kernel<Dv>), dim3((unsigned)n_bh), dim3(256), smem, st, q, q_sB, kc, vc, out, H, pos0, pos_dev, grp_rows, Tmax, scale)
-    if (D == 64) ATT_DECODE_LAUNCH(64);
-    else if (D == 32) ATT_DECODE_LAUNCH(32);
-    else ATT_DECODE_LAUNCH(16);
-#undef ATT_DECODE_LAUNCH
-}
-
-extern "C" int ccvs_attention(const float* q, int64_t q_sB, int64_t ldq, const float* kcache, const float* vcache, float* out, int32_t B,
-                              int32_t H, int32_t Tq, int32_t pos0, const int32_t* pos_dev, int32_t Tmax, int32_t D, void* stream) {
-    CCVS_REQUIRE(q && kcache && vcache && out, "ccvs_attention: null pointer");
-    CCVS_REQUIRE(D == 64 || D == 32 || D == 16, "ccvs_attention: head dim %d unsupported (16, 32, 64)", D);
-    CCVS_REQUIRE(B > 0 && H > 0 && Tq > 0 && pos0 >= 0 && pos0 + Tq <= Tmax, "ccvs_attention: bad positions");
-    CCVS_REQUIRE(cdiv(Tq, 128) <= 65535, "ccvs_attention: %d queries too many for one launch", Tq);
-    // with a device-side position the visible length is unknown to the host: size LDS for the whole cache
-    const int maxL = pos_dev ? Tmax : pos0 + Tq;
-    const float scale = 1.0f / sqrtf((float)D);
-    hipStream_t st = (hipStream_t)stream;
-    if (Tq == 1) {
-        const size_t smem = (size_t)(16 + 4 * 256 + maxL) * sizeof(float);
-        CCVS_REQUIRE(smem <= 64 * 1024, "ccvs_attention: sequence too long for the LDS score buffer");
-        launch_attention_decode(D, B * H, smem, st, q, (long)q_sB, kcache, vcache, out, H, pos0, pos_dev, 0, Tmax, scale);
-    } else {
-        const dim3 grid((unsigned)(B * H), (unsigned)cdiv(Tq, 128));
-        if (D == 64) hipLaunchKernelGGL((attention_prefill_kernel<64>), grid, dim3(256), 0, st, q, (long)q_sB, (long)ldq, kcache, vcache, out, H, Tq, pos0, pos_dev, Tmax, scale);
-        else if (D == 32) hipLaunchKernelGGL((attention_prefill_kernel<32>), grid, dim3(256), 0, st, q, (long)q_sB, (long)ldq, kcache, vcache, out, H, Tq, pos0, pos_dev, Tmax, scale);
-        else hipLaunchKernelGGL((attention_prefill_kernel<16>), grid, dim3(256), 0, st, q, (long)q_sB, (long)ldq, kcache, vcache, out, H, Tq, pos0, pos_dev, Tmax, scale);
-    }
-    CCVS_CHECK_LAUNCH("ccvs_attention");
-    return CCVS_OK;
-}
-
-// ---------------------------------------------------------------------------------------
 // get_icode: temperature, top-k mask (ties with the k-th value kept), softmax, then
 // argmax(p) (greedy) or argmax(p / Exp(1) noise) (== torch.multinomial(p, 1)).
 // One workgroup per row; the k-th largest value is found by a 32-step radix descent on
@@ -1958,7 +1543,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
             float* att = as_global(g.y);
             const int32_t* len = as_global(g.pos_dev);
             for (int bh = blockIdx.x; bh < n_bh; bh += G) {   // attention over the cache
-                attention_decode_item<D, true>(q, q_sB, kc, vc, att, H, 0, len, grp_rows, Tmax, att_scale, bh, smem);
+                attention_decode_item<D, KvF32, true>(q, q_sB, nullptr, nullptr, 0, kc, vc, att, H, 0, len, grp_rows, Tmax, att_scale, bh, smem);
                 __syncthreads();
             }
         } else {
@@ -2223,11 +1808,9 @@ static int decode_step(const ccvs_gpt_decode* d, void* stream, bool kv16) {
     const float scale = 1.0f / sqrtf((float)D);
     const int rc = step_phases(d, who, [&](int kind, Gemm16& g, const char* name) -> int {
         if (kind == STEP_GEMM) return launch_gemm16(g, st, name);
-        if (kv16)   // the appending form: K and V of this position are columns C.. and 2C.. of the QKV output
-            ccvs_kv16_launch_attention_decode(D, g.M * g.H, smem_att, st, g.x, g.ldx, g.x + d->C, g.x + 2 * d->C, g.ldx, (uint16_t*)g.kcache,
-                                              (uint16_t*)g.vcache, g.y, g.H, 0, g.pos_dev, g.grp_rows, g.Tmax, scale);
-        else
-            launch_attention_decode(D, g.M * g.H, smem_att, st, g.x, g.ldx, g.kcache, g.vcache, g.y, g.H, 0, g.pos_dev, g.grp_rows, g.Tmax, scale);
+        // bf16 caches, the appending form: K and V of this position are columns C.. and 2C.. of the QKV output
+        ccvs_launch_attention_decode(kv16, D, g.M * g.H, smem_att, st, g.x, g.ldx, kv16 ? g.x + d->C : nullptr, kv16 ? g.x + 2 * d->C : nullptr,
+                                     g.ldx, g.kcache, g.vcache, g.y, g.H, 0, g.pos_dev, g.grp_rows, g.Tmax, scale);
         CCVS_CHECK_LAUNCH(name);
         return CCVS_OK;
     }, kv16);

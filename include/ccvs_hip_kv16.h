@@ -1,4 +1,4 @@
-/* The token loop on a bfloat16 KV cache (opt-in: `--x_kv_dtype bf16`; ccvs_amd/csrc/attention_kv16.hip, the entry of the step in gpt.hip).
+/* The token loop on a bfloat16 KV cache (opt-in: `--x_kv_dtype bf16`; ccvs_amd/csrc/attention.hip, the entry of the step in gpt.hip).
  * Included by ccvs_hip.h.
  *
  * THE MODE.  Every key and value row is rounded to bfloat16 when it is appended to the cache: round to nearest, ties to even, on the

@@ -1,4 +1,4 @@
-"""Float64 reference of the KV-cached causal attention (`ccvs_attention`, gpt.hip) with a derived per-element error bound, the
+"""Float64 reference of the KV-cached causal attention (`ccvs_attention`, attention.hip) with a derived per-element error bound, the
 wrong references that the bound has to tell from the right one, and the score patterns shared by the host and the GPU tests.
 Plain torch, runs anywhere.
 

@@ -1,5 +1,5 @@
-"""-m gpu: both forms of the KV-cached causal attention (`attention_prefill_kernel<16|32|64>`, `attention_decode_kernel<16|32|64>`,
-gpt.hip) through `ops.attention`, against the float64 reference and the derived per-element bound of tests/attention_ref.py
+"""-m gpu: both forms of the KV-cached causal attention (`attention_prefill_kernel<16|32|64, KvF32>`, `attention_decode_kernel<16|32|64>`,
+ccvs_amd/csrc/attention.hip; their bodies in attention_core.h, shared with the bf16 caches) through `ops.attention`, against the float64 reference and the derived per-element bound of tests/attention_ref.py
 (what the bound can and cannot tell apart is tests/test_attention_ref_host.py).
 
 Every case has B = 2 and H = 3 (H is no power of two: b = bh / H matters), q is the middle third of a [B, Tq, 3*H*D] buffer whose
@@ -54,7 +54,7 @@ def ops():
 
 
 def decode_batch(d):
-    """Rows per register batch of attention_decode_item, from its own constants; the values are pinned so that a change of the
+    """Rows per register batch of attention_decode_item<D, KvF32, COH> (attention_core.h), from its own constants; the values are pinned so that a change of the
     kernel's batching fails here instead of silently moving the edges out of the sweep."""
     lpk = d // 4            # lanes per key row
     kpi = 64 // lpk         # key rows per wave-instruction

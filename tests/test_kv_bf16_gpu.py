@@ -1,4 +1,5 @@
-"""-m gpu: the kernels of the bf16 KV-cache mode (ccvs_amd/csrc/attention_kv16.hip) through `ops.kv_append_bf16` and
+"""-m gpu: the kernels of the bf16 KV-cache mode (ccvs_amd/csrc/attention.hip: `kv_append_bf16_kernel`, `attention_prefill_kernel<D, KvBf16>`,
+`attention_decode_bf16_kernel<D>`; their bodies, shared with the fp32 kernels, in ccvs_amd/csrc/attention_core.h) through `ops.kv_append_bf16` and
 `ops.attention_bf16`, against tests/kv_bf16_ref.py: stored bits against the integer rounding, outputs against the float64 attention over
 the ROUNDED cache within the derived per-element bound of tests/attention_ref.py (a bf16 value is an exact fp32 value: the bound holds
 unchanged).  Geometry and poisoning are those of tests/test_attention_forms_gpu.py: B = 2, H = 3, q the middle third of a NaN-filled
@@ -17,7 +18,8 @@ unchanged).  Geometry and poisoning are those of tests/test_attention_forms_gpu.
   CU budget       each launch form once under a stream CU mask into poisoned outputs: same results as unmasked.
   dtype guards    a mixed-dtype call raises ValueError and writes nothing.
 
-MUTATIONS of attention_kv16.hip, each built once by hand into a library of its own and run against this file and
+MUTATIONS of the kernels (then in a file of their own, attention_kv16.hip; the statements are the ones attention_core.h holds for the bf16
+policy), each built once by hand into a library of its own and run against this file and
 tests/test_kv_bf16_step_gpu.py on an MI355X (41 tests; none is committed):
   * truncation instead of round-to-nearest-even (`bf16_rne` returns u >> 16): 31 fail -- append (the stored bits), the decode sweep (the
     appended rows are not the reference rounding), every test that attends through the appending form, and in the step file the layer-0
@@ -58,7 +60,8 @@ def ops():
 
 
 def decode_batch(d):
-    """Rows per register batch of attention_decode_bf16_kernel, from its own constants (EPL = 8 head dims per lane); pinned so that a
+    """Rows per register batch of attention_decode_item<D, KvBf16, false> (attention_decode_bf16_kernel), from its own constants (EPL = 8
+    head dims per lane, AU = 4 rows in flight); pinned so that a
     change of the kernel's batching fails here instead of silently moving the edges out of the sweep."""
     epl = 8
     lpk = d // epl          # lanes per key row

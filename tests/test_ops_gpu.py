@@ -594,7 +594,7 @@ def test_gpt_embed_clamp_offsets_and_column_view(ops, C):
 
 
 def test_kv_append_strided_views_at_a_device_position(ops):
-    """kv_append_kernel: Tq = 5 rows of the K and V thirds of a [B,Tq,3*H*D] QKV buffer land at pos0 + *pos_dev of both caches
+    """kv_append_kernel (attention.hip): Tq = 5 rows of the K and V thirds of a [B,Tq,3*H*D] QKV buffer land at pos0 + *pos_dev of both caches
     bit for bit, and nothing else of the sentinel-filled caches changes."""
     g = torch.Generator().manual_seed(5)
     B, H, D, Tq, Tmax, pos0, pdev = 2, 3, 16, 5, 23, 4, 9
@@ -996,7 +996,7 @@ def test_gemm_row_blocked_matches_plain(ops):
 @pytest.mark.parametrize("D,B,H,Tq,pos0", [(64, 16, 16, 1024, 0), (64, 2, 3, 301, 0), (64, 2, 2, 97, 200), (32, 3, 2, 130, 5), (16, 2, 2, 33, 0),
                                            (16, 1, 2, 2, 62)])
 def test_attention_prefill_mfma(ops, D, B, H, Tq, pos0):
-    """Flash-style prefill attention on the fp32 matrix cores (attention_prefill_kernel) against softmax(QK^T / sqrt(d)
+    """Flash-style prefill attention on the fp32 matrix cores (attention_prefill_kernel<D, KvF32>, attention_core.h) against softmax(QK^T / sqrt(d)
     masked) V of mingpt.py:67-77: the BAIR-size case T = 1024, D = 64, B = 16; ragged query counts (not multiples of the
     32-query wave block / 128-query workgroup); queries that start at a cache offset (extend); the unwritten tail of the
     cache filled with NaN must not leak into the result."""
