@@ -126,9 +126,13 @@ __device__ void gif_box_stats(GifCutLds& s, const unsigned long long* cnt, int b
     }
 }
 
-__global__ __launch_bounds__(GIF_CUT_THREADS) void gif_cut_kernel(GifPalArgs a) {
+// `cap`: the median cut stops at so many boxes (2 .. 256).  CAPPED = false: at 256 whatever `cap` says -- the constant keeps this
+// instantiation, which max_colours = 256 launches, instruction for instruction the kernel from before the argument
+template <bool CAPPED>
+__global__ __launch_bounds__(GIF_CUT_THREADS) void gif_cut_kernel(GifPalArgs a, int cap) {
     __shared__ GifCutLds s;
     const int tid = threadIdx.x;
+    const int max_boxes = CAPPED ? cap : 256;
     for (int clip = blockIdx.x; clip < a.b; clip += gridDim.x) {
         const unsigned long long* cnt = a.hist + (long)clip * 4 * GIF_NBINS;
         {
@@ -142,7 +146,7 @@ __global__ __launch_bounds__(GIF_CUT_THREADS) void gif_cut_kernel(GifPalArgs a) 
         __syncthreads();
         gif_box_stats(s, cnt, 0);
         int nbox = 1;
-        while (nbox < 256) {
+        while (nbox < max_boxes) {
             if (tid < WAVE) {                                   // the box with the largest population x longest extent, the lowest of equals
                 unsigned long long best = 0;
                 int which = -1;
@@ -395,9 +399,8 @@ extern "C" long ccvs_gif_stream_bound(int n, int h, int w, int band_rows) {
                      clip_stride, (t - 1) * frame_stride + 3L * w * h);                                                              \
     } while (0)
 
-extern "C" int ccvs_gif_palette(const uint8_t* clips, long clip_stride, long frame_stride, int b, int t, int h, int w, uint8_t* palette,
-                                uint8_t* table, int* used, void* workspace, void* hip_stream) {
-    const char* who = "ccvs_gif_palette";
+static int gif_palette_launch(const char* who, const uint8_t* clips, long clip_stride, long frame_stride, int b, int t, int h, int w,
+                              int max_colours, uint8_t* palette, uint8_t* table, int* used, void* workspace, void* hip_stream) {
     GIF_REQUIRE_CLIPS(who);
     CCVS_REQUIRE(clips && palette && table && used && workspace, "%s: null clips, palette, table, used or workspace", who);
     GifPalArgs a;
@@ -412,9 +415,22 @@ extern "C" int ccvs_gif_palette(const uint8_t* clips, long clip_stride, long fra
     }
     const long items = (((long)h * w + GIF_HIST_RUN - 1) / GIF_HIST_RUN) * t * b;
     hipLaunchKernelGGL(gif_bins_kernel, dim3(strided_grid(items, hip_stream, 8)), dim3(GIF_THREADS), 0, st, a);
-    hipLaunchKernelGGL(gif_cut_kernel, dim3(limited_grid(b, hip_stream, 1)), dim3(GIF_CUT_THREADS), 0, st, a);
+    hipLaunchKernelGGL(max_colours == 256 ? gif_cut_kernel<false> : gif_cut_kernel<true>, dim3(limited_grid(b, hip_stream, 1)),
+                       dim3(GIF_CUT_THREADS), 0, st, a, max_colours);
     CCVS_CHECK_LAUNCH(who);
     return CCVS_OK;
+}
+
+extern "C" int ccvs_gif_palette(const uint8_t* clips, long clip_stride, long frame_stride, int b, int t, int h, int w, uint8_t* palette,
+                                uint8_t* table, int* used, void* workspace, void* hip_stream) {
+    return gif_palette_launch("ccvs_gif_palette", clips, clip_stride, frame_stride, b, t, h, w, 256, palette, table, used, workspace, hip_stream);
+}
+
+extern "C" int ccvs_gif_palette_n(const uint8_t* clips, long clip_stride, long frame_stride, int b, int t, int h, int w, int max_colours,
+                                  uint8_t* palette, uint8_t* table, int* used, void* workspace, void* hip_stream) {
+    const char* who = "ccvs_gif_palette_n";
+    CCVS_REQUIRE(max_colours >= 2 && max_colours <= 256, "%s: max_colours %d outside 2 .. 256", who, max_colours);
+    return gif_palette_launch(who, clips, clip_stride, frame_stride, b, t, h, w, max_colours, palette, table, used, workspace, hip_stream);
 }
 
 extern "C" int ccvs_gif_encode(const uint8_t* clips, long clip_stride, long frame_stride, int b, int t, int h, int w, int band_rows,
@@ -444,6 +460,272 @@ extern "C" int ccvs_gif_encode(const uint8_t* clips, long clip_stride, long fram
     hipLaunchKernelGGL(gif_code_kernel, dim3(limited_grid(a.T, hip_stream, 4)), dim3(WAVE), 0, st, a);
     hipLaunchKernelGGL(gif_scan_kernel, dim3(1), dim3(GIF_THREADS), 0, st, a);
     hipLaunchKernelGGL(gif_stitch_kernel, dim3(limited_grid(per_frame * a.n, hip_stream, 8)), dim3(GIF_THREADS), 0, st, a, per_frame);
+    CCVS_CHECK_LAUNCH(who);
+    return CCVS_OK;
+}
+
+// ---- changed-rectangle frames (include/ccvs_hip_output_gif_delta.h).  Candidate 2 f of frame f is the full
+// frame, candidate 2 f + 1 the rectangle of what changed against the frame before (none for a clip's first frame); each has the
+// full frame's number of band slots, of which a rectangle uses its own first ones.
+//   rect     a workgroup per frame: the bounding rectangle of the indices that differ from the frame before;
+//   code     a wave per band of a candidate, over its rectangle; the rectangle's unchanged indices are GIF_TRANSPARENT;
+//   scan     per frame the shorter candidate, its rectangle and size; the frames' offsets;
+//   stitch   as above, of the chosen candidate's words.
+struct GifDeltaArgs {
+    const uint8_t* clips;
+    long clip_stride, frame_stride;
+    int t, n, h, w, band_rows, nb;   // band_rows as the caller gave it (0: by each rectangle's width); nb: band slots per candidate
+    long wstride;
+    const uint8_t* table;
+    uint8_t* stream;
+    long capacity;
+    long* offsets;
+    int* rects;                      // [n][4] the written candidate's x0, y0, rw, rh
+    int* drect;                      // [n][4] the changed rectangle (frames after a clip's first)
+    int* choice;                     // [n] 1: the rectangle is written
+    long* bitoff;                    // [2 n][nb + 1]
+    long* fsize;                     // [n]
+    unsigned* words;                 // [2 n][nb][wstride]
+};
+
+__device__ __forceinline__ const uint8_t* gif_frame(const GifDeltaArgs& a, long f) {
+    return a.clips + (f / a.t) * a.clip_stride + (f % a.t) * a.frame_stride;
+}
+__device__ __forceinline__ GifRect gif_candidate_rect(const GifDeltaArgs& a, long cand) {
+    if (!(cand & 1)) return gif_full_rect(a.h, a.w);
+    const int* r = a.drect + 4 * (cand >> 1);
+    GifRect out = {r[0], r[1], r[2], r[3]};
+    return out;
+}
+// ... for a wave that codes one band: named wave-uniform, so that the band's arithmetic stays on the scalar unit
+__device__ __forceinline__ GifRect gif_uniform_rect(const GifRect& r) {
+    GifRect out = {(int)GIF_U(r.x0), (int)GIF_U(r.y0), (int)GIF_U(r.rw), (int)GIF_U(r.rh)};
+    return out;
+}
+
+__global__ __launch_bounds__(GIF_THREADS) void gif_rect_kernel(GifDeltaArgs a) {
+    __shared__ int s_box[GIF_THREADS / WAVE][4];
+    const long hw = (long)a.h * a.w;
+    const long items = (hw + GIF_HIST_RUN - 1) / GIF_HIST_RUN;
+    for (long f = blockIdx.x; f < a.n; f += gridDim.x) {
+        if (f % a.t == 0) continue;                             // (the same in every thread)
+        const uint8_t* cur = gif_frame(a, f);
+        const uint8_t* prev = gif_frame(a, f - 1);
+        const uint8_t* table = a.table + (f / a.t) * GIF_NBINS;
+        int x_min = a.w, x_max = -1, y_min = a.h, y_max = -1;
+        for (long it = threadIdx.x; it < items; it += GIF_THREADS) {
+            const long p0 = it * GIF_HIST_RUN, p1 = p0 + GIF_HIST_RUN < hw ? p0 + GIF_HIST_RUN : hw;
+            int y = (int)(p0 / a.w), x = (int)(p0 % a.w);
+            for (long p = p0; p < p1; ++p) {
+                if (table[gif_bin(cur + 3 * p)] != table[gif_bin(prev + 3 * p)]) {
+                    x_min = min(x_min, x);
+                    x_max = max(x_max, x);
+                    y_min = min(y_min, y);
+                    y_max = max(y_max, y);
+                }
+                if (++x == a.w) {
+                    x = 0;
+                    ++y;
+                }
+            }
+        }
+#pragma unroll
+        for (int o = WAVE / 2; o > 0; o >>= 1) {
+            x_min = min(x_min, __shfl_xor(x_min, o, WAVE));
+            x_max = max(x_max, __shfl_xor(x_max, o, WAVE));
+            y_min = min(y_min, __shfl_xor(y_min, o, WAVE));
+            y_max = max(y_max, __shfl_xor(y_max, o, WAVE));
+        }
+        if (threadIdx.x % WAVE == 0) {
+            int* box = s_box[threadIdx.x / WAVE];
+            box[0] = x_min; box[1] = x_max; box[2] = y_min; box[3] = y_max;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int k = 1; k < GIF_THREADS / WAVE; ++k) {
+                x_min = min(x_min, s_box[k][0]);
+                x_max = max(x_max, s_box[k][1]);
+                y_min = min(y_min, s_box[k][2]);
+                y_max = max(y_max, s_box[k][3]);
+            }
+            const GifRect r = gif_changed_rect(x_min, x_max, y_min, y_max);
+            int* out = a.drect + 4 * f;
+            out[0] = r.x0; out[1] = r.y0; out[2] = r.rw; out[3] = r.rh;
+        }
+        __syncthreads();                                        // the LDS is the next frame's too
+    }
+}
+
+// code: a wave per band slot of a candidate
+__global__ __launch_bounds__(WAVE) void gif_code_rect_kernel(GifDeltaArgs a) {
+    __shared__ unsigned s_hash[GIF_SLOTS];
+    __shared__ uint8_t s_idx[GIF_CHUNK];
+    const int lane = threadIdx.x;
+    const long units = 2L * a.n * a.nb;
+    for (long unit = blockIdx.x; unit < units; unit += gridDim.x) {
+        const long cand = unit / a.nb, f = cand >> 1;
+        const int b = (int)(unit % a.nb);
+        const bool mask = cand & 1;                             // against the frame before
+        if (mask && f % a.t == 0) continue;                     // (every `continue` is the same in every lane)
+        const GifRect r = gif_uniform_rect(gif_candidate_rect(a, cand));
+        const int nbr = (int)gif_bands(r.rh, r.rw, a.band_rows);
+        if (b >= nbr) continue;
+        const int r0 = gif_rect_band_first(r, a.band_rows, b);
+        const long L = (long)gif_rect_band_count(r, a.band_rows, b) * r.rw;
+        const uint8_t* src = gif_frame(a, f);
+        const uint8_t* table = a.table + (f / a.t) * GIF_NBINS;
+        for (int i = lane; i < GIF_SLOTS; i += WAVE) s_hash[i] = GIF_EMPTY;
+        GifCoder s;
+        gif_start(s, a.words + unit * a.wstride, b == 0, lane == 0);
+        for (long c0 = 0; c0 < L; c0 += GIF_CHUNK) {
+            const int n = (int)(L - c0 < GIF_CHUNK ? L - c0 : GIF_CHUNK);
+            __syncthreads();                                    // the chunk before is coded, the hash is empty
+            for (int i = lane; i < n; i += WAVE) {
+                const long p = gif_rect_pixel(r, a.w, r0, c0 + i);
+                uint8_t v = table[gif_bin(src + 3 * p)];
+                if (mask && table[gif_bin(src - a.frame_stride + 3 * p)] == v) v = GIF_TRANSPARENT;
+                s_idx[i] = v;
+            }
+            __syncthreads();
+            int pos = 0;
+            while (pos < n) {
+                pos += gif_code(s, s_hash, s_idx + pos, n - pos);
+                if (s.full) {                                   // (the same in every lane)
+                    __syncthreads();
+                    for (int i = lane; i < GIF_SLOTS; i += WAVE) s_hash[i] = GIF_EMPTY;
+                    __syncthreads();
+                    s.full = 0;
+                }
+            }
+        }
+        const long bits = gif_finish(s, b == nbr - 1);
+        if (lane == 0) a.bitoff[cand * (a.nb + 1) + b + 1] = bits;
+        __syncthreads();
+    }
+}
+
+// a candidate's band sizes turned into bit positions; returns its payload's bytes
+__device__ __forceinline__ long gif_scan_candidate(const GifDeltaArgs& a, long cand, const GifRect& r) {
+    const int nbr = (int)gif_bands(r.rh, r.rw, a.band_rows);
+    long* off = a.bitoff + cand * (a.nb + 1);
+    long run = 0;
+    off[0] = 0;
+    for (int b = 1; b <= nbr; ++b) {
+        run += off[b];
+        off[b] = run;
+    }
+    return gif_payload_bytes((run + 7) >> 3);
+}
+
+// scan: one workgroup.  Per frame both candidates' band positions and payload sizes, the choice and its rectangle; then the offsets
+__global__ __launch_bounds__(GIF_THREADS) void gif_scan_delta_kernel(GifDeltaArgs a) {
+    __shared__ long s_sum[GIF_THREADS];
+    const int tid = threadIdx.x;
+    for (long f = tid; f < a.n; f += GIF_THREADS) {
+        GifRect rect = gif_full_rect(a.h, a.w);
+        long size = gif_scan_candidate(a, 2 * f, rect);
+        int pick = 0;
+        if (f % a.t != 0) {
+            const GifRect drect = gif_candidate_rect(a, 2 * f + 1);
+            const long dsize = gif_scan_candidate(a, 2 * f + 1, drect);
+            if (dsize < size) {
+                pick = 1;
+                size = dsize;
+                rect = drect;
+            }
+        }
+        a.choice[f] = pick;
+        a.fsize[f] = size;
+        int* out = a.rects + 4 * f;
+        out[0] = rect.x0; out[1] = rect.y0; out[2] = rect.rw; out[3] = rect.rh;
+    }
+    __syncthreads();
+    const long chunk = (a.n + GIF_THREADS - 1) / GIF_THREADS;
+    const long i0 = tid * chunk < a.n ? tid * chunk : a.n;
+    const long i1 = i0 + chunk < a.n ? i0 + chunk : a.n;
+    long sum = 0;
+    for (long i = i0; i < i1; ++i) sum += a.fsize[i];
+    s_sum[tid] = sum;
+    __syncthreads();
+    long run = 0, total = 0;
+    for (int j = 0; j < GIF_THREADS; ++j) {
+        const long c = s_sum[j];
+        run += j < tid ? c : 0;
+        total += c;
+    }
+    for (long i = i0; i < i1; ++i) {
+        a.offsets[i] = run;
+        run += a.fsize[i];
+    }
+    if (tid == 0) a.offsets[a.n] = total;
+}
+
+__global__ __launch_bounds__(GIF_THREADS) void gif_stitch_delta_kernel(GifDeltaArgs a, long per_frame) {
+    const long blocks = per_frame * a.n;
+    for (long blk = blockIdx.x; blk < blocks; blk += gridDim.x) {
+        const long f = blk / per_frame;
+        const long j = (blk % per_frame) * GIF_THREADS + threadIdx.x;
+        const long cand = 2 * f + a.choice[f];
+        const int* r = a.rects + 4 * f;
+        const int nbr = (int)gif_bands(r[3], r[2], a.band_rows);
+        const long* bitoff = a.bitoff + cand * (a.nb + 1);
+        const long data = (bitoff[nbr] + 7) >> 3;
+        if (j >= data) continue;
+        const long base = a.offsets[f];
+        const unsigned byte = gif_data_byte(a.words + cand * a.nb * a.wstride, a.wstride, bitoff, nbr, j);
+        const auto store = [&](long pos, unsigned v) {
+            if (pos < a.capacity) a.stream[pos] = (uint8_t)v;
+        };
+        store(base + gif_data_pos(j), byte);
+        if (j % 255 == 0) store(base + gif_data_pos(j) - 1, gif_block_len(data, j));
+        if (j == 0) store(base, 8u);                            // the LZW minimum code size
+        if (j == data - 1) store(base + gif_payload_bytes(data) - 1, 0u);
+    }
+}
+
+// the workspace behind the palette's bins: the changed rectangles, the choices, both candidates' band positions, the frames' sizes, the
+// bands' bits
+static inline size_t gif_delta_tables_bytes(size_t n, size_t nb) { return n * 16 + gif_align8(n * 4) + 2 * n * (nb + 1) * 8 + n * 8; }
+
+extern "C" size_t ccvs_gif_delta_workspace_bytes(int b, int t, int h, int w, int band_rows) {
+    if (b < 1 || t < 1 || !gif_shape_ok((long)b * t, h, w, band_rows)) return 0;
+    const size_t n = (size_t)b * t, nb = (size_t)gif_bands(h, w, band_rows);
+    return (size_t)b * 4 * GIF_NBINS * 8 + gif_delta_tables_bytes(n, nb) +
+           gif_align8(2 * n * nb * (size_t)gif_band_words(gif_rect_band_max(h, w, band_rows)) * 4);
+}
+
+extern "C" int ccvs_gif_encode_delta(const uint8_t* clips, long clip_stride, long frame_stride, int b, int t, int h, int w, int band_rows,
+                                     const uint8_t* table, uint8_t* stream, long capacity, long* offsets, int* rects, void* workspace,
+                                     void* hip_stream) {
+    const char* who = "ccvs_gif_encode_delta";
+    GIF_REQUIRE_CLIPS(who);
+    CCVS_REQUIRE(band_rows >= 0, "%s: band_rows %d is negative", who, band_rows);
+    CCVS_REQUIRE(gif_shape_ok((long)b * t, h, w, band_rows), "%s: band_rows %d makes a band of 2^24 indices or more", who, band_rows);
+    CCVS_REQUIRE(capacity >= 0, "%s: negative capacity", who);
+    CCVS_REQUIRE(clips && table && offsets && rects && workspace && (stream || capacity == 0),
+                 "%s: null clips, table, stream, offsets, rects or workspace", who);
+    GifDeltaArgs a;
+    a.clips = clips; a.clip_stride = clip_stride; a.frame_stride = frame_stride;
+    a.t = t; a.n = b * t; a.h = h; a.w = w;
+    a.band_rows = band_rows;
+    a.nb = (int)gif_bands(h, w, band_rows);
+    a.wstride = gif_band_words(gif_rect_band_max(h, w, band_rows));
+    a.table = table; a.stream = stream; a.capacity = capacity; a.offsets = offsets; a.rects = rects;
+    char* p = (char*)workspace + (size_t)b * 4 * GIF_NBINS * 8;    // (behind the palette's bins)
+    a.drect = (int*)p;                  p += 16 * (size_t)a.n;
+    a.choice = (int*)p;                 p += gif_align8(4 * (size_t)a.n);
+    a.bitoff = (long*)p;                p += 8 * 2 * (size_t)a.n * (a.nb + 1);
+    a.fsize = (long*)p;                 p += 8 * (size_t)a.n;
+    a.words = (unsigned*)p;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const long rows = gif_band_rows(w, band_rows);                 // no payload is written that is longer than the full frame's can be
+    const long full = rows < h ? rows : h, tail = h - (long)(a.nb - 1) * rows;
+    const long data_max = ((a.nb - 1) * gif_band_bits(full * w) + gif_band_bits(tail * w) + 7) >> 3;
+    const long per_frame = (data_max + GIF_THREADS - 1) / GIF_THREADS;
+    hipLaunchKernelGGL(gif_rect_kernel, dim3(limited_grid(a.n, hip_stream, 8)), dim3(GIF_THREADS), 0, st, a);
+    hipLaunchKernelGGL(gif_code_rect_kernel, dim3(limited_grid(2L * a.n * a.nb, hip_stream, 4)), dim3(WAVE), 0, st, a);
+    hipLaunchKernelGGL(gif_scan_delta_kernel, dim3(1), dim3(GIF_THREADS), 0, st, a);
+    hipLaunchKernelGGL(gif_stitch_delta_kernel, dim3(limited_grid(per_frame * a.n, hip_stream, 8)), dim3(GIF_THREADS), 0, st, a, per_frame);
     CCVS_CHECK_LAUNCH(who);
     return CCVS_OK;
 }

@@ -190,3 +190,46 @@ GIF_FN unsigned gif_data_byte(const unsigned* words, long wstride, const long* b
 // where byte j of the data stands in the payload, and the length byte in front of the sub-block that begins at j (j a multiple of 255)
 GIF_FN long gif_data_pos(long j) { return 2 + j + j / 255; }
 GIF_FN unsigned gif_block_len(long data, long j) { return (unsigned)(data - j < 255 ? data - j : 255); }
+
+// ---- changed-rectangle frames (include/ccvs_hip_output_gif_delta.h): a frame after its clip's first has two
+// candidates, the full frame F and the bounding rectangle D of the indices that differ from the frame before, whose unchanged indices
+// are GIF_TRANSPARENT.  Either is cut into bands of ITS rows and coded by the coder above; the shorter payload is written.
+#define GIF_TRANSPARENT 255          // the palette entry no box of the median cut gets (at most 255 boxes)
+
+struct GifRect {
+    int x0, y0, rw, rh;
+};
+GIF_FN GifRect gif_full_rect(int h, int w) {
+    GifRect r = {0, 0, w, h};
+    return r;
+}
+// the bounding rectangle of the changed indices, whose columns span x_min .. x_max and rows y_min .. y_max; none (x_max < x_min): the
+// frame's first pixel alone
+GIF_FN GifRect gif_changed_rect(int x_min, int x_max, int y_min, int y_max) {
+    GifRect r = {0, 0, 1, 1};
+    if (x_max >= x_min) {
+        r.x0 = x_min;
+        r.y0 = y_min;
+        r.rw = x_max - x_min + 1;
+        r.rh = y_max - y_min + 1;
+    }
+    return r;
+}
+// band b of a rectangle: its first row within the rectangle and its number of rows; index i of the band is the frame's pixel
+// (y0 + first row + i / rw, x0 + i % rw).  A rectangle has gif_bands(rh, rw, band_rows) bands, never more than its frame.
+GIF_FN int gif_rect_band_first(const GifRect& r, int band_rows, int b) { return b * gif_band_rows(r.rw, band_rows); }
+GIF_FN int gif_rect_band_count(const GifRect& r, int band_rows, int b) {
+    const int rows = gif_band_rows(r.rw, band_rows), r0 = b * rows;
+    return r0 + rows < r.rh ? rows : r.rh - r0;
+}
+GIF_FN long gif_rect_pixel(const GifRect& r, int w, int first_row, long i) {
+    return (long)(r.y0 + first_row + (int)(i / r.rw)) * w + r.x0 + (int)(i % r.rw);
+}
+// indices of the largest band of any rectangle of an h x w frame (at least; what the bands' words are sized for).  With band_rows
+// given it is the full frame's band.  With 0 a rectangle of rw <= 4096 columns has bands of (4096 / rw) rw <= 4096 indices -- more
+// than the full frame's where w does not divide 4096 -- and a wider one has bands of one row.
+GIF_FN long gif_rect_band_max(int h, int w, int band_rows) {
+    if (band_rows > 0) return (long)(band_rows < h ? band_rows : h) * w;
+    if (w > GIF_DEFAULT_BAND) return w;
+    return (long)h * w < GIF_DEFAULT_BAND ? (long)h * w : GIF_DEFAULT_BAND;
+}

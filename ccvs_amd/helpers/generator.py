@@ -633,6 +633,8 @@ class Generator:
         how = dict(video_format=None if fmt == "auto" else fmt, quality=getattr(self.opt, "video_quality", 90), return_clip=False,
                    subsampling=getattr(self.opt, "video_subsampling", "444"), optimize=bool(getattr(self.opt, "video_optimize", False)),
                    lz77=bool(getattr(self.opt, "video_lz77", False)))
+        if getattr(self.opt, "video_delta", False):                        # (ccvs_amd) --video_delta: the gif files' changed-rectangle frames
+            how["delta"] = True
         for name in ("real", "fake", "rec", "blur"):                       # generator.py:191-212
             item = out.get(name)
             if item is None:
@@ -661,7 +663,7 @@ class Generator:
         else:
             max_px = ops.flow_max(motion)
         fmt = how["video_format"]
-        tail = {k: how[k] for k in ("quality", "subsampling", "optimize", "lz77")}
+        tail = {k: how[k] for k in ("quality", "subsampling", "optimize", "lz77", "delta") if k in how}
         for suffix, u8 in zip(("_flow", "_occ"), ops.flow_render(motion, max_px)):
             host = u8 if fmt in ("avi", "apng", "gif") else u8.cpu()
             write_u8_clips(host, u8, u8.device, bs, global_iter, os.path.join(opt.result_path, name + suffix), opt.fps, fmt, **tail)
@@ -779,7 +781,8 @@ _SUBSAMPLING = {"444": 0, "422": 1, "420": 2}     # --video_subsampling -> the e
 
 
 def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, span, dataset, state=None, cat=None, idx=None,
-                     is_layout=False, video_format=None, quality=90, return_clip=True, subsampling="444", optimize=False, lz77=False):
+                     is_layout=False, video_format=None, quality=90, return_clip=True, subsampling="444", optimize=False, lz77=False,
+                     delta=False):
     """helpers/generator.py:285-333.  The clamp / rescale / uint8 / channels-last pack runs on the GPU.  video_format:
       None    mp4 when torchvision is importable, else .npy uint8 [T,H,W,3];
       "npy"   the arrays, whatever imports;
@@ -798,6 +801,10 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
               section 4.27) and the palettes and the coded bytes are what is copied out.  The frames are quantised (clips of at most 256
               colours in distinct 5-bit bins, as the flow and occlusion clips of --save_flow mostly are, are stored exactly), so the
               metrics and FVD commands do not read these files; `quality`, `subsampling`, `optimize` and `lz77` are not looked at.
+              delta: a frame after the first may be written as the rectangle of what changed against the frame before, with a
+              transparent index where nothing did, wherever that takes fewer bytes (`ops.gif_encode(delta=True)`, DESIGN.md section
+              4.29): what a player shows is palette[indices] all the same, from 255 colours instead of 256; the other formats do
+              not look at it.
     Returns the uint8 clip on the host; `return_clip=False` lets the "avi", "apng" and "gif" forms skip that copy where no state marker needs
     it (then only the compressed bytes cross to the host, and None is returned)."""
     if is_layout:
@@ -824,12 +831,13 @@ def save_video_batch(vid, bs, global_iter, path, fps, normalize, imagenet_norm, 
                     x, y = st[i, j]
                     u8[i, j] = draw_cross(u8[i, j], min(int(res * x), res - 1), min(int(res * y), res - 1))
             dev_u8 = None  # the marked clip is the one to write: "avi", "apng" and "gif" upload it again (rare and small)
-    write_u8_clips(u8, dev_u8, vid.device, bs, global_iter, path, fps, video_format, quality, subsampling, optimize, lz77, cat=cat, idx=idx)
+    write_u8_clips(u8, dev_u8, vid.device, bs, global_iter, path, fps, video_format, quality, subsampling, optimize, lz77, cat=cat, idx=idx,
+                   **({"delta": True} if delta else {}))
     return u8 if u8.device.type == "cpu" else None
 
 
 def write_u8_clips(u8, dev_u8, device, bs, global_iter, path, fps, video_format, quality=90, subsampling="444", optimize=False, lz77=False,
-                   cat=None, idx=None):
+                   cat=None, idx=None, delta=False):
     """The files of a packed uint8 batch [B, T, H, W, 3] in `save_video_batch`'s formats and names: its tail, which the flow and
     occlusion clips of --save_flow (already uint8 on the device, `ops.flow_render`) go through as well.  u8: the batch on the host --
     or on the device where the format is "avi" / "apng" / "gif", which read `dev_u8`, the batch on the device (None: u8 is uploaded to
@@ -857,7 +865,11 @@ def write_u8_clips(u8, dev_u8, device, bs, global_iter, path, fps, video_format,
     elif video_format == "gif":
         from ccvs_amd.tools import gif
         t, (h, w) = u8.size(1), u8.shape[2:4]
-        gbytes, off, palettes = ops.gif_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(device))
+        rects = None
+        if delta:
+            gbytes, off, palettes, rects = ops.gif_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(device), delta=True)
+        else:
+            gbytes, off, palettes = ops.gif_encode_to_host(dev_u8 if dev_u8 is not None else u8.to(device))
     for i in range(u8.size(0)):
         suffix = '' if cat is None else f'_{cat[i]}'
         suffix += '' if idx is None else f'_{idx[i]}'
@@ -867,7 +879,8 @@ def write_u8_clips(u8, dev_u8, device, bs, global_iter, path, fps, video_format,
         elif video_format == "apng":
             apng.write_apng(stem + ".png", [zbytes[off[k]:off[k + 1]] for k in range(i * t, (i + 1) * t)], fps, h, w)
         elif video_format == "gif":
-            gif.write_gif(stem + ".gif", [gbytes[off[k]:off[k + 1]] for k in range(i * t, (i + 1) * t)], palettes[i], fps, h, w)
+            gif.write_gif(stem + ".gif", [gbytes[off[k]:off[k + 1]] for k in range(i * t, (i + 1) * t)], palettes[i], fps, h, w,
+                          **({"rects": rects[i * t:(i + 1) * t]} if delta else {}))
         elif write_video is not None:
             write_video(stem + ".mp4", u8[i], fps)
         else:

@@ -57,6 +57,9 @@ GIF_SYMBOLS = ["ccvs_gif_workspace_bytes", "ccvs_gif_stream_bound", "ccvs_gif_pa
 # every symbol include/ccvs_hip_kv16.h declares (the token loop on a bf16 KV cache: append, attention, the step's launch chain; included by
 # ccvs_hip.h too; named apart from the `*_EXPORTS` lists for the same reason)
 KV16_SYMBOLS = ["ccvs_kv_append_bf16", "ccvs_attention_bf16", "ccvs_gpt_decode_step_bf16kv"]
+# every symbol include/ccvs_hip_output_gif_delta.h declares (the GIF output stage writing changed rectangles with a transparent index;
+# included by ccvs_hip.h too; named apart from the `*_EXPORTS` lists for the same reason)
+GIF_DELTA_SYMBOLS = ["ccvs_gif_palette_n", "ccvs_gif_delta_workspace_bytes", "ccvs_gif_encode_delta"]
 
 
 class ConvDesc(C.Structure):
@@ -169,6 +172,8 @@ def load():
     lib.ccvs_apng_lz_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_gif_workspace_bytes.restype = C.c_size_t
     lib.ccvs_gif_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.ccvs_gif_delta_workspace_bytes.restype = C.c_size_t
+    lib.ccvs_gif_delta_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_gif_stream_bound.restype = C.c_long
     lib.ccvs_gif_stream_bound.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
     lib.ccvs_png_decode_workspace_bytes.restype = C.c_size_t
@@ -247,6 +252,8 @@ def load():
         "ccvs_apng_encode_lz": [vp, C.c_long, i32, i32, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_gif_palette": [vp, C.c_long, C.c_long, i32, i32, i32, i32, vp, vp, vp, vp, vp],
         "ccvs_gif_encode": [vp, C.c_long, C.c_long, i32, i32, i32, i32, i32, vp, vp, C.c_long, vp, vp, vp],
+        "ccvs_gif_palette_n": [vp, C.c_long, C.c_long, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp],
+        "ccvs_gif_encode_delta": [vp, C.c_long, C.c_long, i32, i32, i32, i32, i32, vp, vp, C.c_long, vp, vp, vp, vp],
         "ccvs_zlib_inflate": [vp, C.c_long, vp, vp, i32, vp, C.c_long, vp, vp],
         "ccvs_png_decode": [vp, C.c_long, vp, vp, i32, i32, i32, vp, C.c_long, vp, vp, vp],
         "ccvs_lpips_prep": [vp, vp, i64, i64, C.POINTER(C.c_float), C.POINTER(C.c_float), vp],

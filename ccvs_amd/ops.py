@@ -1794,30 +1794,35 @@ def _gif_clips(who, u8):
     return clips, b, t, h, w, cs, fs
 
 
-def _gif_palette(L, clips, b, t, h, w, cs, fs, work):
+def _gif_palette(L, clips, b, t, h, w, cs, fs, work, max_colours=256):
     dev = clips.device
     palette = torch.empty((b, 256, 3), dtype=torch.uint8, device=dev)
     table = torch.empty((b, 32768), dtype=torch.uint8, device=dev)
     used = torch.empty(b, dtype=torch.int32, device=dev)
-    _lib.check(L.ccvs_gif_palette(_p(clips), cs, fs, b, t, h, w, _p(palette), _p(table), _p(used), _p(work), _stream()), "ccvs_gif_palette")
+    if max_colours == 256:
+        _lib.check(L.ccvs_gif_palette(_p(clips), cs, fs, b, t, h, w, _p(palette), _p(table), _p(used), _p(work), _stream()), "ccvs_gif_palette")
+    else:
+        _lib.check(L.ccvs_gif_palette_n(_p(clips), cs, fs, b, t, h, w, int(max_colours), _p(palette), _p(table), _p(used), _p(work), _stream()),
+                   "ccvs_gif_palette_n")
     return palette, table, used
 
 
-def gif_palette(u8_clips):
+def gif_palette(u8_clips, max_colours=256):
     """The colour tables of uint8 clips [B, T, H, W, 3] on the device (`ccvs_gif_palette`), one per clip from that
     clip's own pixels: (palette uint8 [B, 256, 3], table uint8 [B, 32768], used int32 [B]), all on the device.  The pixels are counted
     in 32768 bins of 5 bits per channel, median cut makes up to 256 boxes of the occupied bins, a box's mean colour is its palette
     entry (`used` of them; the rest are 0) and `table` gives every bin's entry: a pixel's index is table[(R >> 3) << 10 | (G >> 3) << 5 |
     B >> 3].  A [T, H, W, 3] input is one clip.  Views whose rows are dense and whose frame and clip strides hold a frame / a clip are
-    read in place.  Runs on the current stream; nothing is synchronised."""
+    read in place.  max_colours (2 .. 256): the median cut stops at so many boxes (`ccvs_gif_palette_n`; 255
+    leaves index 255 free for the changed-rectangle frames' transparency).  Runs on the current stream; nothing is synchronised."""
     _need_gpu(u8_clips)
     clips, b, t, h, w, cs, fs = _gif_clips("gif_palette", u8_clips)
     L = _lib.load()
     work = torch.empty(max(int(L.ccvs_gif_workspace_bytes(b, t, h, w, 0)), 8), dtype=torch.uint8, device=clips.device)
-    return _gif_palette(L, clips, b, t, h, w, cs, fs, work)
+    return _gif_palette(L, clips, b, t, h, w, cs, fs, work, max_colours)
 
 
-def gif_encode(u8_clips, band_rows=0, capacity=None, out=None):
+def gif_encode(u8_clips, band_rows=0, capacity=None, out=None, delta=False):
     """The GIF image data of uint8 clips [B, T, H, W, 3] on the device (`ccvs_gif_palette`, then `ccvs_gif_encode`, DESIGN.md section
     4.27): every clip's pixels are mapped to its own 256 colours (`gif_palette`) and every frame's indices are LZW-coded on the GPU and
     framed in sub-blocks -- what follows an image descriptor in a GIF file (`ccvs_amd.tools.gif` writes the container).  Returns
@@ -1826,7 +1831,10 @@ def gif_encode(u8_clips, band_rows=0, capacity=None, out=None):
     strides are handled as in `gif_palette`.  capacity: bytes of `stream` (None: a byte per pixel, which noise overflows); the offsets
     are complete also when offsets[n] > capacity, nothing at or beyond `capacity` is written, and the CALLER runs again with a larger one
     (`gif_encode_to_host` does; `ccvs_gif_stream_bound` always suffices).  out: optional uint8 stream to write into (its length is the
-    capacity).  Runs on the current stream; nothing is synchronised."""
+    capacity).  delta: changed-rectangle frames (`ccvs_gif_palette_n` at 255 colours, then `ccvs_gif_encode_delta`, DESIGN.md section
+    4.29): a frame after its clip's first is written as the rectangle of what changed against the frame before, index 255 transparent,
+    where that is fewer bytes; a fourth result, rects int32 [B T, 4], holds every written frame's x0, y0, width and height.  Runs on the
+    current stream; nothing is synchronised."""
     _need_gpu(u8_clips, out)
     clips, b, t, h, w, cs, fs = _gif_clips("gif_encode", u8_clips)
     n, band_rows = b * t, int(band_rows)
@@ -1838,6 +1846,13 @@ def gif_encode(u8_clips, band_rows=0, capacity=None, out=None):
         capacity = n * (2 + h * w + (h * w + 254) // 255)
     stream = out if out is not None else torch.empty(int(capacity), dtype=torch.uint8, device=clips.device)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=clips.device)
+    if delta:
+        work = torch.empty(max(int(L.ccvs_gif_delta_workspace_bytes(b, t, h, w, max(band_rows, 0))), 8), dtype=torch.uint8, device=clips.device)
+        palette, table, _ = _gif_palette(L, clips, b, t, h, w, cs, fs, work, 255)
+        rects = torch.empty((n, 4), dtype=torch.int32, device=clips.device)
+        _lib.check(L.ccvs_gif_encode_delta(_p(clips), cs, fs, b, t, h, w, band_rows, _p(table), _p(stream), int(capacity), _p(offsets),
+                                           _p(rects), _p(work), _stream()), "ccvs_gif_encode_delta")
+        return stream, offsets, palette, rects
     work = torch.empty(max(int(L.ccvs_gif_workspace_bytes(b, t, h, w, max(band_rows, 0))), 8), dtype=torch.uint8, device=clips.device)
     palette, table, _ = _gif_palette(L, clips, b, t, h, w, cs, fs, work)
     _lib.check(L.ccvs_gif_encode(_p(clips), cs, fs, b, t, h, w, band_rows, _p(table), _p(stream), int(capacity), _p(offsets), _p(work),
@@ -1845,15 +1860,22 @@ def gif_encode(u8_clips, band_rows=0, capacity=None, out=None):
     return stream, offsets, palette
 
 
-def gif_encode_to_host(u8_clips, band_rows=0):
+def gif_encode_to_host(u8_clips, band_rows=0, delta=False):
     """`gif_encode`, then its results on the host: (bytes of all frames' payloads, list of B T + 1 offsets, palettes uint8 numpy
     [B, 256, 3]).  Where the first run's stream is too small the offsets say by how much and a second run with that capacity is exact.
-    What crosses to the host is the offsets, offsets[n] coded bytes and 768 palette bytes per clip."""
-    stream, offsets, palette = gif_encode(u8_clips, band_rows)
+    What crosses to the host is the offsets, offsets[n] coded bytes and 768 palette bytes per clip.  delta: `gif_encode(delta=True)`;
+    a fourth result, the written rectangles as int32 numpy [B T, 4]."""
+    if not delta:
+        stream, offsets, palette = gif_encode(u8_clips, band_rows)
+        off = offsets.cpu().tolist()
+        if off[-1] > stream.numel():
+            stream, offsets, palette = gif_encode(u8_clips, band_rows, capacity=off[-1])
+        return stream[:off[-1]].cpu().numpy().tobytes(), off, palette.cpu().numpy()
+    stream, offsets, palette, rects = gif_encode(u8_clips, band_rows, delta=True)
     off = offsets.cpu().tolist()
     if off[-1] > stream.numel():
-        stream, offsets, palette = gif_encode(u8_clips, band_rows, capacity=off[-1])
-    return stream[:off[-1]].cpu().numpy().tobytes(), off, palette.cpu().numpy()
+        stream, offsets, palette, rects = gif_encode(u8_clips, band_rows, capacity=off[-1], delta=True)
+    return stream[:off[-1]].cpu().numpy().tobytes(), off, palette.cpu().numpy(), rects.cpu().numpy()
 
 
 # ------------------------------------------------------------------ the way back (include/ccvs_hip_decode.h)

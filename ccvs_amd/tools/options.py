@@ -120,11 +120,15 @@ class Options:
         # files are apng
         # gif -- animated GIF in 256 colours per clip, palette and LZW coding on the GPU (csrc/gif.hip); for showing: the frames are
         # quantised, and the metrics and FVD commands do not read these files; the four --video_* options below are ignored
+        # --video_delta: a gif frame after the first may be written as the rectangle of what changed against the frame before, with a
+        # transparent index where nothing did, wherever that is fewer bytes (csrc/gif.hip, DESIGN.md section 4.29: players show the same
+        # pixels, chosen from 255 colours instead of 256; never a larger frame); ignored unless the files are gif
         p.add_argument("--video_format", type=str, default="auto", choices=["auto", "npy", "avi", "apng", "gif"])
         p.add_argument("--video_quality", type=_jpeg_quality, default=90)
         p.add_argument("--video_subsampling", type=str, default="444", choices=["444", "422", "420"])
         _flag(p, "--video_optimize")
         _flag(p, "--video_lz77")
+        _flag(p, "--video_delta")
         # (ccvs_amd) where the PNG frames of a frame-folder dataset are decoded: host -- Pillow in the loader's threads, the uint8 frames
         # uploaded; gpu -- the files' zlib streams uploaded, inflated and un-filtered on the GPU (csrc/png_decode.hip; the same frames).
         # An item that is not all 8-bit RGB non-interlaced PNGs of one size is decoded on the host either way.

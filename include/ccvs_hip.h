@@ -517,6 +517,8 @@ int ccvs_resize_bilinear(const float* x, float* out, int64_t planes, int32_t H, 
 #include "ccvs_hip_output_gif.h"
 /* the token loop on a bfloat16 KV cache (append, attention, the decode step's launch chain), additive to ABI version 6, likewise */
 #include "ccvs_hip_kv16.h"
+/* the GIF output stage writing changed rectangles with a transparent index where that is smaller, additive to ABI version 6, likewise */
+#include "ccvs_hip_output_gif_delta.h"
 
 #ifdef __cplusplus
 }
